@@ -79,9 +79,13 @@ def parse_args(argv=None):
     ap.add_argument("--probes", action="store_true", help="also run the side probes earlier rounds' documents cite (all after the timed region): the same launches over ONE buffer set, "
                     "tools/mixceil, the input transposer alone and in front of the launch")
     ap.add_argument("--no-other-configs", action="store_true", help="default run only: skip the legs over BASELINE configs[2..4] (other_configs in the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed — records, masked rows and status words of a "
+                    "fixed, seeded sample of its strings (at most 64 MB, string-major) — as DIR/<name>.npy in float32 / float64, for comparing two builds output for output")
     ap.add_argument("--leg", action="store_true", help=argparse.SUPPRESS)     # one of the other_configs legs: a child of the default run
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # spawned by a bare --gpus N run
     args = ap.parse_args(argv)
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)
     args.argv = [a for a in argv if a != "--child"]
     return args
 
@@ -307,8 +311,8 @@ def measured_traffic(argv, dev_index):
     exe = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
     if not exe or under_profiler():
         return None
-    keep = [a for a in argv if a not in ("--no-spread", "--no-verify", "--no-cpu-baseline", "--eager")]
-    for flag in ("--steps", "--warmup", "--gpus", "--sets"):          # the child runs 3 eager launches on one device, one buffer set
+    keep = [a for a in argv if a not in ("--no-spread", "--no-verify", "--no-cpu-baseline", "--eager") and not a.startswith("--dump-outputs=")]
+    for flag in ("--steps", "--warmup", "--gpus", "--sets", "--dump-outputs"):          # the child runs 3 eager launches on one device, one buffer set
         while flag in keep:
             i = keep.index(flag)
             del keep[i:i + 2]
@@ -341,6 +345,59 @@ def measured_traffic(argv, dev_index):
 # ----------------------------------------------------------------------------------------------------------------
 # one rank
 # ----------------------------------------------------------------------------------------------------------------
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, out, B, M, D, pm, planes, shift=0, seed=0):
+    """--dump-outputs: the rows one launch wrote into `out` (records, masked, status) for a fixed, seeded sample of the batch's B strings, in string-major order
+    whatever the layout: records.npy (S, M, D) float64, masked.npy (S, M) float32, status.npy (S, 2) float64 (the u64 word's low and high 32 bits, exact),
+    strings.npy (S,) float64 (the sampled strings' indices in the batch).  `out` belongs to a buffer set that holds the batch rotated by `shift` strings
+    (torch.roll): batch string i lies at position (i + shift) % B, so the files do not depend on which set the launch wrote.  S = as many strings as fit
+    DUMP_BYTES, at most 4096."""
+    import numpy as np
+    import torch
+    import halo2_regex_amd as hra
+    S = max(1, min(B, 4096, DUMP_BYTES // (M * D * 8 + M * 4 + 24)))
+    idx = np.sort(np.random.default_rng(seed).choice(B, S, replace=False))
+    order = np.argsort((idx + shift) % B)
+    pos = ((idx + shift) % B)[order]                      # gathered in position order, put back in batch order below
+    rec, msk, st = out
+    q4, q8 = (M + 3) // 4, (M + 7) // 8
+    recs, msks = [], []
+    if not pm:
+        t = torch.from_numpy(pos).to(st.device)
+        recs.append(rec[t]); msks.append(msk[t])
+    else:
+        for blk in range(0, B, hra.PM_BLOCK):               # (position-major buffers are blocked by PM_BLOCK strings: the views of verify_timed_buffers)
+            nb = min(hra.PM_BLOCK, B - blk)
+            sel = pos[(pos >= blk) & (pos < blk + nb)] - blk
+            if len(sel) == 0:
+                continue
+            t = torch.from_numpy(sel).to(st.device)
+            if planes:
+                R = len(rec) // D
+                slots = (q4 + R - 1) // R
+                per_def = []
+                for d_ in range(D):
+                    qs = [rec[r_ * D + d_].view(-1)[blk * slots * 4:][:slots * nb * 4].view(slots, nb, 4)[:, t] for r_ in range(R)]
+                    qq = qs[0] if R == 1 else torch.stack(qs, dim=1).reshape(slots * R, len(sel), 4)[:q4]
+                    per_def.append(qq.permute(1, 0, 2).reshape(len(sel), q4 * 4)[:, :M])
+                recs.append(torch.stack(per_def, dim=2))
+            else:
+                recs.append(rec.view(-1)[blk * q4 * D * 4:][:q4 * D * nb * 4].view(q4, D, nb, 4)[:, :, t].permute(2, 0, 3, 1).reshape(len(sel), q4 * 4, D)[:, :M])
+            msks.append(msk.view(-1)[blk * q8 * 8:][:q8 * nb * 8].view(q8, nb, 8)[:, t].permute(1, 0, 2).reshape(len(sel), q8 * 8)[:, :M])
+    r, m, s = np.empty((S, M, D), np.uint32), np.empty((S, M), np.uint16), np.empty(S, np.uint64)
+    r[order] = torch.cat(recs).cpu().numpy().view(np.uint32)
+    m[order] = torch.cat(msks).cpu().numpy().view(np.uint16)
+    s[order] = st[torch.from_numpy(pos).to(st.device)].cpu().numpy().view(np.uint64)
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "records.npy"), r.astype(np.float64))
+    np.save(os.path.join(dirname, "masked.npy"), m.astype(np.float32))
+    np.save(os.path.join(dirname, "status.npy"), np.stack([s & np.uint64(0xffffffff), s >> np.uint64(32)], axis=1).astype(np.float64))
+    np.save(os.path.join(dirname, "strings.npy"), idx.astype(np.float64))
+    return {"dir": dirname, "strings": int(S), "of": int(B)}
+
+
 def workload(args):
     import numpy as np
     import halo2_regex_amd as hra
@@ -587,6 +644,10 @@ def run_rank(args, rank, world, device_index, barrier):
     elapsed = time.perf_counter() - t0
     barrier()
     kern_ms = ev0.elapsed_time(ev1) / args.steps      # average launch duration, HIP events on the launch stream
+    dumped = None
+    if args.dump_outputs and rank == 0:                   # the last timed step's outputs, before anything below overwrites them
+        last = (args.steps - 1) % nsets
+        dumped = dump_outputs(args.dump_outputs, sets[last][2], B, M, D, pm, planes, shift=last * shift)
 
     # What the verification reads must have been written by the timed work: poison the outputs — status words entirely; records and
     # masked rows at one element per ~64 KiB (filling the 3 GB of buffers outright would take seconds of host-visible time for nothing:
@@ -615,6 +676,8 @@ def run_rank(args, rank, world, device_index, barrier):
            "warmup_effective": {"launches": warm_launches, "eager_steps": args.warmup, "graph_replays": (warm_launches - args.warmup) // max(args.steps, 1),
                                 "ms": warm_ms, "note": "every launch of this workload that ran before the timed region (the --warmup eager steps + the untimed replays of the K-step graph), "
                                                        "and the wall time from the first of them to the barrier in front of the timed region (includes graph capture)"}}
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
     profiled = under_profiler()
     o = None
     if (not args.no_verify and (rank == 0 or args.verify_all_ranks)) or (rank == 0 and not args.no_cpu_baseline):
@@ -1048,6 +1111,8 @@ def aggregate(per_rank, args):
         line["end_to_end_host"] = r0["end_to_end_host"]
     if r0.get("warmup_effective"):
         line["warmup_effective"] = r0["warmup_effective"]
+    if r0.get("dumped_outputs"):
+        line["dumped_outputs"] = r0["dumped_outputs"]
     return line
 
 

@@ -113,11 +113,11 @@ def test_invalid_transition_panics_with_the_reference_message(hra):
     assert _cfg(hra, CFG_1, 64).derive_states(b"").tolist() == [[0]]
 
 
-def test_cpp_host_mirror_runs_the_reference_test(hra):
+def test_cpp_host_mirror_runs_the_reference_test(hra, tmp_path):
     """tests/host_cpp/test_host.cpp = test_substr_pass1 (lib.rs:1067-1092) through csrc/hrx_host.hpp"""
     import subprocess
     from oracle_lib import ROOT
-    exe = "/tmp/hrx_test_host_gpu"
+    exe = str(tmp_path / "hrx_test_host_gpu")
     csrc = os.path.join(ROOT, "halo2_regex_amd", "csrc")
     subprocess.check_call(["g++", "-std=c++17", "-O1", os.path.join(ROOT, "tests", "host_cpp", "test_host.cpp"), "-o", exe,
                            "-L" + csrc, "-lhrx", "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib"])
@@ -147,12 +147,12 @@ def test_chars_to_position_major_device_equals_the_layout_definition(hra, B, str
         assert torch.equal(x, y)
 
 
-def test_c_struct_entry_points_on_the_device(hra):
+def test_c_struct_entry_points_on_the_device(hra, tmp_path):
     """tests/host_c/test_push_structs.c (the Rust binding's call sequence: shuffled hrx_defs_push_allstr entries with explicit line indices, a duplicate key,
     hrx_defs_push_substr) with the witness rows of both configs computed on the device"""
     import subprocess
     from oracle_lib import ROOT
-    exe = "/tmp/hrx_test_push_structs_gpu"
+    exe = str(tmp_path / "hrx_test_push_structs_gpu")
     csrc = os.path.join(ROOT, "halo2_regex_amd", "csrc")
     subprocess.check_call(["gcc", "-std=c11", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "host_c", "test_push_structs.c"), "-o", exe,
                            "-L" + csrc, "-lhrx", "-Wl,-rpath," + csrc, "-Wl,-rpath,/opt/rocm/lib", "-L/opt/rocm/lib"])
