@@ -44,6 +44,10 @@ static int describe_set(const DefsSet &s, int layout, size_t B, size_t M, int nu
     else std::snprintf(name, sizeof name, "hrx::witness_kernel<%u, %s, %s>", a.D, tf[(M % 8) == 0], tf[li.gtab]);
     std::snprintf(line, sizeof line, "%s grid=%d waves=%d ring=%d lds=%zu%s", name, li.grid, li.waves_per_wg, li.nslots, li.lds_bytes, li.dyn ? " groups=dynamic" : "");
     out = line;
+    if (li.split == 0) {      // the one-wave kernel: strings per wave (64, 32 with kDbgGroups32, halved while the batch would leave CUs without a wave)
+        std::snprintf(line, sizeof line, " gs=%u", a.gs);
+        out += line;
+    }
     if (li.spec_tiles) {
         std::snprintf(line, sizeof line, " chunked=%dx%d tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind", li.spec_chunks, li.spec_tiles);
         out += line;

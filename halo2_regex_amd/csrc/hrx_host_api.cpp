@@ -7,6 +7,7 @@
 #include <condition_variable>
 #include <system_error>
 
+#include "hrx_host_split.hpp"
 #include "hrx_host_walk.hpp"
 
 using namespace hrx;
@@ -275,6 +276,8 @@ int hrx_witness_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, co
                 if (fig <= 1.5 * best) way = cand;
             }
         }
+        // (a batch of few long strings has no two parts to give: the faster of the two single ways takes it whole, and no split figure is recorded)
+        if (way == kSplit && B < kSplitMinStrings) way = hr.host_alone > 0 && hr.host_alone < hr.dev_alone ? kHost : kDev;
     }
     hrx_host_route_report &rep = ctx->last_host;
     auto finish = [&](int did, size_t bs, size_t hn, double dev_ms, double host_ms, size_t hthreads) {
@@ -325,9 +328,9 @@ int hrx_witness_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, co
     // ---- both at once: all host cores but two (the staging thread and this one keep the device part fed)
     if (int rc = check_strides()) return rc;
     const double h = hr.host_ns_per_row, d = hr.dev_ns_per_row;
-    double f_dev = (h > 0 && d > 0) ? h / (h + d) : 0.5;
-    f_dev = std::min(15.0 / 16, std::max(1.0 / 16, f_dev));
-    const size_t bs = std::max<size_t>(64, (size_t)((double)B * f_dev) / 64 * 64), hn = B - bs;
+    HostSplit part;
+    if (!host_split(B, (h > 0 && d > 0) ? h / (h + d) : 0.5, part)) return fail(HRX_ERR_STATE, "internal: a split route for a batch too small to split");
+    const size_t bs = part.device, hn = part.host;
     const size_t hthreads = avail > 3 ? avail - 2 : 1;
     double host_ms = 0.0, dev_ms = 0.0;
     std::thread walker;

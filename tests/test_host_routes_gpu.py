@@ -57,6 +57,39 @@ def test_the_three_host_routes_give_identical_rows(hra, oracle, names):
     assert cl.get_option(hra.OPT_HOST_ROUTE) == hra.HOST_ROUTE_AUTO
 
 
+@pytest.mark.parametrize("B", [1, 32, 63, 64, 65])
+def test_auto_route_small_batches_of_long_strings(hra, oracle, B):
+    """AUTO with fewer strings than a split needs but B x M >= 2^22 rows (the split threshold): the calls that would split (3 and 4) take one way whole.  The split
+    once computed its device part as max(64, ...) and the host part as B minus it: for B < 64 the host part wrapped around and walked far past the caller's
+    buffers.  Six calls on one context; every call's rows against the oracle, every report's two parts sum to B, no split figure is ever recorded."""
+    from halo2_regex_amd import synth
+    M = ((1 << 22) + B - 1) // B
+    M = (M + 15) // 16 * 16
+    assert B * M >= 1 << 22
+    chars, lens = synth.regex1_planted(B, M - 1, seed=B, stride=M)
+    chars[0, M - 1] = chars[0, M - 2]
+    lens[0] = M                                     # full length
+    if B > 1:
+        lens[1] = M + 1                             # status 3
+        lens[B - 1] = int(np.random.default_rng(B).integers(0, M))
+        chars[B // 2, M // 2] = 200                 # an undefined transition
+    cfg = _cfg(hra, CFG_1, M)
+    assert cfg.get_option(hra.OPT_HOST_ROUTE) == hra.HOST_ROUTE_AUTO
+    orec, omsk, ost = OracleDefs.from_files(oracle, CFG_1).witness_batch(chars, lens, M, threads=min(16, os.cpu_count() or 1))
+    ok = (ost & np.uint64(0xff)) == 0
+    assert ok.any()
+    routes = []
+    for call in range(6):
+        rec, msk, st = cfg.witness_batch_host(chars, lens)
+        rep = cfg.host_route_report()
+        routes.append(rep["route"])
+        assert rep["device_strings"] + rep["host_strings"] == B, (call, rep)
+        assert rep["route"] in (hra.HOST_ROUTE_DEVICE, hra.HOST_ROUTE_HOST) and rep["split_ns_per_row"] == 0, (call, rep)
+        assert np.array_equal(st, ost), call
+        assert np.array_equal(rec[ok], orec[ok]) and np.array_equal(msk[ok], omsk[ok]), call
+    assert routes[:3] == [hra.HOST_ROUTE_DEVICE, hra.HOST_ROUTE_DEVICE, hra.HOST_ROUTE_HOST]
+
+
 def test_host_route_options_are_checked(hra):
     cfg = _cfg(hra, CFG_1, 64)
     with pytest.raises(hra.HrxError):
