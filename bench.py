@@ -14,6 +14,11 @@ N > 1 runs one process per GPU either way:
     overrides the rank -> device map), they rendezvous over gloo on 127.0.0.1 for the barrier and hand their
     (rows, elapsed) back over a pipe — the data path runs without RCCL.
 Rank 0 (or the parent) prints ONE JSON line: `value` = rows of all ranks / max-over-ranks elapsed of the K timed steps.
+
+A plain run does only what that line's headline needs: it sets up, warms up, times the K steps, writes --dump-outputs if asked and
+prints the line.  --full adds everything else after the timed region, as separate measurements: the comparison of the timed buffers
+with the oracle, the per-step spread, the no-compute and other side figures, the rocprofv3 --pmc traffic passes, the CPU baselines
+and, on the default workload, the legs over BASELINE configs[2..4] (other_configs).
 """
 import argparse
 import json
@@ -48,9 +53,11 @@ def parse_args(argv=None):
     ap.add_argument("--untimed-replays", type=int, default=0, help="untimed replays of the K-step graph before the timed one (default: ~100 ms of them)")
     ap.add_argument("--substr-pairs", type=int, default=200, help="dfa256: transitions in the random substring definition")
     ap.add_argument("--substr-defs", type=int, default=1, help="dfa256: substring definitions of the random DFA (SURVEY §8d cfg 5: 1-2), --substr-pairs tagged pairs each")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-verify", action="store_true", help="skip the comparison of the timed buffers with the oracle")
-    ap.add_argument("--no-spread", action="store_true", help="skip the extra replays that give the per-step spread")
+    ap.add_argument("--full", action="store_true", help="after the timed region also verify the timed buffers against the oracle and run every other measurement "
+                    "(spread, side probes, --pmc traffic, CPU baselines, other_configs); the --no-* options below leave parts of it out")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-verify", action="store_true", help="--full: skip the comparison of the timed buffers with the oracle")
+    ap.add_argument("--no-spread", action="store_true", help="--full: skip the extra replays that give the per-step spread (and the probes that follow them)")
     ap.add_argument("--eager", action="store_true", help="launch the timed steps one by one instead of replaying a HIP graph of them")
     ap.add_argument("--dense", action="store_true", help="string-major: power-of-two pitches (M rows per string, n rounded to 16 "
                     "bytes) instead of hrx_recommended_pitches")
@@ -63,8 +70,8 @@ def parse_args(argv=None):
     ap.add_argument("--scaling", choices=["weak", "strong"], default="weak", help="weak: --batch strings PER GPU; strong: --batch strings IN TOTAL, sharded by "
                     "string index over the ranks (hrx_shard_range) — the BASELINE multi-GPU configs: --config headers3 --batch 262144 --len 32768 --rows 32768, "
                     "--config dfa256 --batch 1048576 --len 4096 --rows 4096")
-    ap.add_argument("--verify-all-ranks", action="store_true", help="every rank compares its own timed buffers with the oracle (default: rank 0)")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the two rocprofv3 --pmc child passes that measure the launch's HBM traffic (roofline.traffic)")
+    ap.add_argument("--verify-all-ranks", action="store_true", help="--full: every rank compares its own timed buffers with the oracle (default: rank 0)")
+    ap.add_argument("--no-pmc", action="store_true", help="--full: skip the two rocprofv3 --pmc child passes that measure the launch's HBM traffic (roofline.traffic)")
     ap.add_argument("--distinct", type=int, default=0, help="generate this many DISTINCT strings and build the batch from rotated copies of them, block after block "
                     "(0 = every string of the batch distinct).  Planting text into 2^20 strings on the host takes minutes; the oracle then walks the distinct "
                     "strings once and EVERY string of every buffer set is compared with the rows of the string it is a copy of")
@@ -76,14 +83,17 @@ def parse_args(argv=None):
                     "with one group per workgroup; the line carries it in config.ctx_options")
     ap.add_argument("--planes-stand-in", action="store_true", help="--planes: the allocator chooses with launches over a constant stand-in input (hrx_alloc_output_planes) instead of this "
                     "run's batch (hrx_alloc_output_planes_for_batch)")
-    ap.add_argument("--probes", action="store_true", help="also run the side probes earlier rounds' documents cite (all after the timed region): the same launches over ONE buffer set, "
+    ap.add_argument("--probes", action="store_true", help="--full: also run the side probes earlier rounds' documents cite (all after the timed region): the same launches over ONE buffer set, "
                     "tools/mixceil, the input transposer alone and in front of the launch")
-    ap.add_argument("--no-other-configs", action="store_true", help="default run only: skip the legs over BASELINE configs[2..4] (other_configs in the line)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full on the default workload: skip the legs over BASELINE configs[2..4] (other_configs in the line)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps write what the last one computed — records, masked rows and status words of a "
                     "fixed, seeded sample of its strings (at most 64 MB, string-major) — as DIR/<name>.npy in float32 / float64, for comparing two builds output for output")
     ap.add_argument("--leg", action="store_true", help=argparse.SUPPRESS)     # one of the other_configs legs: a child of the default run
     ap.add_argument("--child", action="store_true", help=argparse.SUPPRESS)   # spawned by a bare --gpus N run
     args = ap.parse_args(argv)
+    for flag, on in (("--probes", args.probes), ("--verify-all-ranks", args.verify_all_ranks)):
+        if on and not args.full:
+            ap.error("%s runs after the timed region of a --full run only" % flag)
     if args.dump_outputs:
         args.dump_outputs = os.path.abspath(args.dump_outputs)
     args.argv = [a for a in argv if a != "--child"]
@@ -311,8 +321,8 @@ def measured_traffic(argv, dev_index):
     exe = shutil.which("rocprofv3") or ("/opt/rocm/bin/rocprofv3" if os.path.exists("/opt/rocm/bin/rocprofv3") else None)
     if not exe or under_profiler():
         return None
-    keep = [a for a in argv if a not in ("--no-spread", "--no-verify", "--no-cpu-baseline", "--eager") and not a.startswith("--dump-outputs=")]
-    for flag in ("--steps", "--warmup", "--gpus", "--sets", "--dump-outputs"):          # the child runs 3 eager launches on one device, one buffer set
+    keep = [a for a in argv if a not in ("--full", "--probes", "--verify-all-ranks", "--eager") and not a.startswith("--dump-outputs=")]
+    for flag in ("--steps", "--warmup", "--gpus", "--sets", "--dump-outputs"):          # the child: a plain run of 3 eager launches on one device, one buffer set
         while flag in keep:
             i = keep.index(flag)
             del keep[i:i + 2]
@@ -322,7 +332,7 @@ def measured_traffic(argv, dev_index):
             tmp = tempfile.mkdtemp(prefix="hrx_pmc_", dir="/tmp")
             env = dict(os.environ, TMPDIR="/tmp", HIP_VISIBLE_DEVICES=physical_device(dev_index))
             cmd = [exe, "--pmc", counter, "--output-format", "csv", "-d", tmp, "-o", "r1", "--", sys.executable, os.path.abspath(__file__)] + keep + \
-                  ["--eager", "--steps", "3", "--warmup", "1", "--sets", "1", "--no-cpu-baseline", "--no-verify", "--no-spread", "--no-pmc"]
+                  ["--eager", "--steps", "3", "--warmup", "1", "--sets", "1"]
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd="/tmp")
             vals = []
             for f in glob.glob(os.path.join(tmp, "**", "*counter_collection.csv"), recursive=True):
@@ -535,6 +545,8 @@ def run_rank(args, rank, world, device_index, barrier):
     # are the rotated oracle rows of set 0.
     shift = (B // nsets + 37) % B if nsets > 1 else 0
     sets, placement, sm_sets = [], [], []
+    # (kept in a plain run too, where nothing reads them: they are the rolled inputs themselves, no copy, and keeping them means a plain run and a
+    # --full one allocate the timed buffers in the same order)
     keep_sm = pm and world == 1 and not args.no_spread and not args.leg and nsets * B * stride <= (4 << 30)
     for r in range(world):        # one rank at a time: the placement search times memory traffic
         if r == rank:
@@ -649,6 +661,38 @@ def run_rank(args, rank, world, device_index, barrier):
         last = (args.steps - 1) % nsets
         dumped = dump_outputs(args.dump_outputs, sets[last][2], B, M, D, pm, planes, shift=last * shift)
 
+    res = {"rank": rank, "device": device_index, "rows": rows_per_step * args.steps, "elapsed_s": elapsed, "avg_launch_ms": kern_ms,
+           "debug_flags": dbg or None, "numa_node": numa, "strings": B, "shard_begin": b_begin,
+           "warmup_effective": {"launches": warm_launches, "eager_steps": args.warmup, "graph_replays": (warm_launches - args.warmup) // max(args.steps, 1),
+                                "ms": warm_ms, "note": "every launch of this workload that ran before the timed region (the --warmup eager steps + the untimed replays of the K-step graph), "
+                                                       "and the wall time from the first of them to the barrier in front of the timed region (includes graph capture)"}}
+    if dumped is not None:
+        res["dumped_outputs"] = dumped
+    res["desc"] = desc
+    res["placement"] = placement
+    res["library"] = os.path.realpath(hra.LIB_PATH)
+    res["nsets"] = nsets
+    res["config"] = {"workload": "%s DFA (D=%d), %d x %d-byte strings per GPU (n=%d chars, M=%d witness rows), %s"
+                                 % (label, D, B, stride, n, M, "uniform noise over the %s%s%s" % (alphabet, " + planted match" if planted else "",
+                                    "" if nd == B else "; %d distinct strings, the batch = %d blocks of them, block j rotated by %d j strings" % (nd, (B + nd - 1) // nd, sb))),
+                     "batch_per_gpu": B, "n": n, "max_chars_size": M, "defs": D, "rows_counted": "sum of n (character positions)", "ctx_options": list(args.ctx_option),
+                     "buffers": ("HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR with RECORD PLANES (blocks of 65536 strings): chars [%d/16][B][16], %s, "
+                                 "masked [M/8][B][8] (include/hrx.h hrx_witness_batch_device_planes); the %d + 1 output buffers from "
+                                 "hrx_alloc_output_planes (each in a neighbourhood of the device memory of its own)" % (stride, "every def's records [M/4][B][4] in a buffer of its own" if D > 1 else
+                                 ("the one def's records in two ROW STRIPES [M/8][B][4] (quad q of a string in stripe q % 2 at slot q / 2)" if args.stripes == 2 else "the one def's records [M/4][B][4]"),
+                                 D if D > 1 else args.stripes)) if planes else
+                                ("HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR (blocks of 65536 strings): chars [%d/16][B][16], records "
+                                 "[M/4][D][B][4], masked [M/8][B][8] (include/hrx.h); outputs from hrx_alloc_outputs_position_major (placement-aware "
+                                 "from 128 MiB of records on, two plain allocations below)" % stride) if pm else
+                                ("string-major; input stride %d B, records pitch %d rows, masked pitch %d rows" % (stride, rec_pitch, msk_pitch)),
+                     "buffer_sets": "%d input / output buffer sets, step i runs on set i %% %d (set k = the batch rotated by %d k strings): nothing a launch touches "
+                                    "was touched by the previous %d launches, so the 256-MB Infinity Cache holds none of it" % (nsets, nsets, shift, nsets - 1)
+                                    if nsets > 1 else "one buffer set, re-processed every step",
+                     "sharding": "by string index, no collective", "launch_mode": launch_mode}
+    res["D"], res["rows_per_step"] = D, rows_per_step
+    if not args.full:                                     # a plain run: the line's headline is all it measures
+        return res
+
     # What the verification reads must have been written by the timed work: poison the outputs — status words entirely; records and
     # masked rows at one element per ~64 KiB (filling the 3 GB of buffers outright would take seconds of host-visible time for nothing:
     # a launch that skipped a string, a tile or a plane shows at these spots as surely) — and replay the SAME executable graph (or the same
@@ -671,13 +715,6 @@ def run_rank(args, rank, world, device_index, barrier):
         st = sets[k][2][2].cpu().numpy().view(np.uint64)
         assert ((st & np.uint64(0xff)) == 0).all(), "status != ok in the bench workload (buffer set %d)" % k
 
-    res = {"rank": rank, "device": device_index, "rows": rows_per_step * args.steps, "elapsed_s": elapsed, "avg_launch_ms": kern_ms,
-           "debug_flags": dbg or None, "numa_node": numa, "strings": B, "shard_begin": b_begin,
-           "warmup_effective": {"launches": warm_launches, "eager_steps": args.warmup, "graph_replays": (warm_launches - args.warmup) // max(args.steps, 1),
-                                "ms": warm_ms, "note": "every launch of this workload that ran before the timed region (the --warmup eager steps + the untimed replays of the K-step graph), "
-                                                       "and the wall time from the first of them to the barrier in front of the timed region (includes graph capture)"}}
-    if dumped is not None:
-        res["dumped_outputs"] = dumped
     profiled = under_profiler()
     o = None
     if (not args.no_verify and (rank == 0 or args.verify_all_ranks)) or (rank == 0 and not args.no_cpu_baseline):
@@ -958,28 +995,6 @@ def run_rank(args, rank, world, device_index, barrier):
             del gi, il_sets
         except Exception as e:                                   # a probe must never break the bench line
             sys.stderr.write("interleaved-layout comparison failed: %s\n" % e)
-    res["desc"] = desc
-    res["placement"] = placement
-    res["library"] = os.path.realpath(hra.LIB_PATH)
-    res["nsets"] = nsets
-    res["config"] = {"workload": "%s DFA (D=%d), %d x %d-byte strings per GPU (n=%d chars, M=%d witness rows), %s"
-                                 % (label, D, B, stride, n, M, "uniform noise over the %s%s%s" % (alphabet, " + planted match" if planted else "",
-                                    "" if nd == B else "; %d distinct strings, the batch = %d blocks of them, block j rotated by %d j strings" % (nd, (B + nd - 1) // nd, sb))),
-                     "batch_per_gpu": B, "n": n, "max_chars_size": M, "defs": D, "rows_counted": "sum of n (character positions)", "ctx_options": list(args.ctx_option),
-                     "buffers": ("HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR with RECORD PLANES (blocks of 65536 strings): chars [%d/16][B][16], %s, "
-                                 "masked [M/8][B][8] (include/hrx.h hrx_witness_batch_device_planes); the %d + 1 output buffers from "
-                                 "hrx_alloc_output_planes (each in a neighbourhood of the device memory of its own)" % (stride, "every def's records [M/4][B][4] in a buffer of its own" if D > 1 else
-                                 ("the one def's records in two ROW STRIPES [M/8][B][4] (quad q of a string in stripe q % 2 at slot q / 2)" if args.stripes == 2 else "the one def's records [M/4][B][4]"),
-                                 D if D > 1 else args.stripes)) if planes else
-                                ("HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR (blocks of 65536 strings): chars [%d/16][B][16], records "
-                                 "[M/4][D][B][4], masked [M/8][B][8] (include/hrx.h); outputs from hrx_alloc_outputs_position_major (placement-aware "
-                                 "from 128 MiB of records on, two plain allocations below)" % stride) if pm else
-                                ("string-major; input stride %d B, records pitch %d rows, masked pitch %d rows" % (stride, rec_pitch, msk_pitch)),
-                     "buffer_sets": "%d input / output buffer sets, step i runs on set i %% %d (set k = the batch rotated by %d k strings): nothing a launch touches "
-                                    "was touched by the previous %d launches, so the 256-MB Infinity Cache holds none of it" % (nsets, nsets, shift, nsets - 1)
-                                    if nsets > 1 else "one buffer set, re-processed every step",
-                     "sharding": "by string index, no collective", "launch_mode": launch_mode}
-    res["D"], res["rows_per_step"] = D, rows_per_step
     if world == 1:
         del sets
         torch.cuda.empty_cache()
@@ -1195,8 +1210,8 @@ def spawn_children(args, argv, timeout_s=3600):
     return aggregate(results, args)
 
 
-# The BASELINE configs other than the one the metric is quoted on, at their per-GPU sizes: each runs as a child of the default single-GPU run AFTER the headline's
-# timed region, verification and probes, through the same code path (rotating buffer sets, the K steps replayed as one HIP graph, every string of every
+# The BASELINE configs other than the one the metric is quoted on, at their per-GPU sizes: each runs as a --full child of the default single-GPU --full run AFTER the
+# headline's timed region, verification and probes, through the same code path (rotating buffer sets, the K steps replayed as one HIP graph, every string of every
 # set compared with the oracle, hrx_traffic_pass_device over the same buffers), and is condensed into the line's `other_configs`.
 OTHER_CONFIGS = [
     ("configs[2]: regex2_test + regex3_test with substr extraction, 2^20 x 2048-byte strings, 1 MI355X",
@@ -1241,7 +1256,7 @@ def other_config_legs(dev_index, timeout_s=600):
     for name, argv in OTHER_CONFIGS:
         t0 = time.time()
         try:
-            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--leg", "--no-cpu-baseline", "--no-pmc"], capture_output=True, text=True,
+            r = subprocess.run([sys.executable, os.path.abspath(__file__)] + argv + ["--leg", "--full", "--no-cpu-baseline", "--no-pmc"], capture_output=True, text=True,
                                timeout=timeout_s, env=env)
             lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
             if r.returncode != 0 or not lines:
@@ -1313,7 +1328,7 @@ def main(argv=None):
         return
     res = run_rank(args, 0, 1, 0, lambda: None)
     line = aggregate([res], args)
-    if is_default_workload(args) and not args.no_other_configs:
+    if is_default_workload(args) and args.full and not args.no_other_configs:
         line["other_configs"] = other_config_legs(0)
     emit(line)
 

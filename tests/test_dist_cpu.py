@@ -84,6 +84,19 @@ def test_aggregate_of_a_bare_multi_gpu_run():
     assert line["roofline"]["bytes_per_row"] == 11 and line["roofline"]["algorithmic_bytes_per_launch"] == 1100
 
 
+def test_plain_run_and_full_options():
+    """a plain bench.py run measures the headline only; the options that act after the timed region of a --full run are refused without --full"""
+    import pytest
+    import bench
+    assert bench.parse_args([]).full is False
+    a = bench.parse_args(["--full", "--probes", "--verify-all-ranks"])
+    assert a.full and a.probes and a.verify_all_ranks
+    assert not bench.parse_args(["--no-verify", "--no-spread", "--no-pmc", "--no-cpu-baseline", "--no-other-configs"]).full
+    for flag in ("--probes", "--verify-all-ranks"):
+        with pytest.raises(SystemExit):
+            bench.parse_args([flag])
+
+
 def test_cpp_host_mirror_builds_and_runs(tmp_path):
     exe = str(tmp_path / "hrx_test_host")
     csrc = os.path.join(ROOT, "halo2_regex_amd", "csrc")

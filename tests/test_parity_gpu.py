@@ -1569,7 +1569,7 @@ def test_bench_runs_bare_with_two_ranks_on_one_device():
     env = dict(os.environ, HRX_BENCH_DEVICES="0,0")
     env.pop("HRX_DEBUG_FLAGS", None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "10", "--warmup", "2", "--batch", "16384",
-                          "--no-cpu-baseline", "--no-spread"], capture_output=True, text=True, env=env, timeout=600)
+                          "--full", "--no-cpu-baseline", "--no-spread"], capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and len(line["per_rank"]) == 2
@@ -1589,7 +1589,7 @@ def test_bench_strong_scaling_shards_one_job_over_the_ranks():
     env = dict(os.environ, HRX_BENCH_DEVICES="0,0")
     env.pop("HRX_DEBUG_FLAGS", None)
     common = ["--steps", "6", "--warmup", "2", "--config", "headers3", "--batch", "6000", "--len", "2000", "--rows", "2048", "--sets", "2",
-              "--no-cpu-baseline", "--no-spread", "--no-pmc"]
+              "--full", "--no-cpu-baseline", "--no-spread", "--no-pmc"]
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--scaling", "strong", "--verify-all-ranks"] + common,
                          capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-3000:]

@@ -2,7 +2,7 @@
 # cfg 5 position-major, two library builds alternating on ONE lease (leases differ by +-3 %): tools/ab_cfg5_libs.sh <other .so> [rounds]
 cd "$(dirname "$0")/.." || exit 1
 OTHER=$1; N=${2:-3}
-B="python3 bench.py --config dfa256 --len 4095 --rows 4096 --warmup 3 --no-cpu-baseline --no-pmc --no-spread"
+B="python3 bench.py --config dfa256 --len 4095 --rows 4096 --warmup 3 --full --no-cpu-baseline --no-pmc --no-spread"
 run() { echo -n "$1: "; env $2 $B $3 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d['roofline']

@@ -5,7 +5,7 @@ OTHER=$1; N=${2:-2}
 P='import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]
 print("ms/step %.4f frac %.3f verified %s" % (d["ms_per_step"], r["frac"], (d.get("verified") or {}).get("bit_exact")))'
-B="python3 bench.py --no-cpu-baseline --no-pmc --no-spread"
+B="python3 bench.py --full --no-cpu-baseline --no-pmc --no-spread"
 run() { echo -n "$1 | $2: "; shift; local lib=$1; shift; if [ "$lib" = other ]; then HRX_LIB_PATH=$OTHER timeout 400 $B --allow-debug-flags "$@" 2>/dev/null | python3 -c "$P"; else timeout 400 $B "$@" 2>/dev/null | python3 -c "$P"; fi; }
 for i in $(seq $N); do
 for lib in release other; do

@@ -1,7 +1,7 @@
 #!/bin/bash
 # cfg 5 (dfa256) bench lines: position-major and string-major, 65536 and 131072 strings
 cd "$(dirname "$0")/.." || exit 1
-run() { echo -n "$1: "; shift; python3 bench.py --config dfa256 --len 4095 --rows 4096 --no-cpu-baseline --no-pmc --no-spread "$@" 2>&1 | python3 -c "
+run() { echo -n "$1: "; shift; python3 bench.py --config dfa256 --len 4095 --rows 4096 --full --no-cpu-baseline --no-pmc --no-spread "$@" 2>&1 | python3 -c "
 import json,sys
 t=sys.stdin.read().strip().splitlines()
 try:

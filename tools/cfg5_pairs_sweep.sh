@@ -3,7 +3,7 @@
 P='import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]
 print("ms/step %.4f frac %.3f verified %s" % (d["ms_per_step"], r["frac"], (d.get("verified") or {}).get("bit_exact")))'
-B="python3 bench.py --config dfa256 --len 4095 --rows 4096 --warmup 3 --no-cpu-baseline --no-pmc --no-spread --batch 131072 --steps 10"
+B="python3 bench.py --config dfa256 --len 4095 --rows 4096 --warmup 3 --full --no-cpu-baseline --no-pmc --no-spread --batch 131072 --steps 10"
 for p in 0 2 20 200 2000 20000; do echo -n "substr pairs $p: "; timeout 300 $B --substr-pairs $p 2>/dev/null | python3 -c "$P"; done
 echo -n "substr pairs 200, fix-ups skipped (wrong output): "; HRX_DEBUG_FLAGS=$(python3 -c "
 import re

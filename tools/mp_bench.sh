@@ -1,7 +1,7 @@
 #!/bin/bash
 # more than three defs (headers5, D = 5): the last pass merging the groups' summaries itself against the separate combine launch
 cd "$(dirname "$0")/.." || exit 1
-run() { echo -n "$1: "; shift; env $ENVV python3 bench.py --config headers5 --batch 65536 --no-cpu-baseline --no-pmc --no-spread "$@" 2>&1 | python3 -c "
+run() { echo -n "$1: "; shift; env $ENVV python3 bench.py --config headers5 --batch 65536 --full --no-cpu-baseline --no-pmc --no-spread "$@" 2>&1 | python3 -c "
 import json,sys
 t=sys.stdin.read().strip().splitlines()
 try:

@@ -1,6 +1,6 @@
 #!/bin/bash
 cd "$(dirname "$0")/.." || exit 1
-run() { echo -n "$1: "; shift; python3 bench.py --batch 8192 --len 32768 --rows 32768 --no-cpu-baseline --no-pmc "$@" 2>&1 | python3 -c "
+run() { echo -n "$1: "; shift; python3 bench.py --batch 8192 --len 32768 --rows 32768 --full --no-cpu-baseline --no-pmc "$@" 2>&1 | python3 -c "
 import json,sys
 t=sys.stdin.read().strip().splitlines()
 try:
