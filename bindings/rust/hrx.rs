@@ -39,6 +39,13 @@ extern "C" {
     pub fn hrx_last_error() -> *const c_char;
     pub fn hrx_witness_batch_host(ctx: *mut hrx_ctx, chars: *const u8, stride: usize, lens: *const u32, b: usize,
                                   m: usize, records: *mut u32, masked: *mut u16, status: *mut u64) -> c_int;
+    // MATCH: status + revealed spans, no witness rows (include/hrx.h)
+    pub fn hrx_match_batch_device(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32, b: usize, m: usize,
+                                  status: *mut u64, span_counts: *mut u32, spans: *mut u64, max_spans: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_match_batch_host(ctx: *mut hrx_ctx, chars: *const u8, stride: usize, lens: *const u32, b: usize, m: usize,
+                                status: *mut u64, span_counts: *mut u32, spans: *mut u64, max_spans: usize) -> c_int;
+    pub fn hrx_describe_match(defs: *const hrx_defs, layout: c_int, b: usize, m: usize, num_cus: c_int, out: *mut c_char, cap: usize) -> c_int;
+    pub fn hrx_ctx_describe_match(ctx: *const hrx_ctx, layout: c_int, b: usize, m: usize, out: *mut c_char, cap: usize) -> c_int;
     pub fn hrx_witness_batch_device(ctx: *mut hrx_ctx, chars: *const u8, stride: usize, lens: *const u32, b: usize,
                                     m: usize, records: *mut u32, masked: *mut u16, status: *mut u64,
                                     stream: *mut c_void) -> c_int;

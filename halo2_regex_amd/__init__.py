@@ -134,6 +134,10 @@ def _load():
         "hrx_fr_columns_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, vp, sz, sz, sz, sz, vp, i, vp]),
         "hrx_fr_from_u64": (None, [C.c_uint64, i, _u64p]),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
+        "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
+        "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
+        "hrx_describe_match": (i, [vp, i, sz, sz, i, C.c_char_p, sz]),
+        "hrx_ctx_describe_match": (i, [vp, i, sz, sz, C.c_char_p, sz]),
         "hrx_shard_range": (None, [sz, i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hrx_derive_states": (i, [vp, _u8p, sz, _u64p]),
         "hrx_derive_substr_ids": (i, [vp, _u64p, sz, _u64p]),
@@ -729,6 +733,49 @@ class RegexVerifyConfig:
                                           _ptr(rec, _u32p), _ptr(msk, _u16p), _ptr(st, _u64p)))
         return rec, msk, st
 
+    # -- match only: status + revealed spans, no witness rows (include/hrx.h MATCH) ----------------
+    def match_batch_host(self, chars2d, lens, max_spans=16):
+        """chars2d (B, stride) uint8 numpy, lens (B,) -> status (B,) u64, counts (B,) u32, spans (B, max_spans) u64 (decode_spans)."""
+        chars2d = _np(chars2d, np.uint8)
+        lens = _np(lens, np.uint32)
+        B, stride = chars2d.shape
+        st = np.zeros(B, np.uint64)
+        cnt = np.zeros(B, np.uint32)
+        sp = np.zeros((B, max_spans), np.uint64)
+        _check(lib.hrx_match_batch_host(self._need_ctx(), _ptr(chars2d, _u8p), stride, _ptr(lens, _u32p), B, self.max_chars_size,
+                                        _ptr(st, _u64p), _ptr(cnt, _u32p), _ptr(sp, _u64p) if max_spans else None, max_spans))
+        return st, cnt, sp
+
+    def match_batch(self, chars, lens, max_spans=16, stream=None, chars_pm_stride=None, out=None):
+        """Device-resident batch (as witness_batch; chars_pm_stride: the position-major input of chars_to_position_major) ->
+        (status (B,) int64, counts (B,) int32, spans (B, max_spans) int64) CUDA tensors holding the u64 / u32 / u64 words of include/hrx.h.
+        Asynchronous on `stream` (default: torch's current stream).  out=(status, counts, spans): the caller's tensors."""
+        assert chars.is_cuda and lens.is_cuda and chars.dtype == torch.uint8 and lens.dtype == torch.int32 and lens.is_contiguous()
+        if chars_pm_stride is None:
+            assert chars.stride(1) == 1
+            B, stride, layout = chars.shape[0], chars.stride(0), LAYOUT_STRING_MAJOR
+        else:
+            assert chars.is_contiguous() and chars.numel() == lens.numel() * chars_pm_stride
+            B, stride, layout = lens.numel(), int(chars_pm_stride), LAYOUT_INPUT_POSITION_MAJOR
+        if out is None:
+            out = (torch.empty(B, dtype=torch.int64, device=chars.device), torch.empty(B, dtype=torch.int32, device=chars.device),
+                   torch.empty((B, max(max_spans, 1)), dtype=torch.int64, device=chars.device))
+        st, cnt, sp = out
+        s = torch.cuda.current_stream(chars.device) if stream is None else stream
+        _check(lib.hrx_match_batch_device(self._need_device(chars, lens, st, cnt, sp), layout, chars.data_ptr(), stride, lens.data_ptr(), B,
+                                          self.max_chars_size, st.data_ptr(), cnt.data_ptr(), sp.data_ptr() if max_spans else None, max_spans,
+                                          s.cuda_stream))
+        return st, cnt, sp
+
+    def describe_match(self, B, layout=0, num_cus=256):
+        """hrx_ctx_describe_match (or hrx_describe_match without a context): the kernel(s) match_batch runs for B strings, as text."""
+        buf = C.create_string_buffer(4096)
+        if self._ctx:
+            _check(lib.hrx_ctx_describe_match(self._ctx, layout, B, self.max_chars_size, buf, 4096))
+        else:
+            _check(lib.hrx_describe_match(self._defs.h, layout, B, self.max_chars_size, num_cus, buf, 4096))
+        return buf.value.decode()
+
     def alloc_outputs(self, B, device=None, pitched=False):
         """Device buffers for witness_batch: records int32 (B,M,D), masked int16 (B,M), status int64 (B,).
         pitched=True: the same shapes as views into buffers whose per-string pitch is hrx_recommended_pitches(M)
@@ -1046,6 +1093,55 @@ class MultiDevice:
         _check(lib.hrx_multi_witness_batch_host(self._h, _ptr(chars2d, _u8p), stride, _ptr(lens, _u32p), B, M,
                                                 _ptr(rec, _u32p), _ptr(msk, _u16p), _ptr(st, _u64p)))
         return rec, msk, st
+
+
+def decode_spans(counts, spans):
+    """(counts (B,), spans (B, max_spans)) of a match call -> per string a list of (substr_id, start, length), the first
+    min(count, max_spans) runs (include/hrx.h: bits 0..27 start, 28..55 length, 56..63 masked_substr_id)."""
+    counts = counts.cpu().numpy() if hasattr(counts, "cpu") else np.asarray(counts)
+    spans = spans.cpu().numpy() if hasattr(spans, "cpu") else np.asarray(spans)
+    spans = spans.view(np.uint64) if spans.dtype != np.uint64 else spans
+    out = []
+    for b in range(len(counts)):
+        k = min(int(counts[b]) & 0xFFFFFFFF, spans.shape[1] if spans.ndim == 2 else 0)
+        row = []
+        for w in spans[b, :k]:
+            w = int(w)
+            row.append((w >> 56, w & 0xFFFFFFF, (w >> 28) & 0xFFFFFFF))
+        out.append(row)
+    return out
+
+
+def runs_from_masked(masked, lens, status):
+    """The runs a match call reports, from witness output: masked rows (B, M) u16 -> (counts, per string [(substr_id, start, length)]), the maximal
+    runs of one non-zero masked_substr_id (masked >> 8) below n_b; none where the status code != 0."""
+    masked, lens, status = np.asarray(masked), np.asarray(lens), np.asarray(status)
+    counts, runs = [], []
+    for b in range(masked.shape[0]):
+        r = []
+        if not int(status[b]) & 0xff:
+            v = masked[b].astype(np.int64) >> 8
+            v[int(lens[b]):] = 0
+            cuts = np.flatnonzero(np.diff(v)) + 1
+            starts, ends = np.concatenate(([0], cuts)), np.concatenate((cuts, [len(v)]))
+            r = [(int(v[s]), int(s), int(e - s)) for s, e in zip(starts, ends) if v[s] != 0]
+        counts.append(len(r))
+        runs.append(r)
+    return counts, runs
+
+
+def revealed_substrings(chars, lens, status, counts, spans):
+    """Per string a list of (substr_id, start, bytes) — what the circuit reveals (lib.rs:1046-1058); [] for strings whose status code != 0.
+    chars: (B, stride) string-major bytes (numpy or tensor)."""
+    chars = chars.cpu().numpy() if hasattr(chars, "cpu") else np.asarray(chars)
+    status = status.cpu().numpy() if hasattr(status, "cpu") else np.asarray(status)
+    res = []
+    for b, runs in enumerate(decode_spans(counts, spans)):
+        if int(status[b]) & 0xff:
+            res.append([])
+            continue
+        res.append([(sid, start, bytes(chars[b, start:start + length])) for sid, start, length in runs])
+    return res
 
 
 def decode_status(s):

@@ -23,6 +23,10 @@ uint32_t debug_flags_from_env() {
     const char *dbg = std::getenv("HRX_DEBUG_FLAGS");
     return dbg ? ((uint32_t)std::strtoul(dbg, nullptr, 0) & kDbgHonoured) : 0u;
 }
+bool match_via_rows_from_env() {
+    const char *dbg = std::getenv("HRX_DEBUG_FLAGS");
+    return dbg && (std::strtoull(dbg, nullptr, 0) & kDbgMatchViaRows) != 0;
+}
 }  // namespace hrx
 
 static hipError_t upload_blob(const std::vector<uint8_t> &v, uint8_t *&d) {
@@ -218,6 +222,7 @@ static int ctx_create_from(const DefsSet &set, int device, hrx_ctx **out) {
         c->s = defs->s;
         c->device = HRX_DEVICE_NONE;
         c->debug = debug_flags_from_env();
+        c->match_via_rows = match_via_rows_from_env();
         *out = c;
         return HRX_OK;
     }
@@ -235,6 +240,7 @@ static int ctx_create_from(const DefsSet &set, int device, hrx_ctx **out) {
     c->device = device;
     c->num_cus = prop.multiProcessorCount;
     c->debug = debug_flags_from_env();
+    c->match_via_rows = match_via_rows_from_env();
     // host-buffer batches (hrx_host_api.cpp): the defaults of HRX_OPT_HOST_PIPELINE and the pipeline's chunk size / trace come from the environment ONCE, here
     if (const char *v = std::getenv("HRX_HOST_PIPELINE")) c->host_pipeline = std::atoi(v) != 0 ? 1 : 2;
     if (const char *v = std::getenv("HRX_HOST_CHUNK_MIB")) { const long n = std::atol(v); if (n >= 4 && n <= 4096) c->host_chunk_mib = (size_t)n; }
@@ -336,6 +342,7 @@ void hrx_ctx_destroy(hrx_ctx *c) {
     for (uint8_t *p : c->d_member) (void)hipFree(p);
     c->chars.release(); c->lens.release(); c->records.release(); c->masked.release();
     c->status.release(); c->states.release(); c->tags.release();
+    c->match_rec.release(); c->match_msk.release(); c->match_chars.release(); c->match_counts.release(); c->match_spans.release();
     delete c;
 }
 

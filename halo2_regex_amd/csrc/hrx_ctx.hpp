@@ -141,6 +141,12 @@ struct hrx_ctx {
     double place_max_ms = 0.0;        // ... and the wall-clock time a walk may take (0: the rule's own bounds, hrx_place_rule.hpp)
     hrx_place_report last_place{};
     struct hrx_place_pool *pool = nullptr;   // bench-sized outputs: the device's measured arena pair, shared by every context of that device in this process
+    // hrx_match_batch_* (hrx_match_api.cpp): HRX_DEBUG_FLAGS bit 32 (kDbgMatchViaRows), the "via rows" scratch (witness slices, a slice's string-major input) and its last stream,
+    // the host entry's staged counts / spans
+    bool match_via_rows = false;
+    DevBuf match_rec, match_msk, match_chars, match_counts, match_spans;
+    hipStream_t match_stream = nullptr;
+    bool match_used = false;
     DevBuf d_cw;                    // CLASS-WIDE image of a config of 4 .. 7 defs (DefsSet::cw_image): the single-launch def-parallel path
 #ifdef HRX_STAMPS
     DevBuf stamps;                  // tools-only build: 8 u64 per walker pair of the position-major kernel (hrx_kernel_pm.hip)
@@ -149,6 +155,8 @@ struct hrx_ctx {
 
 // device copies of one DefsSet's kernel-side images
 
+// hrx_describe_api.cpp: the text of hrx_describe_launch for a config (hrx_match_api.cpp names the "via rows" witness launch with it)
+extern "C" HRX_INTERNAL int describe_config(const hrx::DefsSet &s, const uint32_t dbg, const uint32_t tune, const bool mpc_on, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap);
 // hrx_host_api.cpp
 HRX_INTERNAL int check_host_shape(size_t B, size_t M);
 // hrx_api.cpp: one batch on the context's device (device pointers; the caller holds ctx->mu and has selected the device)

@@ -55,7 +55,7 @@ static int describe_set(const DefsSet &s, int layout, size_t B, size_t M, int nu
     return HRX_OK;
 }
 
-static int describe_config(const DefsSet &s, const uint32_t dbg, const uint32_t tune, const bool mpc_on, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
+int describe_config(const DefsSet &s, const uint32_t dbg, const uint32_t tune, const bool mpc_on, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
     std::string text;
     if (s.groups.empty()) {
         const bool byte_split = !s.byte.image.empty() && !(dbg & (kDbgNoByte | kDbgForceHalf));

@@ -29,7 +29,9 @@
 
 namespace hrx {
 
-uint64_t host_witness_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, size_t M, uint32_t *records, uint16_t *masked) {
+// ROWS: write records and masked rows (host_witness_one); otherwise feed the span emitter `em` (host_match_one) and write no row
+template <bool ROWS, class Out>
+static uint64_t host_walk_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, size_t M, uint32_t *records, uint16_t *masked, SpanEmitter *em, Out *out) {
     const size_t D = s.defs.size();
     if (n_raw > M) return kStatusBadLength;
     const uint32_t n = (uint32_t)n_raw;
@@ -50,6 +52,7 @@ uint64_t host_witness_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, 
         const uint32_t t0 = t * 64u;
         const uint32_t rows = (uint32_t)std::min<size_t>(64, M - t0);
         TileBits tb = {0, 0, 0};
+        uint64_t nz = 0;
         for (uint32_t p = 0; p < rows; ++p) {
             const uint32_t r = t0 + p;
             uint32_t sid = 0, stn = 0, enn = 0;
@@ -71,7 +74,7 @@ uint64_t host_witness_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, 
                     if (r == n) acc_state[d] = state;                                     // the state at row n: lib.rs:437-457
                     e[d] = c.dummy_entry;                                                 // rows > n: lib.rs:404-418
                 }
-                records[(size_t)r * D + d] = state | (tag << 16);
+                if (ROWS) records[(size_t)r * D + d] = state | (tag << 16);
                 sid += tag & 0xffu;
                 stn += (tag >> 8) & 1u;
                 enn += (tag >> 9) & 1u;
@@ -81,6 +84,7 @@ uint64_t host_witness_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, 
             tb.st |= (uint64_t)(stn ? 1u : 0u) << p;
             tb.en1 |= (uint64_t)(enn ? 1u : 0u) << p;
             tb.ch |= (uint64_t)(sid != sid_prev ? 1u : 0u) << p;
+            nz |= (uint64_t)(sid & 0xffu ? 1u : 0u) << p;
             sid_prev = sid;
             sid_row[p] = (uint8_t)sid;
         }
@@ -88,6 +92,10 @@ uint64_t host_witness_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, 
             for (size_t d = 0; d < D; ++d) acc_state[d] = (e[d] >> kNextShift) - s.consts[d].row_base;
         // reveal masks: lib.rs:598-764
         const TileMasks tm = tile_masks<64>(tb, mc, t0, tile_is_exact(t0, n, (uint32_t)M), rows_below(t0, n));
+        if (!ROWS) {
+            em->tile(tm, mc, tb.ch, nz, t0, rows, [&](int p) { return (uint32_t)sid_row[p]; }, *out);
+            continue;
+        }
         if (tm.fix)
             for (uint32_t r = tm.fix_start; r < t0; ++r) masked[r] = 0;
         for (uint32_t p = 0; p < rows; ++p) {
@@ -95,12 +103,26 @@ uint64_t host_witness_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, 
             masked[r] = ((tm.mask >> p) & 1u) ? (uint16_t)(chars[r] | (uint32_t)sid_row[p] << 8) : (uint16_t)0;   // lib.rs:752-761
         }
     }
+    if (!ROWS) em->finish((uint32_t)M, *out);
     for (size_t d = 0; d < D; ++d)   // lowest def wins: the reference walks defs in order (lib.rs:806)
         if (dead[d]) return status_invalid((uint32_t)d, err_pos[d], err_state[d], err_char[d]);
     if (D > 1 && ov_row != 0xffffffffu) return status_overlap(ov_row);
     uint32_t accept = 0;
     for (size_t d = 0; d < D && d < 32; ++d) accept |= (acc_state[d] == s.consts[d].accepted_state ? 1u : 0u) << d;
     return status_ok(accept);
+}
+
+uint64_t host_witness_one(const DefsSet &s, const uint8_t *chars, size_t n_raw, size_t M, uint32_t *records, uint16_t *masked) {
+    return host_walk_one<true, SpanSlots>(s, chars, n_raw, M, records, masked, nullptr, nullptr);
+}
+
+uint64_t host_match_one(const DefsSet &s, const uint8_t *chars, size_t n, size_t M, uint64_t *spans, size_t max_spans, uint32_t *count) {
+    SpanEmitter em;
+    em.init();
+    SpanSlots out{spans, (uint32_t)max_spans};
+    const uint64_t st = host_walk_one<false, SpanSlots>(s, chars, n, M, nullptr, nullptr, &em, &out);
+    *count = (st & 0xffu) == kStatusOk ? em.count : 0u;
+    return st;
 }
 
 // The host threads of host_witness_batch: a process-wide pool of workers that sleep between jobs.  (Until round 6 every call started its threads anew — ~30 us apiece, one after the other:
@@ -192,6 +214,20 @@ void host_witness_batch(const DefsSet &s, const uint8_t *chars, size_t stride, c
     };
     if (threads <= 1 || B < 2) { run(0, B); return; }
     // pieces of ~32768 rows (~0.1-0.4 ms of walk): small enough to balance ragged strings over the threads, large enough that the counter is not contended
+    const size_t grain = std::max<size_t>(1, 32768 / std::max<size_t>(1, M));
+    HostPool::get().run(B, grain, (size_t)threads, run);
+}
+
+void host_match_batch(const DefsSet &s, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
+                      uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads) {
+    auto run = [&](size_t lo, size_t hi) {
+        for (size_t b = lo; b < hi; ++b) {
+            uint32_t c = 0;
+            status[b] = host_match_one(s, chars + b * stride, lens[b], M, spans ? spans + b * max_spans : nullptr, max_spans, &c);
+            if (span_counts) span_counts[b] = c;
+        }
+    };
+    if (threads <= 1 || B < 2) { run(0, B); return; }
     const size_t grain = std::max<size_t>(1, 32768 / std::max<size_t>(1, M));
     HostPool::get().run(B, grain, (size_t)threads, run);
 }

@@ -92,6 +92,33 @@ bool plan_witness_launch(WitnessArgs &a, int num_cus, LaunchInfo &out) {
     return plan_witness_launch_groups(a, num_cus, out);
 }
 
+// MATCH (hrx_kernel_match.hip).  The fused kernel walks one string per lane; it takes every batch of at most three defs except where the witness
+// planner walks in chunks (few long strings: one lane per string would be chain-bound, ~1.2 ms at 8192 x 32768 against the chunked witness's 0.45).
+// Table: the narrow one in LDS where it fits (kDbgForceNarrow / kDbgForceWide: this one — the WIDE table only speeds up the witness's record
+// assembly, which the match does not do), else the HALF table (also where kDbgForceHalf or kDbgForceByte say so: the BYTE table's pair-hash tags serve
+// the witness's finisher wave, the match walk has none), else the narrow table out of L2 (GTAB; kDbgForceGlobalTable).
+bool plan_match_launch(WitnessArgs &a, int num_cus, bool via_rows, MatchPlan &out) {
+    out = MatchPlan{};
+    if (via_rows || a.D < 1 || a.D > 3 || !a.table_image) return true;
+    LaunchInfo li;
+    WitnessArgs w = a;
+    w.layout |= 1u;   // (the "via rows" witness launch is position-major)
+    if (plan_witness_launch(w, num_cus, li) && li.spec_tiles) return true;
+    const bool fits = a.table_bytes <= kLdsLimit, has_half = a.half_image != nullptr;
+    if (a.debug & kDbgForceGlobalTable) out.gtab = 1;
+    else if (has_half && (a.debug & (kDbgForceHalf | kDbgForceByte))) out.half = 1;
+    else if (fits) {}
+    else if (has_half) out.half = 1;
+    else out.gtab = 1;
+    out.fused = 1;
+    out.lds_bytes = out.gtab ? 0 : out.half ? (((size_t)a.half_bytes + 15) & ~(size_t)15) : (((size_t)a.table_bytes + 15) & ~(size_t)15);
+    // workgroups of 256 lanes, fewer where that would leave CUs without one (a workgroup stages the table once: no smaller than one wave)
+    out.threads = (int)kMatchThreads;
+    while (out.threads > 64 && ((size_t)a.B + out.threads - 1) / out.threads < (size_t)num_cus) out.threads /= 2;
+    out.grid = (int)(((size_t)a.B + out.threads - 1) / out.threads);
+    return true;
+}
+
 // (a.n_groups given: the chunked launch plans the walk over n_groups x chunks virtual groups)
 static bool plan_witness_launch_groups(WitnessArgs &a, int num_cus, LaunchInfo &out) {
     out.gtab = 0;

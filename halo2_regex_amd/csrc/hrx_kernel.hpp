@@ -140,6 +140,9 @@ enum : uint32_t {
 };
 // HRX_DEBUG_FLAGS from the environment, reduced to the bits this build honours
 uint32_t debug_flags_from_env();
+// ... and the one bit above the 32 of WitnessArgs::debug: the match entry points (hrx_match_batch_device) go "via rows" whatever the planner says (tests)
+constexpr uint64_t kDbgMatchViaRows = 1ull << 32;
+bool match_via_rows_from_env();
 
 struct LaunchInfo {
     int split;         // 6: pair-step loader/walker kernel, position-major, D = 1 (witness_pp_kernel: two bytes per dependent lookup),
@@ -276,6 +279,43 @@ struct SpecArgs {
 hipError_t launch_spec_scout(const SpecArgs &a, int num_cus, hipStream_t stream);
 hipError_t launch_spec_compose(const SpecArgs &a, hipStream_t stream);
 hipError_t launch_spec_stitch(const SpecArgs &a, int num_cus, hipStream_t stream);
+
+// MATCH (include/hrx.h hrx_match_batch_device; hrx_kernel_match.hip): status + revealed runs, no witness rows.
+//   fused:     match_lane_kernel<D, GTAB, HALF> — one lane per string on the narrow fused table (in LDS, or out of L2: GTAB) or the HALF table
+//              (in LDS), the lane algorithm of hrx_host_walk.cpp with no row stores, tile_masks + SpanEmitter (hrx_lane.h) at every tile end
+//   via rows:  the position-major witness launch into context scratch, then spans_from_masked_pm_kernel over its masked rows
+constexpr uint32_t kMatchThreads = 256;     // most lanes (strings) per workgroup of the fused kernel
+constexpr uint32_t kMatchMaxSpans = 1u << 16;
+constexpr size_t kMatchScratchBytes = (size_t)768 << 20;    // "via rows" witness slices (DevBuf rounds it up by a quarter: < 1 GiB)
+struct MatchArgs {
+    const uint8_t *chars;
+    uint64_t stride;
+    const uint32_t *lens;
+    uint32_t B, M, D;
+    uint32_t in_pm;                 // 1: input [stride/16][nb][16] per block of kPmBlock strings
+    const uint32_t *table_image;    // the narrow fused table (device copy): staged into LDS, or read in place (GTAB)
+    const uint16_t *half_image;     // the HALF table (device copy), staged into LDS
+    uint32_t table_bytes;           // bytes staged into LDS (0: GTAB)
+    const uint16_t *masked;         // spans_from_masked_pm_kernel: the slice's position-major masked rows [ceil(M/8)][nb][8], blocked
+    uint64_t *status;
+    uint32_t *span_counts;          // may be NULL
+    uint64_t *spans;                // [B][max_spans], NULL when max_spans == 0
+    uint32_t max_spans;
+    DefConsts dc[3];
+};
+struct MatchPlan {
+    int fused;          // 1: match_lane_kernel<D, gtab, half>; 0: via rows
+    int gtab, half;
+    int grid, threads;
+    size_t lds_bytes;
+};
+// fused for D <= 3 on the narrow table in LDS where it fits, else the HALF table, else the narrow table out of L2 (the forced BYTE / HALF / global-table
+// bits pick among these); via rows for more defs, where the witness planner walks in chunks (few long strings), or when forced (kDbgMatchViaRows)
+bool plan_match_launch(WitnessArgs &a, int num_cus, bool via_rows, MatchPlan &out);
+hipError_t launch_match_lane(const MatchArgs &a, const MatchPlan &p, hipStream_t stream);
+hipError_t launch_spans_from_masked(const MatchArgs &a, hipStream_t stream);
+// position-major input of strings [b0, b0 + n) (all in one block of kPmBlock) -> string-major [n][stride] (the "via rows" slices inside a block)
+hipError_t launch_pm_input_slice(const uint8_t *chars_pm, size_t stride, size_t B, size_t b0, size_t n, uint8_t *out, hipStream_t stream);
 
 // position-major -> string-major (hrx_kernel_tp.hip): string-major callers served by the position-major path
 struct TransposeArgs {

@@ -250,6 +250,69 @@ HRX_HD uint64_t rows_below(uint32_t t0, uint32_t n) {
     return k >= 64 ? ~0ull : ((1ull << k) - 1);
 }
 
+// Revealed RUNS of one string (hrx_match_batch_*, include/hrx.h): maximal ranges of rows r < n on which masked_substr_id[r]
+// (lib.rs:752-761: SID[r] where the reveal mask is 1, else 0) is one non-zero value, fed one tile at a time with what
+// tile_masks made of it.  A run breaks where `in` = mask & (SID != 0) changes or where SID changes (a `ch` bit).
+// Optimistic end masks: rows [pend_start, t0) of a later fix-up were all emitted with end_mask = 1, and end_mask is uniform
+// over such a range, so the emitter saves (count, open run) when it reaches pend_start and, on the fix, goes back to that
+// point and closes the open run there.  Runs are stored as they close (slot `count`, when < max); a rollback only lowers
+// `count`, later runs overwrite the slots — which is why slots >= the final count are unspecified.
+// Span word: bits 0..27 start row, 28..55 length, 56..63 masked_substr_id.
+HRX_HD uint64_t span_word(uint32_t start, uint32_t len, uint32_t sid) {
+    return (uint64_t)start | (uint64_t)len << 28 | (uint64_t)(sid & 0xffu) << 56;
+}
+
+struct SpanEmitter {
+    uint32_t count, open, o_start, o_sid;          // runs closed so far; the open run
+    uint32_t s_count, s_open, s_start, s_sid;      // the same at the pending range's first row
+
+    HRX_HD void init() { count = open = o_start = o_sid = s_count = s_open = s_start = s_sid = 0; }
+    template <class Out> HRX_HD void close(uint32_t end, Out &out) {
+        out.put(count, span_word(o_start, end - o_start, o_sid));
+        ++count;
+        open = 0;
+    }
+    // the boundaries `bnd` of one tile (bit p <-> row t0 + p) in increasing order; `in` says which of them open a run
+    template <class Out, class SidAt> HRX_HD void walk_bits(uint64_t bnd, uint64_t in, uint32_t t0, const SidAt &sid_at, Out &out) {
+        while (bnd) {
+            const int p = ctz64(bnd);
+            bnd &= bnd - 1;
+            if (open) close(t0 + (uint32_t)p, out);
+            if ((in >> p) & 1u) { open = 1; o_start = t0 + (uint32_t)p; o_sid = sid_at(p); }
+        }
+    }
+    // one tile of W rows: tm / c_after = what tile_masks<W> returned / left in its carry, ch = TileBits::ch, nz: bit p = SID[t0 + p] != 0,
+    // sid_at(p) = SID[t0 + p]
+    template <class Out, class SidAt>
+    HRX_HD void tile(const TileMasks &tm, const MaskCarry &c_after, uint64_t ch, uint64_t nz, uint32_t t0, uint32_t W, const SidAt &sid_at, Out &out) {
+        if (tm.fix) {   // rows [fix_start, t0) were not revealed after all
+            count = s_count; open = s_open; o_start = s_start; o_sid = s_sid;
+            if (open) close(tm.fix_start, out);
+        }
+        const uint64_t all = W >= 64 ? ~0ull : ((1ull << W) - 1);
+        const uint64_t in = tm.mask & nz & all;
+        const uint64_t prev = ((in << 1) | (uint64_t)open) & all;    // in[r - 1]
+        const uint64_t bnd = (in ^ prev) | (in & prev & ch);
+        // a pending range that starts in this tile: save the state in front of its first row
+        const uint32_t ps = (c_after.pend && c_after.pend_start >= t0) ? c_after.pend_start - t0 : 64u;
+        const uint64_t below = ps >= 64 ? ~0ull : ((1ull << ps) - 1);
+        walk_bits(bnd & below, in, t0, sid_at, out);
+        if (ps < 64) { s_count = count; s_open = open; s_start = o_start; s_sid = o_sid; }
+        walk_bits(bnd & ~below, in, t0, sid_at, out);
+    }
+    // after the last tile (rows end at `end`)
+    template <class Out> HRX_HD void finish(uint32_t end, Out &out) {
+        if (open) close(end, out);
+    }
+};
+
+// SpanEmitter output into a caller's [max] slots (host and fallback paths): slots beyond max are dropped
+struct SpanSlots {
+    uint64_t *p;
+    uint32_t max;
+    HRX_HD void put(uint32_t i, uint64_t v) const { if (i < max) p[i] = v; }
+};
+
 HRX_HD uint64_t status_ok(uint32_t accept_mask) { return (uint64_t)accept_mask << 8; }   // bit 8 + d: def d ends in its accept state (up to 32 defs)
 HRX_HD uint64_t status_invalid(uint32_t def, uint32_t pos, uint32_t state, uint32_t ch) {
     return kStatusInvalidTransition | (uint64_t)(def & 0xff) << 8 | (uint64_t)(ch & 0xff) << 16 |

@@ -1,0 +1,212 @@
+// hrx_match_api.cpp — hrx_match_batch_device / hrx_match_batch_host: the status word and the revealed runs of every string, without the witness
+// rows (include/hrx.h MATCH).  The fused kernel where plan_match_launch allows it (hrx_kernel_match.hip), "via rows" otherwise: the position-major
+// witness launch (launch_batch) slice by slice into context scratch, then the masked rows' runs.  DESIGN.md §11.
+#include "hrx_ctx.hpp"
+#include "hrx_host_walk.hpp"
+#include "hrx_lane.h"
+
+using namespace hrx;
+
+static int check_match_args(const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M, const uint64_t *status,
+                            const uint32_t *span_counts, const uint64_t *spans, size_t max_spans) {
+    if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
+    if (B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "batch too large");
+    if (max_spans > kMatchMaxSpans) return fail(HRX_ERR_ARG, "max_spans must be <= 2^16");
+    if (B == 0) return HRX_OK;
+    if (!chars || !lens || !status) return fail(HRX_ERR_ARG, "NULL buffer");
+    if (max_spans == 0 && spans) return fail(HRX_ERR_ARG, "spans must be NULL when max_spans == 0");
+    if (max_spans && (!spans || !span_counts)) return fail(HRX_ERR_ARG, "span_counts and spans are needed when max_spans > 0");
+    if (((uintptr_t)status & 7) || ((uintptr_t)span_counts & 7) || ((uintptr_t)spans & 7) || ((uintptr_t)lens & 3))
+        return fail(HRX_ERR_ARG, "status, span_counts and spans must be 8-byte aligned");
+    (void)stride;
+    return HRX_OK;
+}
+
+// the planner's view of a context's config for the match entry points (describe and launch agree by construction)
+static void match_args_of(const DefsSet &s, uint32_t dbg, int layout, size_t B, size_t M, WitnessArgs &a) {
+    a = WitnessArgs{};
+    a.layout = (uint32_t)layout; a.B = (uint32_t)B; a.M = (uint32_t)M;
+    a.table_image = s.table_image.empty() ? nullptr : s.table_image.data(); a.table_bytes = (uint32_t)(s.table_image.size() * 4);
+    a.wide_image = s.wide_image.empty() ? nullptr : s.wide_image.data();
+    a.half_image = s.half_image.empty() ? nullptr : s.half_image.data(); a.half_bytes = (uint32_t)(s.half_image.size() * 2);
+    a.pair_image = s.pair.image.empty() ? nullptr : s.pair.image.data(); a.pair_bytes = s.pair.bytes; a.pair_classes = s.pair.n_classes;
+    a.pair_blk_bytes = s.pair.blk_bytes; a.pair_lut_off = s.pair.lut_off;
+    a.byte_image = s.byte.image.empty() ? nullptr : s.byte.image.data(); a.byte_bytes = s.byte.bytes; a.byte_dead = s.byte.dead; a.byte16_bytes = s.byte.bytes16;
+    a.D = s.groups.empty() ? (uint32_t)s.defs.size() : 0u;     // (a multi-pass config always goes via rows)
+    a.debug = dbg;
+}
+
+static bool match_plan(const DefsSet &s, uint32_t dbg, bool via_rows, int layout, size_t B, size_t M, int num_cus, MatchPlan &p) {
+    WitnessArgs a;
+    match_args_of(s, dbg, layout, B, M, a);
+    return plan_match_launch(a, num_cus, via_rows, p);
+}
+
+// strings per "via rows" slice: the witness rows of a slice fit the scratch; slices of more than one block are whole blocks.  0: not even one string's rows fit
+static size_t via_rows_slice(size_t B, size_t M, size_t D) {
+    const size_t per = ((M + 3) / 4) * 4 * D * 4 + ((M + 7) / 8) * 8 * 2;
+    size_t n = kMatchScratchBytes / per;
+    if (n == 0) return 0;
+    if (n >= kPmBlock) n = n / kPmBlock * kPmBlock;
+    return std::min(n, B);
+}
+
+// the device part (device pointers; ctx->mu held, the device selected)
+static int match_device_locked(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
+                               uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
+    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
+        return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR or HRX_LAYOUT_INPUT_POSITION_MAJOR");
+    if ((stride & 15) || stride < 16 || ((uintptr_t)chars & 15))
+        return fail(HRX_ERR_ARG, "chars must be 16-byte aligned with stride % 16 == 0 and stride >= 16");
+    if (B == 0) return HRX_OK;
+    const bool in_pm = layout == HRX_LAYOUT_INPUT_POSITION_MAJOR;
+    MatchPlan p;
+    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, layout, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    MatchArgs m{};
+    m.stride = stride; m.M = (uint32_t)M; m.max_spans = (uint32_t)max_spans;
+    if (p.fused) {
+        m.chars = chars; m.lens = lens; m.B = (uint32_t)B; m.D = (uint32_t)ctx->s.defs.size(); m.in_pm = in_pm ? 1u : 0u;
+        m.table_image = ctx->d_table; m.half_image = ctx->d_half; m.table_bytes = (uint32_t)p.lds_bytes;
+        m.status = status; m.span_counts = span_counts; m.spans = spans;
+        for (uint32_t d = 0; d < m.D; ++d) m.dc[d] = ctx->s.consts[d];
+        HIP_TRY(launch_match_lane(m, p, st));
+        return HRX_OK;
+    }
+    // ---- via rows.  The scratch is this context's: a launch on another stream first waits for the one that used it last (not possible inside a capture)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cap));
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    const size_t D = ctx->s.defs.size();
+    const size_t slice = via_rows_slice(B, M, D);
+    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
+    const size_t noct = (M + 7) / 8, nquad = (M + 3) / 4;
+    const bool gather = in_pm && slice < B && slice < kPmBlock;      // slices inside a block of position-major input: its strings go string-major first
+    const size_t rec_bytes = nquad * 4 * D * 4 * slice, msk_bytes = noct * 8 * 2 * slice, chr_bytes = gather ? slice * stride : 0;
+    if (rec_bytes > ctx->match_rec.cap || msk_bytes > ctx->match_msk.cap || chr_bytes > ctx->match_chars.cap) {
+        if (capturing) return fail(HRX_ERR_STATE, "match via rows: the context's scratch is allocated at first use, not inside a stream capture");
+        HIP_TRY(hipDeviceSynchronize());     // (the buffers may be in use by earlier launches)
+        HIP_TRY(ctx->match_rec.reserve(rec_bytes));
+        HIP_TRY(ctx->match_msk.reserve(msk_bytes));
+        if (chr_bytes) HIP_TRY(ctx->match_chars.reserve(chr_bytes));
+    }
+    if (ctx->match_used && ctx->match_stream != st) {
+        if (capturing) return fail(HRX_ERR_STATE, "match via rows: the scratch was last used on another stream");
+        HIP_TRY(hipStreamSynchronize(ctx->match_stream));
+    }
+    ctx->match_used = true;
+    ctx->match_stream = st;
+    for (size_t b0 = 0; b0 < B; b0 += slice) {
+        const size_t n = std::min(slice, B - b0);
+        const uint8_t *c = chars + b0 * stride;
+        int lay = HRX_LAYOUT_POSITION_MAJOR;
+        if (in_pm && !gather) { c = chars + b0 * stride; lay |= HRX_LAYOUT_INPUT_POSITION_MAJOR; }      // (whole blocks: b0 % kPmBlock == 0)
+        if (gather) {
+            HIP_TRY(launch_pm_input_slice(chars, stride, B, b0, n, (uint8_t *)ctx->match_chars.p, st));
+            c = (const uint8_t *)ctx->match_chars.p;
+        }
+        if (int rc = launch_batch(ctx, c, stride, lens + b0, n, M, (uint32_t *)ctx->match_rec.p, (uint16_t *)ctx->match_msk.p, status + b0, st, 0, 0, lay)) return rc;
+        if (max_spans || span_counts) {
+            m.B = (uint32_t)n; m.masked = (const uint16_t *)ctx->match_msk.p; m.status = status + b0;
+            m.span_counts = span_counts ? span_counts + b0 : nullptr; m.spans = spans ? spans + b0 * max_spans : nullptr;
+            HIP_TRY(launch_spans_from_masked(m, st));
+        }
+    }
+    return HRX_OK;
+}
+
+extern "C" {
+
+int hrx_match_batch_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
+                           uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (int rc = check_match_args(chars, stride, lens, B, M, status, span_counts, spans, max_spans)) return rc;
+    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard;
+    HIP_TRY(guard.set(ctx->device));
+    return match_device_locked(ctx, layout, chars, stride, lens, B, M, status, span_counts, spans, max_spans, (hipStream_t)stream);
+}
+
+int hrx_match_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
+                         uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (int rc = check_match_args(chars, stride, lens, B, M, status, span_counts, spans, max_spans)) return rc;
+    if (B == 0) return HRX_OK;
+    for (size_t b = 0; b < B; ++b)
+        if (lens[b] <= M && lens[b] > stride) return fail(HRX_ERR_ARG, "a string is longer than the stride");
+    if (ctx->device == HRX_DEVICE_NONE) {     // the native host walk, no row written
+        const size_t threads = std::max<size_t>(1, std::min<size_t>(ctx->host_threads > 0 ? (size_t)ctx->host_threads : std::thread::hardware_concurrency(), B * M / 8192));
+        host_match_batch(ctx->s, chars, stride, lens, B, M, status, span_counts, spans, max_spans, (int)threads);
+        return HRX_OK;
+    }
+    // through the device: chunk by chunk in, match, out on the context's stream; only status / counts / spans come back
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard;
+    HIP_TRY(guard.set(ctx->device));
+    const size_t dstride = (stride + 15) & ~(size_t)15;
+    size_t cb = std::max<size_t>(1024, ((size_t)64 << 20) / std::max<size_t>(1, dstride));    // ~64 MiB of input per chunk
+    cb = std::min(cb, B);
+    HIP_TRY(ctx->chars.reserve(dstride * cb + 16));
+    HIP_TRY(ctx->lens.reserve(4 * cb));
+    HIP_TRY(ctx->status.reserve(8 * cb));
+    HIP_TRY(ctx->match_counts.reserve(4 * cb + 8));
+    if (max_spans) HIP_TRY(ctx->match_spans.reserve(8 * cb * max_spans));
+    hipStream_t st = ctx->stream;
+    for (size_t b0 = 0; b0 < B; b0 += cb) {
+        const size_t n = std::min(cb, B - b0);
+        if (dstride != stride) HIP_TRY(hipMemsetAsync(ctx->chars.p, 0, dstride * n, st));
+        HIP_TRY(hipMemcpy2DAsync(ctx->chars.p, dstride, chars + b0 * stride, stride, stride, n, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->lens.p, lens + b0, 4 * n, hipMemcpyHostToDevice, st));
+        uint32_t *d_counts = (span_counts || max_spans) ? (uint32_t *)ctx->match_counts.p : nullptr;
+        uint64_t *d_spans = max_spans ? (uint64_t *)ctx->match_spans.p : nullptr;
+        if (int rc = match_device_locked(ctx, HRX_LAYOUT_STRING_MAJOR, (const uint8_t *)ctx->chars.p, dstride, (const uint32_t *)ctx->lens.p, n, M,
+                                         (uint64_t *)ctx->status.p, d_counts, d_spans, max_spans, st))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(status + b0, ctx->status.p, 8 * n, hipMemcpyDeviceToHost, st));
+        if (span_counts) HIP_TRY(hipMemcpyAsync(span_counts + b0, d_counts, 4 * n, hipMemcpyDeviceToHost, st));
+        if (max_spans) HIP_TRY(hipMemcpyAsync(spans + b0 * max_spans, d_spans, 8 * n * max_spans, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    return HRX_OK;
+}
+
+static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_rows, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
+    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
+        return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR or HRX_LAYOUT_INPUT_POSITION_MAJOR");
+    MatchPlan p;
+    if (!match_plan(s, dbg, via_rows, layout, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.fused) {
+        std::snprintf(out, cap, "hrx::match_lane_kernel<%zu, %s, %s> grid=%d threads=%d lds=%zu", s.defs.size(), p.gtab ? "true" : "false", p.half ? "true" : "false",
+                      p.grid, p.threads, p.lds_bytes);
+        return HRX_OK;
+    }
+    const size_t slice = via_rows_slice(B, M, s.defs.size());
+    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
+    const bool in_pm = layout == HRX_LAYOUT_INPUT_POSITION_MAJOR;
+    const bool gather = in_pm && slice < B && slice < kPmBlock;
+    char w[3072];
+    const int wl = HRX_LAYOUT_POSITION_MAJOR | (in_pm && !gather ? HRX_LAYOUT_INPUT_POSITION_MAJOR : 0);
+    if (int rc = describe_config(s, dbg, 0u, mpc_on, wl, slice, M, num_cus, w, sizeof w)) return rc;
+    std::snprintf(out, cap, "via rows, %zu slice(s) of %zu strings: %s%s + hrx::spans_from_masked_pm_kernel", (B + slice - 1) / std::max<size_t>(1, slice), slice,
+                  gather ? "hrx::pm_input_slice_kernel + " : "", w);
+    return HRX_OK;
+}
+
+int hrx_describe_match(const hrx_defs *defs, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
+    if (!defs || !out || !cap) return fail(HRX_ERR_ARG, "NULL argument");
+    if (!defs->s.finalized) return fail(HRX_ERR_STATE, "call hrx_defs_finalize first");
+    if (num_cus < 1) return fail(HRX_ERR_ARG, "num_cus must be >= 1");
+    if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
+    const char *mpc = std::getenv("HRX_MP_COMBINE");      // (what hrx_ctx_create would read now)
+    return describe_match(defs->s, debug_flags_from_env(), mpc && std::atoi(mpc) != 0, match_via_rows_from_env(), layout, B ? B : 1, M, num_cus, out, cap);
+}
+
+int hrx_ctx_describe_match(const hrx_ctx *ctx, int layout, size_t B, size_t M, char *out, size_t cap) {
+    if (!ctx || !out || !cap) return fail(HRX_ERR_ARG, "NULL argument");
+    if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
+    return describe_match(ctx->s, ctx->debug, ctx->mp_combine, ctx->match_via_rows, layout, B ? B : 1, M, ctx->num_cus > 0 ? ctx->num_cus : 256, out, cap);
+}
+
+}  // extern "C"
+

@@ -389,6 +389,33 @@ int hrx_witness_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, co
                            size_t M, uint32_t *records, uint16_t *masked, uint64_t *status);
 
 /* ------------------------------------------------------------------ */
+/* MATCH: status + revealed spans of B strings, no witness rows         */
+/* ------------------------------------------------------------------ */
+/*
+ * For callers that need only whether a string matches and what it reveals (the circuit's public instances,
+ * lib.rs:1046-1058): no records, no masked rows, nothing of the witness's (4 D + 2) bytes per row leaves the device.
+ *   status       [B] u64, bit for bit what hrx_witness_batch_device writes for the same batch
+ *   span_counts  [B] u32: number of revealed RUNS of string b (may exceed max_spans); 0 when the status code != 0
+ *   spans        [B][max_spans] u64: the first min(count, max_spans) runs in increasing start order; entries beyond are unspecified
+ *                run = maximal range of rows r < n_b on which masked_substr_id[r] (lib.rs:752-761) is one non-zero value
+ *                bits 0..27 start row, 28..55 length, 56..63 masked_substr_id
+ *   max_spans    <= 2^16; 0: status only (span_counts may then be NULL, spans must be NULL)
+ *   layout       HRX_LAYOUT_STRING_MAJOR (chars [B][stride]) or HRX_LAYOUT_INPUT_POSITION_MAJOR (blocked as for the witness)
+ * Argument rules as for the witness entry points (alignment, M <= 2^24, stride % 16 == 0); span_counts and spans 8-byte aligned.
+ * The device entry is asynchronous on `stream`.  Def sets the fused match kernel walks (hrx_ctx_describe_match names it) need no
+ * scratch, and the call is then legal inside a stream capture; every other def set goes "via rows": the witness launch into
+ * context-owned scratch (at most 1 GiB, allocated at first use: inside a capture before that, HRX_ERR_STATE; HRX_ERR_BOUNDS if one string's
+ * witness rows alone would not fit) and a scan of its masked rows.
+ * hrx_match_batch_host: HOST buffers, synchronous; on a host-only context the native host walk, otherwise staged through the device. */
+int hrx_match_batch_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
+                           uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream);
+int hrx_match_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
+                         uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans);
+/* Which kernel(s) hrx_match_batch_device runs for a shape, as text (as hrx_describe_launch; host-only, nothing launched). */
+int hrx_describe_match(const hrx_defs *defs, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap);
+int hrx_ctx_describe_match(const hrx_ctx *ctx, int layout, size_t B, size_t M, char *out, size_t cap);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f4 — compact witness -> field cells (the step after the path)        */
 /* ------------------------------------------------------------------ */
 /* Expands the compact rows of strings [b_begin, b_begin + b_count) of a finished batch into what
