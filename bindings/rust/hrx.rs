@@ -46,6 +46,13 @@ extern "C" {
                                 status: *mut u64, span_counts: *mut u32, spans: *mut u64, max_spans: usize) -> c_int;
     pub fn hrx_describe_match(defs: *const hrx_defs, layout: c_int, b: usize, m: usize, num_cus: c_int, out: *mut c_char, cap: usize) -> c_int;
     pub fn hrx_ctx_describe_match(ctx: *const hrx_ctx, layout: c_int, b: usize, m: usize, out: *mut c_char, cap: usize) -> c_int;
+    // RAGGED input: string b = values[offsets[b] .. offsets[b + 1]) (include/hrx.h); a Vec<Vec<u8>> flattens to values + offsets, no padding
+    pub fn hrx_match_batch_device_ragged(ctx: *mut hrx_ctx, values: *const u8, offsets: *const u64, b: usize, m: usize,
+                                         status: *mut u64, span_counts: *mut u32, spans: *mut u64, max_spans: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_match_batch_host_ragged(ctx: *mut hrx_ctx, values: *const u8, offsets: *const u64, b: usize, m: usize,
+                                       status: *mut u64, span_counts: *mut u32, spans: *mut u64, max_spans: usize) -> c_int;
+    pub fn hrx_ragged_to_position_major_device(ctx: *mut hrx_ctx, values: *const u8, offsets: *const u64, b: usize, stride: usize,
+                                               chars_pm: *mut u8, lens: *mut u32, stream: *mut c_void) -> c_int;
     pub fn hrx_witness_batch_device(ctx: *mut hrx_ctx, chars: *const u8, stride: usize, lens: *const u32, b: usize,
                                     m: usize, records: *mut u32, masked: *mut u16, status: *mut u64,
                                     stream: *mut c_void) -> c_int;

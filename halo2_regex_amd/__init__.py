@@ -138,6 +138,9 @@ def _load():
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
         "hrx_describe_match": (i, [vp, i, sz, sz, i, C.c_char_p, sz]),
         "hrx_ctx_describe_match": (i, [vp, i, sz, sz, C.c_char_p, sz]),
+        "hrx_match_batch_device_ragged": (i, [vp, vp, vp, sz, sz, vp, vp, vp, sz, vp]),
+        "hrx_match_batch_host_ragged": (i, [vp, _u8p, _u64p, sz, sz, _u64p, _u32p, _u64p, sz]),
+        "hrx_ragged_to_position_major_device": (i, [vp, vp, vp, sz, sz, vp, vp, vp]),
         "hrx_shard_range": (None, [sz, i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hrx_derive_states": (i, [vp, _u8p, sz, _u64p]),
         "hrx_derive_substr_ids": (i, [vp, _u64p, sz, _u64p]),
@@ -441,6 +444,7 @@ def recommended_pitches(M):
 
 LAYOUT_STRING_MAJOR, LAYOUT_POSITION_MAJOR, LAYOUT_INPUT_POSITION_MAJOR = 0, 1, 2
 LAYOUT_RECORD_PLANES = 4      # describe_launch only: the launch witness_batch_planes makes
+LAYOUT_INPUT_RAGGED = 8       # describe_match only: the launch match_batch_ragged makes (values + offsets, include/hrx.h RAGGED)
 
 
 PLACE_OFF, PLACE_WALK = 0, 1     # hrx_ctx_set_placement modes
@@ -766,6 +770,58 @@ class RegexVerifyConfig:
                                           self.max_chars_size, st.data_ptr(), cnt.data_ptr(), sp.data_ptr() if max_spans else None, max_spans,
                                           s.cuda_stream))
         return st, cnt, sp
+
+    # -- ragged input: values + offsets, no padding (include/hrx.h RAGGED) ----------------------------------------------
+    def match_batch_host_ragged(self, values, offsets, max_spans=16):
+        """values (uint8) + offsets (B + 1, uint64) host arrays (pack_strings), string b = values[offsets[b]:offsets[b + 1]] ->
+        status (B,) u64, counts (B,) u32, spans (B, max_spans) u64, bit for bit what match_batch_host gives the padded batch."""
+        values = _np(values, np.uint8)
+        offsets = _np(offsets, np.uint64)
+        B = len(offsets) - 1
+        assert B >= 0
+        st = np.zeros(B, np.uint64)
+        cnt = np.zeros(B, np.uint32)
+        sp = np.zeros((B, max_spans), np.uint64)
+        vals = values if values.size else np.zeros(16, np.uint8)
+        _check(lib.hrx_match_batch_host_ragged(self._need_ctx(), _ptr(vals, _u8p), _ptr(offsets, _u64p) if B else None, B, self.max_chars_size,
+                                               _ptr(st, _u64p), _ptr(cnt, _u32p), _ptr(sp, _u64p) if max_spans else None, max_spans))
+        return st, cnt, sp
+
+    def match_strings(self, strings, max_spans=16):
+        """A list of bytes on the host (match_batch_host_ragged of pack_strings(strings)) -> (status, counts, spans)."""
+        return self.match_batch_host_ragged(*pack_strings(strings), max_spans=max_spans)
+
+    def match_batch_ragged(self, values, offsets, max_spans=16, stream=None, out=None):
+        """Device-resident ragged batch: values uint8 CUDA tensor (16-byte aligned; readable up to the 16-byte chunk end of every string's last
+        byte, as pack_strings pads it), offsets int64 CUDA tensor of B + 1 entries -> the tensors match_batch returns.  Asynchronous on
+        `stream` (default: torch's current stream).  out=(status, counts, spans): the caller's tensors."""
+        assert values.is_cuda and offsets.is_cuda and values.dtype == torch.uint8 and offsets.dtype == torch.int64
+        assert values.is_contiguous() and offsets.is_contiguous() and offsets.dim() == 1
+        B = offsets.numel() - 1
+        if out is None:
+            out = (torch.empty(B, dtype=torch.int64, device=values.device), torch.empty(B, dtype=torch.int32, device=values.device),
+                   torch.empty((B, max(max_spans, 1)), dtype=torch.int64, device=values.device))
+        st, cnt, sp = out
+        s = torch.cuda.current_stream(values.device) if stream is None else stream
+        _check(lib.hrx_match_batch_device_ragged(self._need_device(values, offsets, st, cnt, sp), values.data_ptr(), offsets.data_ptr(), B,
+                                                 self.max_chars_size, st.data_ptr(), cnt.data_ptr(), sp.data_ptr() if max_spans else None, max_spans,
+                                                 s.cuda_stream))
+        return st, cnt, sp
+
+    def ragged_to_position_major(self, values, offsets, stride=None, out=None, stream=None):
+        """hrx_ragged_to_position_major_device: a device-resident ragged batch -> (chars_pm, lens): the flat HRX_LAYOUT_INPUT_POSITION_MAJOR buffer
+        with per-string capacity `stride` (default: max_chars_size rounded up to 16) and lens int32 (-1 = UINT32_MAX: longer than stride or
+        decreasing offsets), the input of witness_batch_position_major / witness_batch_planes / match_batch with chars_pm_stride=stride."""
+        assert values.is_cuda and offsets.is_cuda and values.dtype == torch.uint8 and offsets.dtype == torch.int64 and offsets.is_contiguous()
+        B = offsets.numel() - 1
+        stride = -(-self.max_chars_size // 16) * 16 if stride is None else int(stride)
+        if out is None:
+            out = (torch.empty((B * stride,), dtype=torch.uint8, device=values.device), torch.empty(B, dtype=torch.int32, device=values.device))
+        chars_pm, lens = out
+        s = torch.cuda.current_stream(values.device) if stream is None else stream
+        _check(lib.hrx_ragged_to_position_major_device(self._need_device(values, offsets, chars_pm, lens), values.data_ptr(), offsets.data_ptr(), B,
+                                                       stride, chars_pm.data_ptr(), lens.data_ptr(), s.cuda_stream))
+        return chars_pm, lens
 
     def describe_match(self, B, layout=0, num_cus=256):
         """hrx_ctx_describe_match (or hrx_describe_match without a context): the kernel(s) match_batch runs for B strings, as text."""
@@ -1141,6 +1197,35 @@ def revealed_substrings(chars, lens, status, counts, spans):
             res.append([])
             continue
         res.append([(sid, start, bytes(chars[b, start:start + length])) for sid, start, length in runs])
+    return res
+
+
+def pack_strings(strings):
+    """A list of bytes -> (values uint8, offsets uint64 (B + 1)): the strings back to back (an Arrow large-binary column), values padded with
+    zeros to a multiple of 16 bytes (the device entry points read whole aligned 16-byte chunks)."""
+    lens = np.fromiter((len(x) for x in strings), dtype=np.uint64, count=len(strings))
+    offsets = np.zeros(len(strings) + 1, np.uint64)
+    np.cumsum(lens, out=offsets[1:])
+    total = int(offsets[-1])
+    values = np.zeros(-(-total // 16) * 16, np.uint8)
+    if total:
+        values[:total] = np.frombuffer(b"".join(bytes(x) for x in strings), np.uint8)
+    return values, offsets
+
+
+def revealed_substrings_ragged(values, offsets, status, counts, spans):
+    """revealed_substrings for a ragged batch: per string a list of (substr_id, start, bytes); [] where the status code != 0."""
+    values = values.cpu().numpy() if hasattr(values, "cpu") else np.asarray(values)
+    offsets = offsets.cpu().numpy() if hasattr(offsets, "cpu") else np.asarray(offsets)
+    status = status.cpu().numpy() if hasattr(status, "cpu") else np.asarray(status)
+    offsets = offsets.astype(np.uint64)
+    res = []
+    for b, runs in enumerate(decode_spans(counts, spans)):
+        if int(status[b]) & 0xff:
+            res.append([])
+            continue
+        o = int(offsets[b])
+        res.append([(sid, start, bytes(values[o + start:o + start + length])) for sid, start, length in runs])
     return res
 
 

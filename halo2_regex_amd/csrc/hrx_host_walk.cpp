@@ -232,6 +232,22 @@ void host_match_batch(const DefsSet &s, const uint8_t *chars, size_t stride, con
     HostPool::get().run(B, grain, (size_t)threads, run);
 }
 
+// ragged batch: string b is values[offsets[b] .. offsets[b + 1]) (decreasing offsets: kStatusBadLength, nothing read)
+void host_match_batch_ragged(const DefsSet &s, const uint8_t *values, const uint64_t *offsets, size_t B, size_t M,
+                             uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads) {
+    auto run = [&](size_t lo, size_t hi) {
+        for (size_t b = lo; b < hi; ++b) {
+            uint32_t c = 0;
+            const size_t n = offsets[b + 1] >= offsets[b] ? (size_t)(offsets[b + 1] - offsets[b]) : SIZE_MAX;
+            status[b] = host_match_one(s, values + offsets[b], n, M, spans ? spans + b * max_spans : nullptr, max_spans, &c);
+            if (span_counts) span_counts[b] = c;
+        }
+    };
+    if (threads <= 1 || B < 2) { run(0, B); return; }
+    const size_t grain = std::max<size_t>(1, 32768 / std::max<size_t>(1, M));
+    HostPool::get().run(B, grain, (size_t)threads, run);
+}
+
 // derive_states (lib.rs:804-823) for one string: states[d * (n + 1) + i]; false + (state, char) of the reference's panic
 bool host_derive_states(const DefsSet &s, const uint8_t *chars, size_t n, uint64_t *states, uint32_t &bad_state, uint32_t &bad_char) {
     const uint32_t *T = s.table_image.data();

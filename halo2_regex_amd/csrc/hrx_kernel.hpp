@@ -317,6 +317,22 @@ hipError_t launch_spans_from_masked(const MatchArgs &a, hipStream_t stream);
 // position-major input of strings [b0, b0 + n) (all in one block of kPmBlock) -> string-major [n][stride] (the "via rows" slices inside a block)
 hipError_t launch_pm_input_slice(const uint8_t *chars_pm, size_t stride, size_t B, size_t b0, size_t n, uint8_t *out, hipStream_t stream);
 
+// RAGGED input (include/hrx.h hrx_match_batch_device_ragged, hrx_ragged_to_position_major_device; hrx_kernel_ragged.hip): string b is the bytes
+// values + (offsets[b] - base) .. values + (offsets[b + 1] - base), read as the aligned 16-byte chunks that hold them.
+//   match_ragged_kernel<D, GTAB, HALF> — the fused match (plan_match_launch picks D and the table as for the padded kernel), persistent lanes
+struct RaggedMatchArgs {
+    MatchArgs m;                    // chars = values; stride, lens and in_pm unused
+    const uint64_t *offsets;        // [B + 1]
+    uint64_t base;                  // subtracted from every offset (0 on the device entry: offsets index values)
+};
+hipError_t launch_match_ragged(const RaggedMatchArgs &r, const MatchPlan &p, int num_cus, hipStream_t stream);
+// strings [b0, b0 + n) -> string-major [n][stride] zero-padded, lens [n] (UINT32_MAX: decreasing offsets or longer than limit; no byte read)
+hipError_t launch_ragged_slice(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t b0, size_t n, uint32_t limit, size_t stride,
+                               uint8_t *out, uint32_t *lens, hipStream_t stream);
+// the batch -> HRX_LAYOUT_INPUT_POSITION_MAJOR [stride/16][nb][16] per block, zero-padded, lens [B] (UINT32_MAX: as above, limit = stride)
+hipError_t launch_ragged_to_position_major(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t stride, uint8_t *chars_pm,
+                                           uint32_t *lens, hipStream_t stream);
+
 // position-major -> string-major (hrx_kernel_tp.hip): string-major callers served by the position-major path
 struct TransposeArgs {
     const uint32_t *records_pm;     // [ceil(M/4)][D][nb][4], blocked by kPmBlock strings

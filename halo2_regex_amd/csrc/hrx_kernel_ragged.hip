@@ -1,0 +1,277 @@
+// hrx_kernel_ragged.hip — RAGGED input (include/hrx.h: strings back to back in one byte buffer, B + 1 u64 offsets, as an Arrow large-binary column).
+//
+//   match_ragged_kernel<D, GTAB, HALF>  the fused match of hrx_kernel_match.hip on ragged input: the same tile walk (hrx_match_tile.h), fed from the
+//                                 aligned 16-byte chunks that hold the string's bytes, realigned with v_alignbyte_b32.  Persistent lanes: the grid fills
+//                                 the device once at the kernel's occupancy, lane g walks strings g, g + G, g + 2G, ... in one flat tile loop, so a lane
+//                                 that ends a short string starts its next at once.  A string stops after the tile that holds row min(n, M - 1)
+//                                 (the padded kernel's later tiles change nothing).  No atomics, no counters, no scratch.
+//   ragged_slice_kernel           "via rows": strings [b0, b0 + n) -> string-major [n][stride] zero-padded + lens, the input of the witness launch.
+//   ragged_to_pm_kernel           hrx_ragged_to_position_major_device: the batch -> HRX_LAYOUT_INPUT_POSITION_MAJOR + lens, one thread per output chunk.
+// A string whose offsets decrease or whose length passes the limit (M; the stride for the staging kernels) has none of its bytes read.
+#include "hrx_device.h"
+#include "hrx_walk_pm.h"
+#include "hrx_match_tile.h"
+
+namespace hrx {
+
+// o[k] = dword k of the bytes that start at byte sh (0..15) of the window w (N + 4 dwords): a dword shift by sh / 4 in two select
+// stages (the shift is the lane's own: no indexed register array), then v_alignbyte_b32 by sh % 4
+template <int N>
+__device__ __forceinline__ void realign(const uint32_t (&w)[N + 4], uint32_t sh, uint32_t (&o)[N]) {
+    // (bit masks, not ?: on array elements, which the compiler turns into a dynamically indexed load: scratch memory)
+    uint32_t y[N + 2], z[N + 1];
+    const uint32_t m2 = 0u - ((sh >> 3) & 1u), m1 = 0u - ((sh >> 2) & 1u);
+#pragma unroll
+    for (int i = 0; i < N + 2; ++i) y[i] = (w[i + 2] & m2) | (w[i] & ~m2);
+#pragma unroll
+    for (int i = 0; i < N + 1; ++i) z[i] = (y[i + 1] & m1) | (y[i] & ~m1);
+#pragma unroll
+    for (int k = 0; k < N; ++k) o[k] = __builtin_amdgcn_alignbyte(z[k + 1], z[k], sh & 3u);
+}
+
+// string b of a ragged batch: its first byte and length; false where the offsets decrease or the length passes `limit`
+__device__ __forceinline__ bool ragged_string(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t b, uint64_t limit,
+                                              const uint8_t *&p, uint32_t &n) {
+    const uint64_t o0 = offsets[b], o1 = offsets[b + 1];
+    if (o1 < o0 || o1 - o0 > limit) return false;
+    p = values + (o0 - base);
+    n = (uint32_t)(o1 - o0);
+    return true;
+}
+
+// bytes [16 c, 16 c + 16) of the string of n bytes at p, zero past n; reads only the aligned chunks that hold bytes of the string
+__device__ __forceinline__ uint4 ragged_chunk(const uint8_t *p, uint32_t n, uint32_t c) {
+    if ((uint64_t)c * 16u >= n) return make_uint4(0, 0, 0, 0);
+    const uint32_t sh = (uint32_t)((uintptr_t)p & 15u);
+    const uint4 *q = reinterpret_cast<const uint4 *>(p - sh);
+    const uint32_t nck = (sh + n + 15u) / 16u;
+    const uint4 lo = q[c], hi = c + 1u < nck ? q[c + 1] : make_uint4(0, 0, 0, 0);
+    const uint32_t w[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+    uint32_t o[4];
+    realign<4>(w, sh, o);
+    const uint32_t keep = n - 16u * c;       // >= 1
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint32_t v = keep > 4u * k ? min(keep - 4u * k, 4u) : 0u;
+        o[k] &= v >= 4u ? 0xffffffffu : ((1u << (8u * v)) - 1u);
+    }
+    return make_uint4(o[0], o[1], o[2], o[3]);
+}
+
+template <int D, bool GTAB, bool HALF>
+__global__ __launch_bounds__(kMatchThreads) void match_ragged_kernel(const RaggedMatchArgs r) {
+    const MatchArgs &a = r.m;
+    // the table at LDS offset 0 (the kernel declares no static LDS)
+    if (!GTAB) {
+        const uint32_t tab16 = (a.table_bytes + 15u) & ~15u;
+        const uint8_t *img = HALF ? reinterpret_cast<const uint8_t *>(a.half_image) : reinterpret_cast<const uint8_t *>(a.table_image);
+        for (uint32_t i = threadIdx.x * 16u; i < tab16; i += blockDim.x * 16u)
+            *reinterpret_cast<uint4 *>(smem + i) = *reinterpret_cast<const uint4 *>(img + i);
+        __syncthreads();
+    }
+    const size_t G = (size_t)gridDim.x * blockDim.x;
+    const uint32_t M = a.M, max_spans = a.max_spans;
+    size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    // the lane's current string: first byte p, length n, the aligned chunk q that holds p (sh = p % 16), nck chunks from q hold its bytes,
+    // tiles t < nt are walked
+    const uint8_t *p = nullptr;
+    const uint4 *q = nullptr;
+    uint32_t n = 0, sh = 0, nck = 0, nt = 0, t = 0;
+    uint32_t e[D], mx[D], acc_state[D], dead_row[D], err_state[D], err_char[D];
+    uint32_t sid_prev = 0, ov_row = 0xffffffffu;
+    MaskCarry mc = {0, 0, 0, 0};
+    SpanEmitter em;
+    SpanSlots out{nullptr, max_spans};
+    uint4 win[5], nxt[4] = {};     // the tile's window: the chunk it starts in and the four after it (the last one starts the next tile)
+    auto chunk = [&](uint32_t j) { return j < nck ? q[j] : make_uint4(0, 0, 0, 0); };
+    // fresh: find the next string with a valid length at or after b (strings passed over get kStatusBadLength, count 0) and reset the lane's state
+    for (bool fresh = true;;) {
+        if (fresh) {
+            for (; b < a.B; b += G) {
+                if (ragged_string(a.chars, r.offsets, r.base, b, M, p, n)) break;
+                a.status[b] = kStatusBadLength;
+                if (a.span_counts) a.span_counts[b] = 0;
+            }
+            if (b >= a.B) break;
+            fresh = false;
+            sh = (uint32_t)((uintptr_t)p & 15u);
+            q = reinterpret_cast<const uint4 *>(p - sh);
+            nck = n ? (sh + n + 15u) / 16u : 0u;
+            nt = min(n, M - 1u) / 64u + 1u;      // through the tile that holds row min(n, M - 1)
+            t = 0;
+#pragma unroll
+            for (int d = 0; d < D; ++d) {
+                e[d] = HALF ? a.dc[d].half_row_base + a.dc[d].first_state : a.dc[d].first_entry;       // states[d][0] = first_state_val: lib.rs:807
+                mx[d] = 0;
+                acc_state[d] = a.dc[d].first_state;
+                dead_row[d] = 0xffffffffu;
+            }
+            sid_prev = 0;
+            ov_row = 0xffffffffu;
+            mc = MaskCarry{0, 0, 0, 0};
+            em.init();
+            out.p = a.spans ? a.spans + b * max_spans : nullptr;
+#pragma unroll
+            for (int j = 0; j < 5; ++j) win[j] = chunk((uint32_t)j);
+        }
+        const uint32_t t0 = t * 64u;
+        if (t + 1 < nt) {      // the next tile's four new chunks are on their way during this one's walk
+#pragma unroll
+            for (int j = 0; j < 4; ++j) nxt[j] = chunk(4u * t + 5u + (uint32_t)j);
+        }
+        uint4 cq[4];
+        {
+            const uint32_t w[20] = {win[0].x, win[0].y, win[0].z, win[0].w, win[1].x, win[1].y, win[1].z, win[1].w, win[2].x, win[2].y,
+                                    win[2].z, win[2].w, win[3].x, win[3].y, win[3].z, win[3].w, win[4].x, win[4].y, win[4].z, win[4].w};
+            uint32_t o[16];
+            realign<16>(w, sh, o);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) cq[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
+        }
+        uint32_t e0[D], mx0[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) { e0[d] = e[d]; mx0[d] = mx[d]; }
+        uint64_t nz;
+        uint32_t sidq[16];
+        // FULL only where every live lane of the wave has a full tile: lanes end their strings at different tiles, and a wave that ran both
+        // forms of the walk for the same tile would pay for two walks (the general form gives the same bits on a full tile)
+        const bool full = __all(t0 + 64u <= n && t0 + 64u < M);
+        const TileBits tb = full ? match_walk_tile<D, true, GTAB, HALF>(cq, a, e, mx, sid_prev, ov_row, acc_state, t0, n, nz, sidq)
+                                 : match_walk_tile<D, false, GTAB, HALF>(cq, a, e, mx, sid_prev, ov_row, acc_state, t0, n, nz, sidq);
+        // the first undefined transition of a def (rare: the tile is walked again row by row, through the string's own bytes)
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            if (dead_row[d] == 0xffffffffu && mx[d] >= match_dead<HALF>(a, d) && mx0[d] < match_dead<HALF>(a, d)) {
+                uint32_t x = e0[d];
+                for (uint32_t i = 0; i < 64u && t0 + i < n; ++i) {
+                    const uint32_t ch = p[t0 + i];
+                    const uint32_t ne = match_next<GTAB, HALF>(a, x, ch);
+                    if (ne >= match_dead<HALF>(a, d)) {
+                        dead_row[d] = t0 + i;
+                        err_state[d] = match_state<HALF>(a, d, x);
+                        err_char[d] = ch;
+                        break;
+                    }
+                    x = ne;
+                }
+            }
+        }
+        if (n == M && t + 1 == nt) {   // n == M: row n does not exist, s[n] is the live state
+#pragma unroll
+            for (int d = 0; d < D; ++d) acc_state[d] = match_state<HALF>(a, d, e[d]);
+        }
+        // reveal masks (lib.rs:598-764) and the runs they make
+        const TileMasks tm = tile_masks<64>(tb, mc, t0, tile_is_exact(t0, n, M), rows_below(t0, n));
+        if (max_spans || a.span_counts) em.tile(tm, mc, tb.ch, nz, t0, min(64u, M - t0), [&](int i) { return sid_byte(sidq, i); }, out);
+        win[0] = win[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) win[j + 1] = nxt[j];
+        if (++t < nt) continue;
+        // the string's last tile: the padded walk's later tiles hold rows > n only (no tags, no pending range left: this tile is exact)
+        em.finish(M, out);
+        uint64_t status = 0;
+        bool done = false;
+#pragma unroll
+        for (int d = 0; d < D; ++d)   // lowest def wins: the reference walks defs in order (lib.rs:806)
+            if (!done && dead_row[d] != 0xffffffffu) { status = status_invalid((uint32_t)d, dead_row[d], err_state[d], err_char[d]); done = true; }
+        if (!done && D > 1 && ov_row != 0xffffffffu) { status = status_overlap(ov_row); done = true; }
+        if (!done) {
+            uint32_t accept = 0;
+#pragma unroll
+            for (int d = 0; d < D; ++d) accept |= (acc_state[d] == a.dc[d].accepted_state ? 1u : 0u) << d;
+            status = status_ok(accept);
+        }
+        a.status[b] = status;
+        if (a.span_counts) a.span_counts[b] = done ? 0u : em.count;
+        b += G;
+        fresh = true;
+    }
+}
+
+__global__ __launch_bounds__(256) void ragged_slice_kernel(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t b0, size_t n,
+                                                           uint32_t limit, size_t stride, uint8_t *outp, uint32_t *lens) {
+    const size_t units = stride / 16;
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n * units) return;
+    const size_t s = i / units;
+    const uint32_t c = (uint32_t)(i % units);
+    const uint8_t *p;
+    uint32_t len;
+    const bool ok = ragged_string(values, offsets, base, b0 + s, limit, p, len);
+    *reinterpret_cast<uint4 *>(outp + s * stride + (size_t)c * 16) = ok ? ragged_chunk(p, len, c) : make_uint4(0, 0, 0, 0);
+    if (c == 0) lens[s] = ok ? len : 0xffffffffu;
+}
+
+// a workgroup: 64 strings x 8 output chunks (wave w writes chunks c0 + w and c0 + 4 + w of its 64 strings: 1 KiB contiguous per store, as
+// chars_sm_to_pm_kernel); the four waves read the same 128 bytes of each string, so the strided reads share cache lines
+__global__ __launch_bounds__(256) void ragged_to_pm_kernel(const uint8_t *values, const uint64_t *offsets, uint64_t base, uint32_t B, uint32_t units,
+                                                           uint8_t *chars_pm, uint32_t *lens) {
+    const uint32_t b = blockIdx.x * 64u + (threadIdx.x & 63u);
+    if (b >= B) return;
+    const uint32_t blk0 = b / kPmBlock * kPmBlock, nb = min(kPmBlock, B - blk0);
+    const uint8_t *p;
+    uint32_t len;
+    const bool ok = ragged_string(values, offsets, base, b, (uint64_t)units * 16u, p, len);
+    uint4 *dst = reinterpret_cast<uint4 *>(chars_pm) + (size_t)blk0 * units + (b - blk0);
+    for (uint32_t cg = blockIdx.y; cg * 8u < units; cg += gridDim.y) {
+#pragma unroll
+        for (uint32_t h = 0; h < 2u; ++h) {
+            const uint32_t c = cg * 8u + h * 4u + (threadIdx.x >> 6);
+            if (c < units) dst[(size_t)c * nb] = ok ? ragged_chunk(p, len, c) : make_uint4(0, 0, 0, 0);
+        }
+    }
+    if (blockIdx.y == 0 && threadIdx.x < 64u) lens[b] = ok ? len : 0xffffffffu;
+}
+
+template <int D, bool GTAB, bool HALF>
+static hipError_t launch_ragged_one(const RaggedMatchArgs &r, const MatchPlan &p, int num_cus, hipStream_t stream) {
+    static std::atomic<size_t> granted{0};
+    if (p.lds_bytes) {
+        const hipError_t e = ensure_lds(match_ragged_kernel<D, GTAB, HALF>, granted, p.lds_bytes);
+        if (e != hipSuccess) return e;
+    }
+    // persistent lanes: as many workgroups as the device holds at once (no more than the batch needs)
+    int per_cu = 0;
+    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, match_ragged_kernel<D, GTAB, HALF>, p.threads, p.lds_bytes);
+    if (e != hipSuccess) return e;
+    const size_t need = ((size_t)r.m.B + p.threads - 1) / p.threads;
+    const size_t grid = std::min(need, (size_t)std::max(1, per_cu) * (size_t)std::max(1, num_cus));
+    hipLaunchKernelGGL((match_ragged_kernel<D, GTAB, HALF>), dim3((unsigned)grid), dim3(p.threads), p.lds_bytes, stream, r);
+    return hipGetLastError();
+}
+template <int D>
+static hipError_t launch_ragged_d(const RaggedMatchArgs &r, const MatchPlan &p, int num_cus, hipStream_t stream) {
+    if (p.half) return launch_ragged_one<D, false, true>(r, p, num_cus, stream);
+    if (p.gtab) return launch_ragged_one<D, true, false>(r, p, num_cus, stream);
+    return launch_ragged_one<D, false, false>(r, p, num_cus, stream);
+}
+
+hipError_t launch_match_ragged(const RaggedMatchArgs &r, const MatchPlan &p, int num_cus, hipStream_t stream) {
+    if (r.m.B == 0) return hipSuccess;
+    switch (r.m.D) {
+    case 1: return launch_ragged_d<1>(r, p, num_cus, stream);
+    case 2: return launch_ragged_d<2>(r, p, num_cus, stream);
+    case 3: return launch_ragged_d<3>(r, p, num_cus, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_ragged_slice(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t b0, size_t n, uint32_t limit, size_t stride,
+                               uint8_t *out, uint32_t *lens, hipStream_t stream) {
+    const size_t work = n * (stride / 16);
+    if (work == 0) return hipSuccess;
+    hipLaunchKernelGGL(ragged_slice_kernel, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, stream, values, offsets, base, b0, n, limit, stride, out, lens);
+    return hipGetLastError();
+}
+
+hipError_t launch_ragged_to_position_major(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t stride, uint8_t *chars_pm,
+                                           uint32_t *lens, hipStream_t stream) {
+    if (B == 0) return hipSuccess;
+    const uint32_t units = (uint32_t)(stride / 16);
+    const size_t cgroups = (units + 7u) / 8u;
+    hipLaunchKernelGGL(ragged_to_pm_kernel, dim3((unsigned)((B + 63) / 64), (unsigned)std::min<size_t>(cgroups, 65535)), dim3(256), 0, stream,
+                       values, offsets, base, (uint32_t)B, units, chars_pm, lens);
+    return hipGetLastError();
+}
+
+}  // namespace hrx

@@ -115,6 +115,89 @@ static int match_device_locked(hrx_ctx *ctx, int layout, const uint8_t *chars, s
     return HRX_OK;
 }
 
+// ---- RAGGED input (include/hrx.h RAGGED; hrx_kernel_ragged.hip).  String b: values + (offsets[b] - base), offsets[b + 1] - offsets[b] bytes.
+static int check_ragged_args(const uint8_t *values, const uint64_t *offsets, size_t B, size_t M, const uint64_t *status, const uint32_t *span_counts,
+                             const uint64_t *spans, size_t max_spans) {
+    if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
+    if (B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "batch too large");
+    if (max_spans > kMatchMaxSpans) return fail(HRX_ERR_ARG, "max_spans must be <= 2^16");
+    if (B == 0) return HRX_OK;
+    if (!values || !offsets || !status) return fail(HRX_ERR_ARG, "NULL buffer");
+    if (max_spans == 0 && spans) return fail(HRX_ERR_ARG, "spans must be NULL when max_spans == 0");
+    if (max_spans && (!spans || !span_counts)) return fail(HRX_ERR_ARG, "span_counts and spans are needed when max_spans > 0");
+    if (((uintptr_t)status & 7) || ((uintptr_t)span_counts & 7) || ((uintptr_t)spans & 7) || ((uintptr_t)offsets & 7))
+        return fail(HRX_ERR_ARG, "offsets, status, span_counts and spans must be 8-byte aligned");
+    return HRX_OK;
+}
+
+// ragged "via rows": strings per slice, so that the witness rows and the slice's string-major input (+ lens) fit the scratch bound together
+static size_t ragged_via_rows_slice(size_t B, size_t M, size_t D) {
+    const size_t stride = (M + 15) & ~(size_t)15;
+    const size_t per = ((M + 3) / 4) * 4 * D * 4 + ((M + 7) / 8) * 8 * 2 + stride + 4;
+    size_t n = kMatchScratchBytes / per;
+    if (n == 0) return 0;
+    if (n >= kPmBlock) n = n / kPmBlock * kPmBlock;
+    return std::min(n, B);
+}
+
+// the device part of the ragged match (device pointers; ctx->mu held, the device selected)
+static int match_ragged_device_locked(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t M,
+                                      uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
+    if (B == 0) return HRX_OK;
+    MatchPlan p;
+    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, HRX_LAYOUT_STRING_MAJOR, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    MatchArgs m{};
+    m.M = (uint32_t)M; m.max_spans = (uint32_t)max_spans;
+    if (p.fused) {
+        RaggedMatchArgs r{};
+        r.m = m;
+        r.m.chars = values; r.m.B = (uint32_t)B; r.m.D = (uint32_t)ctx->s.defs.size();
+        r.m.table_image = ctx->d_table; r.m.half_image = ctx->d_half; r.m.table_bytes = (uint32_t)p.lds_bytes;
+        r.m.status = status; r.m.span_counts = span_counts; r.m.spans = spans;
+        for (uint32_t d = 0; d < r.m.D; ++d) r.m.dc[d] = ctx->s.consts[d];
+        r.offsets = offsets; r.base = base;
+        HIP_TRY(launch_match_ragged(r, p, ctx->num_cus, st));
+        return HRX_OK;
+    }
+    // ---- via rows: each slice's strings string-major into scratch (ragged_slice_kernel), then the steps of the padded path.  Scratch rules as there
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cap));
+    const bool capturing = cap != hipStreamCaptureStatusNone;
+    const size_t D = ctx->s.defs.size();
+    const size_t slice = ragged_via_rows_slice(B, M, D);
+    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
+    const size_t stride = (M + 15) & ~(size_t)15;
+    const size_t noct = (M + 7) / 8, nquad = (M + 3) / 4;
+    const size_t rec_bytes = nquad * 4 * D * 4 * slice, msk_bytes = noct * 8 * 2 * slice, chr_bytes = slice * stride, len_bytes = slice * 4;
+    if (rec_bytes > ctx->match_rec.cap || msk_bytes > ctx->match_msk.cap || chr_bytes > ctx->match_chars.cap || len_bytes > ctx->match_lens.cap) {
+        if (capturing) return fail(HRX_ERR_STATE, "match via rows: the context's scratch is allocated at first use, not inside a stream capture");
+        HIP_TRY(hipDeviceSynchronize());     // (the buffers may be in use by earlier launches)
+        HIP_TRY(ctx->match_rec.reserve(rec_bytes));
+        HIP_TRY(ctx->match_msk.reserve(msk_bytes));
+        HIP_TRY(ctx->match_chars.reserve(chr_bytes));
+        HIP_TRY(ctx->match_lens.reserve(len_bytes));
+    }
+    if (ctx->match_used && ctx->match_stream != st) {
+        if (capturing) return fail(HRX_ERR_STATE, "match via rows: the scratch was last used on another stream");
+        HIP_TRY(hipStreamSynchronize(ctx->match_stream));
+    }
+    ctx->match_used = true;
+    ctx->match_stream = st;
+    for (size_t b0 = 0; b0 < B; b0 += slice) {
+        const size_t n = std::min(slice, B - b0);
+        uint8_t *c = (uint8_t *)ctx->match_chars.p;
+        uint32_t *lens = (uint32_t *)ctx->match_lens.p;
+        HIP_TRY(launch_ragged_slice(values, offsets, base, b0, n, (uint32_t)M, stride, c, lens, st));
+        if (int rc = launch_batch(ctx, c, stride, lens, n, M, (uint32_t *)ctx->match_rec.p, (uint16_t *)ctx->match_msk.p, status + b0, st, 0, 0, HRX_LAYOUT_POSITION_MAJOR)) return rc;
+        if (max_spans || span_counts) {
+            m.B = (uint32_t)n; m.masked = (const uint16_t *)ctx->match_msk.p; m.status = status + b0;
+            m.span_counts = span_counts ? span_counts + b0 : nullptr; m.spans = spans ? spans + b0 * max_spans : nullptr;
+            HIP_TRY(launch_spans_from_masked(m, st));
+        }
+    }
+    return HRX_OK;
+}
+
 extern "C" {
 
 int hrx_match_batch_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
@@ -171,9 +254,110 @@ int hrx_match_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, cons
     return HRX_OK;
 }
 
+int hrx_match_batch_device_ragged(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, size_t B, size_t M,
+                                  uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (int rc = check_ragged_args(values, offsets, B, M, status, span_counts, spans, max_spans)) return rc;
+    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if ((uintptr_t)values & 15) return fail(HRX_ERR_ARG, "values must be 16-byte aligned");
+    if (B == 0) return HRX_OK;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard;
+    HIP_TRY(guard.set(ctx->device));
+    return match_ragged_device_locked(ctx, values, offsets, 0, B, M, status, span_counts, spans, max_spans, (hipStream_t)stream);
+}
+
+int hrx_match_batch_host_ragged(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, size_t B, size_t M,
+                                uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (int rc = check_ragged_args(values, offsets, B, M, status, span_counts, spans, max_spans)) return rc;
+    if (B == 0) return HRX_OK;
+    if (ctx->device == HRX_DEVICE_NONE) {     // the native host walk, no row written
+        const size_t bytes = offsets[B] >= offsets[0] ? (size_t)(offsets[B] - offsets[0]) : 0;
+        const size_t threads = std::max<size_t>(1, std::min<size_t>(ctx->host_threads > 0 ? (size_t)ctx->host_threads : std::thread::hardware_concurrency(),
+                                                                    std::max<size_t>(bytes, B) / 8192));
+        host_match_batch_ragged(ctx->s, values, offsets, B, M, status, span_counts, spans, max_spans, (int)threads);
+        return HRX_OK;
+    }
+    // through the device: chunks of whole strings whose bytes span ~64 MiB; a chunk copies its one byte range (from the aligned 16 bytes its first
+    // byte is in, so every string keeps its alignment) and its offsets as they are (the kernel subtracts the range's start); only status / counts /
+    // spans come back.  Strings with decreasing offsets or longer than M are read by nobody and do not widen a range.
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard;
+    HIP_TRY(guard.set(ctx->device));
+    const size_t kSpan = (size_t)64 << 20;
+    const size_t max_n = std::max<size_t>(1, std::min<size_t>((size_t)1 << 20, kSpan / (8 * max_spans + 12)));
+    hipStream_t st = ctx->stream;
+    for (size_t b0 = 0; b0 < B;) {
+        uint64_t lo = UINT64_MAX, hi = 0;
+        size_t b1 = b0;
+        for (; b1 < B && b1 - b0 < max_n; ++b1) {
+            const uint64_t o0 = offsets[b1], o1 = offsets[b1 + 1];
+            if (o1 < o0 || o1 - o0 > M || o1 == o0) continue;
+            const uint64_t nlo = std::min(lo, o0 & ~(uint64_t)15), nhi = std::max(hi, o1);
+            if (b1 > b0 && nhi - nlo > kSpan) break;
+            lo = nlo; hi = nhi;
+        }
+        const size_t n = b1 - b0;
+        if (lo > hi) lo = hi = 0;          // (no byte to read in this chunk)
+        const size_t bytes = (size_t)(hi - lo);
+        HIP_TRY(ctx->chars.reserve(((bytes + 15) & ~(size_t)15) + 16));
+        HIP_TRY(ctx->lens.reserve(8 * (n + 1)));
+        HIP_TRY(ctx->status.reserve(8 * n));
+        HIP_TRY(ctx->match_counts.reserve(4 * n + 8));
+        if (max_spans) HIP_TRY(ctx->match_spans.reserve(8 * n * max_spans));
+        if (bytes) HIP_TRY(hipMemcpyAsync(ctx->chars.p, values + lo, bytes, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->lens.p, offsets + b0, 8 * (n + 1), hipMemcpyHostToDevice, st));
+        uint32_t *d_counts = (span_counts || max_spans) ? (uint32_t *)ctx->match_counts.p : nullptr;
+        uint64_t *d_spans = max_spans ? (uint64_t *)ctx->match_spans.p : nullptr;
+        if (int rc = match_ragged_device_locked(ctx, (const uint8_t *)ctx->chars.p, (const uint64_t *)ctx->lens.p, lo, n, M, (uint64_t *)ctx->status.p,
+                                                d_counts, d_spans, max_spans, st))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(status + b0, ctx->status.p, 8 * n, hipMemcpyDeviceToHost, st));
+        if (span_counts) HIP_TRY(hipMemcpyAsync(span_counts + b0, d_counts, 4 * n, hipMemcpyDeviceToHost, st));
+        if (max_spans) HIP_TRY(hipMemcpyAsync(spans + b0 * max_spans, d_spans, 8 * n * max_spans, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        b0 = b1;
+    }
+    return HRX_OK;
+}
+
+int hrx_ragged_to_position_major_device(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, size_t B, size_t stride, uint8_t *chars_pm,
+                                        uint32_t *lens, void *stream) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (B == 0) return HRX_OK;
+    if (!values || !offsets || !chars_pm || !lens) return fail(HRX_ERR_ARG, "NULL buffer");
+    if (B > 0xffffffffull - 64 || stride / 16 > 0xffffffffull) return fail(HRX_ERR_ARG, "shape out of range");
+    if ((stride & 15) || stride < 16 || ((uintptr_t)values & 15) || ((uintptr_t)chars_pm & 15) || ((uintptr_t)offsets & 7) || ((uintptr_t)lens & 3))
+        return fail(HRX_ERR_ARG, "values and chars_pm must be 16-byte aligned, offsets 8-byte, lens 4-byte, stride % 16 == 0 and stride >= 16");
+    DeviceGuard guard;      // (stateless: no context scratch, no lock)
+    HIP_TRY(guard.set(ctx->device));
+    HIP_TRY(launch_ragged_to_position_major(values, offsets, 0, B, stride, chars_pm, lens, (hipStream_t)stream));
+    return HRX_OK;
+}
+
+static int describe_match_ragged(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_rows, size_t B, size_t M, int num_cus, char *out, size_t cap) {
+    MatchPlan p;
+    if (!match_plan(s, dbg, via_rows, HRX_LAYOUT_STRING_MAJOR, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.fused) {
+        std::snprintf(out, cap, "hrx::match_ragged_kernel<%zu, %s, %s> grid=persistent threads=%d lds=%zu", s.defs.size(), p.gtab ? "true" : "false",
+                      p.half ? "true" : "false", p.threads, p.lds_bytes);
+        return HRX_OK;
+    }
+    const size_t slice = ragged_via_rows_slice(B, M, s.defs.size());
+    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
+    char w[3072];
+    if (int rc = describe_config(s, dbg, 0u, mpc_on, HRX_LAYOUT_POSITION_MAJOR, slice, M, num_cus, w, sizeof w)) return rc;
+    std::snprintf(out, cap, "via rows, %zu slice(s) of %zu strings: hrx::ragged_slice_kernel + %s + hrx::spans_from_masked_pm_kernel",
+                  (B + slice - 1) / slice, slice, w);
+    return HRX_OK;
+}
+
 static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_rows, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
+    if (layout == HRX_LAYOUT_INPUT_RAGGED) return describe_match_ragged(s, dbg, mpc_on, via_rows, B, M, num_cus, out, cap);
     if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
-        return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR or HRX_LAYOUT_INPUT_POSITION_MAJOR");
+        return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR, HRX_LAYOUT_INPUT_POSITION_MAJOR or HRX_LAYOUT_INPUT_RAGGED");
     MatchPlan p;
     if (!match_plan(s, dbg, via_rows, layout, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
     if (p.fused) {

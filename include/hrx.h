@@ -416,6 +416,38 @@ int hrx_describe_match(const hrx_defs *defs, int layout, size_t B, size_t M, int
 int hrx_ctx_describe_match(const hrx_ctx *ctx, int layout, size_t B, size_t M, char *out, size_t cap);
 
 /* ------------------------------------------------------------------ */
+/* RAGGED input: strings back to back in one byte buffer + B + 1 offsets */
+/* ------------------------------------------------------------------ */
+/*
+ * string b = values[offsets[b] .. offsets[b+1]), n_b = offsets[b+1] - offsets[b]; offsets has B + 1 entries (an Arrow large-binary column:
+ * no string is padded).  offsets[0] need not be 0 and offsets may point at any byte: offsets + begin (with the same values) is a valid
+ * slice of a larger column, which is how a caller shards one.  A string whose offsets decrease (offsets[b+1] < offsets[b]) or with
+ * n_b > M gets kStatusBadLength (status code 3, the code the padded entry points give lens[b] > M) and count 0; none of its bytes are read.
+ *
+ * hrx_match_batch_device_ragged / hrx_match_batch_host_ragged: status, span_counts and spans are bit for bit what hrx_match_batch_device /
+ *   hrx_match_batch_host return for the same strings padded into [B][stride] with lens[b] = n_b.
+ *   Device entry: values 16-byte aligned, offsets 8-byte aligned.  The call reads whole aligned 16-byte chunks, so values must be readable
+ *   up to round_up(offsets[B], 16) (in general: up to the aligned chunk end of every string's last byte), and it never reads a chunk that
+ *   holds no byte of some string of the batch.  Every other argument rule, the asynchronous behaviour and the stream-capture rules are those
+ *   of hrx_match_batch_device: where the fused kernel runs (hrx_ctx_describe_match with HRX_LAYOUT_INPUT_RAGGED names it) no scratch is
+ *   needed and the launch can be captured; "via rows" uses the context scratch with the same first-use and capture rules.
+ *   Host entry: host buffers (no alignment rule for values), synchronous.  On a host-only context the native host walk; on a device
+ *   context chunks of whole strings whose bytes span about 64 MiB go through the device, each one contiguous byte range plus its offsets
+ *   in, status / counts / spans out.
+ * hrx_ragged_to_position_major_device: the batch as HRX_LAYOUT_INPUT_POSITION_MAJOR input blocked by HRX_PM_BLOCK, per-string capacity
+ *   `stride` (stride % 16 == 0): chars_pm [B * stride] bytes (16-byte aligned), the bytes past n_b zero, lens[b] = n_b.  A string longer than
+ *   stride or with decreasing offsets gets lens[b] = UINT32_MAX (every consumer then reports kStatusBadLength for it).  The output feeds
+ *   hrx_witness_batch_device_layout, hrx_witness_batch_device_planes, hrx_fr_columns_device* and hrx_match_batch_device unchanged: the
+ *   ragged counterpart of hrx_chars_to_position_major_device.  Asynchronous on `stream`, no scratch, capturable. */
+enum { HRX_LAYOUT_INPUT_RAGGED = 8 /* hrx_describe_match / hrx_ctx_describe_match only: the launch of hrx_match_batch_device_ragged */ };
+int hrx_match_batch_device_ragged(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, size_t B, size_t M,
+                                  uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream);
+int hrx_match_batch_host_ragged(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, size_t B, size_t M,
+                                uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans);
+int hrx_ragged_to_position_major_device(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, size_t B,
+                                        size_t stride, uint8_t *chars_pm, uint32_t *lens, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f4 — compact witness -> field cells (the step after the path)        */
 /* ------------------------------------------------------------------ */
 /* Expands the compact rows of strings [b_begin, b_begin + b_count) of a finished batch into what
