@@ -96,8 +96,11 @@ def ragged(B, n_max, seed=5, alphabet=ALPHABET98, planted=True):
 
 def reveal_stress(B, n, seed=7):
     """Strings built from the pieces that drive the reveal-mask scans of regex1/2/3 through every branch:
-    complete matches, matches cut before their end (start_mask set, never reset), long public parts crossing
-    64-row tile boundaries, back-to-back matches."""
+    complete matches, matches cut before their end, long public parts crossing 64-row tile boundaries, back-to-back
+    matches.  A cut regex1 / regex2 piece is still revealed: the end state of their substrings is the loop state, every row
+    of a run carries an end flag and leaving the run is an end event.  Only the cut regex3 pieces (a tagged run without an
+    end flag) leave start_mask set with no end behind it, so only on regex3 is an optimistic end mask ever taken back.
+    tests/carry_defs.py makes such ranges on purpose, at any length."""
     rng = _rng(seed, 3)
     stride = _stride(n)
     chars = np.zeros((B, stride), np.uint8)

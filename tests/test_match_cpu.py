@@ -6,6 +6,7 @@ import os
 import numpy as np
 import pytest
 
+import carry_defs as cd
 import fuzz_defs as fd
 import halo2_regex_amd as hra
 from halo2_regex_amd import synth
@@ -106,8 +107,10 @@ def _regex1_hit(name):
 
 @pytest.mark.parametrize("tiles", [3, 30, 300])
 def test_long_spans_and_one_that_never_closes(oracle, tiles):
-    """runs that close `tiles` tiles after they open (the optimistic end mask confirmed or fixed that much later), and one whose string
-    ends inside it (it never closes: the reference reveals nothing there)"""
+    """runs that close `tiles` tiles after they open, and one whose string ends inside it.  On regex1 every row of a run carries an end flag (the substring's end
+    state is its loop state), so the unterminated match is revealed like the others: all of these optimistic end masks are CONFIRMED that much later, none is
+    fixed.  The lever strings of tests/carry_defs.py behind them are the ones that are taken back, over the same number of tiles: by a second start, by the string's
+    end, by reaching M, with islands of tagged rows inside (the run emitter rolls back), next to a confirmed one."""
     M = 64 * (tiles + 2)
     stride = -(-(M + 1) // 16) * 16
     B = 4
@@ -121,6 +124,22 @@ def test_long_spans_and_one_that_never_closes(oracle, tiles):
         lens[b] = len(t)
     check_match(oracle, CFG_1, chars, lens, M)
     check_match(oracle, CFG_A, chars, lens, M)
+    a, b = 21, 21 + 64 * tiles
+    made = [cd.sc_second_start(M, a, b), cd.sc_string_end(M, a, b), cd.sc_reach_m(M, a), cd.sc_islands(M, a, b, confirmed=False), cd.sc_confirmed(M, a, b),
+            cd.sc_second_start(M, 0, b), cd.sc_end_at_last_row(M, a)]
+    lever = cd.lever_defs(1)
+    chars = np.zeros((len(made), stride), np.uint8)
+    lens = np.array([len(v) for v, _, _ in made], np.uint32)
+    for k, (v, code, ranges) in enumerate(made):
+        chars[k, :len(v)] = v
+    o = OracleDefs(oracle, [(t, subs) for t, subs, _ in lever])
+    _, omsk, ost = o.witness_batch(chars, lens, M)
+    assert not (ost & np.uint64(0xff)).any()
+    for k, (v, code, ranges) in enumerate(made):      # they are what they say: taken back means nothing of the range is revealed
+        for r0, r1, kind in ranges:
+            assert omsk[k, r0:min(r1, M)].all() if kind == "confirmed" else not omsk[k, r0:min(r1, M)].any(), (k, kind)
+    cfg = hra.RegexVerifyConfig.configure(M, [hra.RegexDefs(hra.AllstrRegexDef(t), [hra.SubstrRegexDef(x) for x in subs]) for t, subs, _ in lever], device=hra.HRX_DEVICE_NONE)
+    check_match(oracle, None, chars, lens, M, cfg=cfg, o=o)
 
 
 def test_sid_changes_without_flags_and_overlap(oracle):

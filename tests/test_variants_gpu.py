@@ -169,6 +169,90 @@ def _stripe_sizes(hra, B, M, R):
     return npl.value, nm.value
 
 
+def launch_every_form(hra, row, case, cfg, o, ost, tag, fr=False, pitched=None):
+    """The row's entry point on one case, every output into poisoned, guarded buffers (string-major: pitched ones on odd seeds, the pitch gaps checked; position-major:
+    both input layouts, then record planes / row stripes); fr: fr_columns of the launch's rows as well.  Returns [(form, status, records (B, M, D), masked (B, M))]."""
+    import torch
+    dev = torch.device("cuda", 0)
+    B, M, D, stride = case.B, case.M, case.D, case.stride
+    d_chars = torch.from_numpy(case.chars).to(dev)
+    d_lens = torch.from_numpy(case.lens.astype(np.int32)).to(dev)
+    runs = []      # (form, st, rec (B, M, D) numpy u32, msk (B, M) numpy u16)
+    if row["entry"] == "sm":
+        pitched = case.seed % 2 == 1 if pitched is None else pitched
+        rp, mp = hra.recommended_pitches(M)[:2] if pitched else (M, M)
+        r_v, r_raw = _guarded(torch, dev, B * rp * D * 4, torch.int32)
+        m_v, m_raw = _guarded(torch, dev, B * mp * 2, torch.int16)
+        s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
+        out = (r_v.view(B, rp, D)[:, :M], m_v.view(B, mp)[:, :M], s_v)
+        cfg.witness_batch(d_chars, d_lens, out=out)
+        torch.cuda.synchronize()
+        for raw, n, what in ((r_raw, B * rp * D * 4, "records"), (m_raw, B * mp * 2, "masked"), (s_raw, B * 8, "status")):
+            _guards_intact(raw, n, tag + " " + what)
+        if pitched:      # rows M.. of every string's slot are never written
+            assert (r_raw[:B * rp * D * 4].view(B, rp, D * 4)[:, M:] == POISON).all(), tag + ": a write into the records' pitch gap"
+            assert (m_raw[:B * mp * 2].view(B, mp, 2)[:, M:] == POISON).all(), tag + ": a write into the masked rows' pitch gap"
+        runs.append(("string-major" + (" pitched" if pitched else ""), out[2].cpu().numpy().view(np.uint64),
+                     out[0].cpu().numpy().view(np.uint32), out[1].cpu().numpy().view(np.uint16)))
+        if fr:
+            _check_fr(hra, torch, o, cfg, case, d_chars, d_lens, out, dict(position_major=False), ost, tag)
+    else:
+        nr, nm = C.c_size_t(0), C.c_size_t(0)
+        hra.lib.hrx_position_major_sizes(B, M, D, C.byref(nr), C.byref(nm))
+        for pm_input in (False, True):
+            r_v, r_raw = _guarded(torch, dev, nr.value * 4, torch.int32)
+            m_v, m_raw = _guarded(torch, dev, nm.value * 2, torch.int16)
+            s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
+            if pm_input:
+                src, kw = hra.chars_to_position_major(d_chars), dict(chars_pm_stride=stride)
+            else:
+                src, kw = d_chars, {}
+            cfg.witness_batch_position_major(src, d_lens, out=(r_v, m_v, s_v), **kw)
+            torch.cuda.synchronize()
+            form = "position-major" + (" (position-major input)" if pm_input else "")
+            for raw, n, what in ((r_raw, nr.value * 4, "records"), (m_raw, nm.value * 2, "masked"), (s_raw, B * 8, "status")):
+                _guards_intact(raw, n, "%s %s %s" % (tag, form, what))
+            r1, m1 = hra.position_major_to_string_major(r_v, m_v, B, M, D)
+            runs.append((form, s_v.cpu().numpy().view(np.uint64), r1.cpu().numpy().view(np.uint32), m1.cpu().numpy().view(np.uint16)))
+            if fr and pm_input:
+                _check_fr(hra, torch, o, cfg, case, src, d_lens, (r_v, m_v, s_v), dict(position_major=True, **kw), ost, tag)
+        # record planes (D >= 2) or the two row stripes of one def.  Only the guards behind the buffers are checked: rows >= M of the last quad /
+        # octet, and with it the second stripe's slot past the last quad, are unspecified by the layout (include/hrx.h) (the kernels may store whole quads)
+        R = 2 if D == 1 else 1
+        npl, nmp = _stripe_sizes(hra, B, M, R)
+        planes, raws = [], []
+        for _ in range(D * R):
+            p_v, p_raw = _guarded(torch, dev, npl * 4, torch.int32)
+            planes.append(p_v)
+            raws.append(p_raw)
+        m_v, m_raw = _guarded(torch, dev, nmp * 2, torch.int16)
+        s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
+        pm_input = case.seed % 2 == 0
+        src, kw = (hra.chars_to_position_major(d_chars), dict(chars_pm_stride=stride)) if pm_input else (d_chars, {})
+        form = "row stripes" if D == 1 else "record planes"
+        if row.get("planes") is False:      # a multi-pass config has no one-launch planes path: the library refuses, it writes nothing
+            with pytest.raises(hra.HrxError, match="record planes"):
+                cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw)
+            torch.cuda.synchronize()
+            for k, raw in enumerate(raws + [m_raw, s_raw]):
+                assert (raw == POISON).all(), "%s %s %d: written by a refused call" % (tag, form, k)
+            runs_planes = False
+        else:
+            cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw)
+            torch.cuda.synchronize()
+            runs_planes = True
+        for k, raw in enumerate(raws):
+            _guards_intact(raw, npl * 4, "%s %s %d" % (tag, form, k))
+        _guards_intact(m_raw, nmp * 2, tag + " " + form + " masked")
+        _guards_intact(s_raw, B * 8, tag + " " + form + " status")
+        if runs_planes:
+            r1, m1 = hra.planes_to_string_major(planes, m_v, B, M, D)
+            runs.append((form, s_v.cpu().numpy().view(np.uint64), r1.cpu().numpy().view(np.uint32), m1.cpu().numpy().view(np.uint16)))
+        if runs_planes and fr:
+            _check_fr(hra, torch, o, cfg, case, src, d_lens, (planes, m_v, s_v), dict(position_major=True, **kw), ost, tag + " " + form)
+    return runs
+
+
 @pytest.mark.parametrize("row", ROWS, ids=ROW_IDS)
 def test_variant_on_edge_case_definitions(hra, oracle, row):
     import torch
@@ -189,82 +273,8 @@ def test_variant_on_edge_case_definitions(hra, oracle, row):
             assert (code == 0).mean() >= 1 / 3, (row["id"], case.seed, np.bincount(code))
         accepted |= bool(((ost >> np.uint64(8)) & np.uint64(0xffffffff))[code == 0].any())
         masked_nonzero |= bool(omsk[code == 0].any())
-        d_chars = torch.from_numpy(case.chars).to(dev)
-        d_lens = torch.from_numpy(case.lens.astype(np.int32)).to(dev)
         tag = "%s seed %d (B=%d M=%d D=%d)" % (row["id"], case.seed, B, M, D)
-        runs = []      # (form, st, rec (B, M, D) numpy u32, msk (B, M) numpy u16)
-        if row["entry"] == "sm":
-            pitched = case.seed % 2 == 1
-            rp, mp = hra.recommended_pitches(M)[:2] if pitched else (M, M)
-            r_v, r_raw = _guarded(torch, dev, B * rp * D * 4, torch.int32)
-            m_v, m_raw = _guarded(torch, dev, B * mp * 2, torch.int16)
-            s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
-            out = (r_v.view(B, rp, D)[:, :M], m_v.view(B, mp)[:, :M], s_v)
-            cfg.witness_batch(d_chars, d_lens, out=out)
-            torch.cuda.synchronize()
-            for raw, n, what in ((r_raw, B * rp * D * 4, "records"), (m_raw, B * mp * 2, "masked"), (s_raw, B * 8, "status")):
-                _guards_intact(raw, n, tag + " " + what)
-            if pitched:      # rows M.. of every string's slot are never written
-                assert (r_raw[:B * rp * D * 4].view(B, rp, D * 4)[:, M:] == POISON).all(), tag + ": a write into the records' pitch gap"
-                assert (m_raw[:B * mp * 2].view(B, mp, 2)[:, M:] == POISON).all(), tag + ": a write into the masked rows' pitch gap"
-            runs.append(("string-major" + (" pitched" if pitched else ""), out[2].cpu().numpy().view(np.uint64),
-                         out[0].cpu().numpy().view(np.uint32), out[1].cpu().numpy().view(np.uint16)))
-            if case.seed == fr_seed:
-                _check_fr(hra, torch, o, cfg, case, d_chars, d_lens, out, dict(position_major=False), ost, tag)
-        else:
-            nr, nm = C.c_size_t(0), C.c_size_t(0)
-            hra.lib.hrx_position_major_sizes(B, M, D, C.byref(nr), C.byref(nm))
-            for pm_input in (False, True):
-                r_v, r_raw = _guarded(torch, dev, nr.value * 4, torch.int32)
-                m_v, m_raw = _guarded(torch, dev, nm.value * 2, torch.int16)
-                s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
-                if pm_input:
-                    src, kw = hra.chars_to_position_major(d_chars), dict(chars_pm_stride=stride)
-                else:
-                    src, kw = d_chars, {}
-                cfg.witness_batch_position_major(src, d_lens, out=(r_v, m_v, s_v), **kw)
-                torch.cuda.synchronize()
-                form = "position-major" + (" (position-major input)" if pm_input else "")
-                for raw, n, what in ((r_raw, nr.value * 4, "records"), (m_raw, nm.value * 2, "masked"), (s_raw, B * 8, "status")):
-                    _guards_intact(raw, n, "%s %s %s" % (tag, form, what))
-                r1, m1 = hra.position_major_to_string_major(r_v, m_v, B, M, D)
-                runs.append((form, s_v.cpu().numpy().view(np.uint64), r1.cpu().numpy().view(np.uint32), m1.cpu().numpy().view(np.uint16)))
-                if case.seed == fr_seed and pm_input:
-                    _check_fr(hra, torch, o, cfg, case, src, d_lens, (r_v, m_v, s_v), dict(position_major=True, **kw), ost, tag)
-            # record planes (D >= 2) or the two row stripes of one def.  Only the guards behind the buffers are checked: rows >= M of the last quad /
-            # octet, and with it the second stripe's slot past the last quad, are unspecified by the layout (include/hrx.h) (the kernels may store whole quads)
-            R = 2 if D == 1 else 1
-            npl, nmp = _stripe_sizes(hra, B, M, R)
-            planes, raws = [], []
-            for _ in range(D * R):
-                p_v, p_raw = _guarded(torch, dev, npl * 4, torch.int32)
-                planes.append(p_v)
-                raws.append(p_raw)
-            m_v, m_raw = _guarded(torch, dev, nmp * 2, torch.int16)
-            s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
-            pm_input = case.seed % 2 == 0
-            src, kw = (hra.chars_to_position_major(d_chars), dict(chars_pm_stride=stride)) if pm_input else (d_chars, {})
-            form = "row stripes" if D == 1 else "record planes"
-            if row.get("planes") is False:      # a multi-pass config has no one-launch planes path: the library refuses, it writes nothing
-                with pytest.raises(hra.HrxError, match="record planes"):
-                    cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw)
-                torch.cuda.synchronize()
-                for k, raw in enumerate(raws + [m_raw, s_raw]):
-                    assert (raw == POISON).all(), "%s %s %d: written by a refused call" % (tag, form, k)
-                runs_planes = False
-            else:
-                cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw)
-                torch.cuda.synchronize()
-                runs_planes = True
-            for k, raw in enumerate(raws):
-                _guards_intact(raw, npl * 4, "%s %s %d" % (tag, form, k))
-            _guards_intact(m_raw, nmp * 2, tag + " " + form + " masked")
-            _guards_intact(s_raw, B * 8, tag + " " + form + " status")
-            if runs_planes:
-                r1, m1 = hra.planes_to_string_major(planes, m_v, B, M, D)
-                runs.append((form, s_v.cpu().numpy().view(np.uint64), r1.cpu().numpy().view(np.uint32), m1.cpu().numpy().view(np.uint16)))
-            if runs_planes and case.seed == fr_seed:
-                _check_fr(hra, torch, o, cfg, case, src, d_lens, (planes, m_v, s_v), dict(position_major=True, **kw), ost, tag + " " + form)
+        runs = launch_every_form(hra, row, case, cfg, o, ost, tag, fr=case.seed == fr_seed)
         for form, st, rec, msk in runs:
             err = _compare(row, case, ost, orec, omsk, st, rec, msk)
             assert err is None, "%s, %s: %s" % (tag, form, err)
