@@ -205,47 +205,45 @@ private:
     }
 };
 
+// one(b) for every string b of a batch of M rows each.  On the pool in pieces of ~32768 rows (~0.1-0.4 ms of walk): small enough to balance ragged
+// strings over the threads, large enough that the counter is not contended
+template <class One>
+static void host_batch_run(size_t B, size_t M, int threads, const One &one) {
+    const std::function<void(size_t, size_t)> run = [&](size_t lo, size_t hi) { for (size_t b = lo; b < hi; ++b) one(b); };
+    if (threads <= 1 || B < 2) run(0, B);
+    else HostPool::get().run(B, std::max<size_t>(1, 32768 / std::max<size_t>(1, M)), (size_t)threads, run);
+}
+
 void host_witness_batch(const DefsSet &s, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
                         uint32_t *records, uint16_t *masked, uint64_t *status, int threads) {
     const size_t D = s.defs.size();
-    auto run = [&](size_t lo, size_t hi) {
-        for (size_t b = lo; b < hi; ++b)
-            status[b] = host_witness_one(s, chars + b * stride, lens[b], M, records + b * M * D, masked + b * M);
-    };
-    if (threads <= 1 || B < 2) { run(0, B); return; }
-    // pieces of ~32768 rows (~0.1-0.4 ms of walk): small enough to balance ragged strings over the threads, large enough that the counter is not contended
-    const size_t grain = std::max<size_t>(1, 32768 / std::max<size_t>(1, M));
-    HostPool::get().run(B, grain, (size_t)threads, run);
+    host_batch_run(B, M, threads, [&](size_t b) { status[b] = host_witness_one(s, chars + b * stride, lens[b], M, records + b * M * D, masked + b * M); });
+}
+
+// host_match_one over a batch whose string b is the n bytes at string(b, n)
+template <class String>
+static void host_match_strings(const DefsSet &s, size_t B, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads, const String &string) {
+    host_batch_run(B, M, threads, [&](size_t b) {
+        size_t n;
+        const uint8_t *p = string(b, n);
+        uint32_t c = 0;
+        status[b] = host_match_one(s, p, n, M, spans ? spans + b * max_spans : nullptr, max_spans, &c);
+        if (span_counts) span_counts[b] = c;
+    });
 }
 
 void host_match_batch(const DefsSet &s, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
                       uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads) {
-    auto run = [&](size_t lo, size_t hi) {
-        for (size_t b = lo; b < hi; ++b) {
-            uint32_t c = 0;
-            status[b] = host_match_one(s, chars + b * stride, lens[b], M, spans ? spans + b * max_spans : nullptr, max_spans, &c);
-            if (span_counts) span_counts[b] = c;
-        }
-    };
-    if (threads <= 1 || B < 2) { run(0, B); return; }
-    const size_t grain = std::max<size_t>(1, 32768 / std::max<size_t>(1, M));
-    HostPool::get().run(B, grain, (size_t)threads, run);
+    host_match_strings(s, B, M, status, span_counts, spans, max_spans, threads, [&](size_t b, size_t &n) { n = lens[b]; return chars + b * stride; });
 }
 
 // ragged batch: string b is values[offsets[b] .. offsets[b + 1]) (decreasing offsets: kStatusBadLength, nothing read)
 void host_match_batch_ragged(const DefsSet &s, const uint8_t *values, const uint64_t *offsets, size_t B, size_t M,
                              uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads) {
-    auto run = [&](size_t lo, size_t hi) {
-        for (size_t b = lo; b < hi; ++b) {
-            uint32_t c = 0;
-            const size_t n = offsets[b + 1] >= offsets[b] ? (size_t)(offsets[b + 1] - offsets[b]) : SIZE_MAX;
-            status[b] = host_match_one(s, values + offsets[b], n, M, spans ? spans + b * max_spans : nullptr, max_spans, &c);
-            if (span_counts) span_counts[b] = c;
-        }
-    };
-    if (threads <= 1 || B < 2) { run(0, B); return; }
-    const size_t grain = std::max<size_t>(1, 32768 / std::max<size_t>(1, M));
-    HostPool::get().run(B, grain, (size_t)threads, run);
+    host_match_strings(s, B, M, status, span_counts, spans, max_spans, threads, [&](size_t b, size_t &n) {
+        n = offsets[b + 1] >= offsets[b] ? (size_t)(offsets[b + 1] - offsets[b]) : SIZE_MAX;
+        return values + offsets[b];
+    });
 }
 
 // derive_states (lib.rs:804-823) for one string: states[d * (n + 1) + i]; false + (state, char) of the reference's panic

@@ -282,7 +282,9 @@ hipError_t launch_spec_stitch(const SpecArgs &a, int num_cus, hipStream_t stream
 
 // MATCH (include/hrx.h hrx_match_batch_device; hrx_kernel_match.hip): status + revealed runs, no witness rows.
 //   fused:     match_lane_kernel<D, GTAB, HALF> — one lane per string on the narrow fused table (in LDS, or out of L2: GTAB) or the HALF table
-//              (in LDS), the lane algorithm of hrx_host_walk.cpp with no row stores, tile_masks + SpanEmitter (hrx_lane.h) at every tile end
+//              (in LDS), the lane algorithm of hrx_host_walk.cpp with no row stores, tile_masks + SpanEmitter (hrx_lane.h) at every tile end.
+//              The per-string state, the tile step and the status epilogue are the lane core of hrx_match_tile.h (MatchLane), which the ragged
+//              kernel below shares; so is the launch ladder over D and the table form (fused_kernel)
 //   via rows:  the position-major witness launch into context scratch, then spans_from_masked_pm_kernel over its masked rows
 constexpr uint32_t kMatchThreads = 256;     // most lanes (strings) per workgroup of the fused kernel
 constexpr uint32_t kMatchMaxSpans = 1u << 16;
@@ -319,7 +321,8 @@ hipError_t launch_pm_input_slice(const uint8_t *chars_pm, size_t stride, size_t 
 
 // RAGGED input (include/hrx.h hrx_match_batch_device_ragged, hrx_ragged_to_position_major_device; hrx_kernel_ragged.hip): string b is the bytes
 // values + (offsets[b] - base) .. values + (offsets[b + 1] - base), read as the aligned 16-byte chunks that hold them.
-//   match_ragged_kernel<D, GTAB, HALF> — the fused match (plan_match_launch picks D and the table as for the padded kernel), persistent lanes
+//   match_ragged_kernel<D, GTAB, HALF> — the fused match (plan_match_launch picks D and the table as for the padded kernel), persistent lanes:
+//   the ragged addressing, window carry and realign around the same lane core
 struct RaggedMatchArgs {
     MatchArgs m;                    // chars = values; stride, lens and in_pm unused
     const uint64_t *offsets;        // [B + 1]

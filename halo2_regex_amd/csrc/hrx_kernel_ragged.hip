@@ -1,6 +1,6 @@
 // hrx_kernel_ragged.hip — RAGGED input (include/hrx.h: strings back to back in one byte buffer, B + 1 u64 offsets, as an Arrow large-binary column).
 //
-//   match_ragged_kernel<D, GTAB, HALF>  the fused match of hrx_kernel_match.hip on ragged input: the same tile walk (hrx_match_tile.h), fed from the
+//   match_ragged_kernel<D, GTAB, HALF>  the fused match of hrx_kernel_match.hip on ragged input: the same lane core (hrx_match_tile.h MatchLane), fed from the
 //                                 aligned 16-byte chunks that hold the string's bytes, realigned with v_alignbyte_b32.  Persistent lanes: the grid fills
 //                                 the device once at the kernel's occupancy, lane g walks strings g, g + G, g + 2G, ... in one flat tile loop, so a lane
 //                                 that ends a short string starts its next at once.  A string stops after the tile that holds row min(n, M - 1)
@@ -61,27 +61,16 @@ __device__ __forceinline__ uint4 ragged_chunk(const uint8_t *p, uint32_t n, uint
 template <int D, bool GTAB, bool HALF>
 __global__ __launch_bounds__(kMatchThreads) void match_ragged_kernel(const RaggedMatchArgs r) {
     const MatchArgs &a = r.m;
-    // the table at LDS offset 0 (the kernel declares no static LDS)
-    if (!GTAB) {
-        const uint32_t tab16 = (a.table_bytes + 15u) & ~15u;
-        const uint8_t *img = HALF ? reinterpret_cast<const uint8_t *>(a.half_image) : reinterpret_cast<const uint8_t *>(a.table_image);
-        for (uint32_t i = threadIdx.x * 16u; i < tab16; i += blockDim.x * 16u)
-            *reinterpret_cast<uint4 *>(smem + i) = *reinterpret_cast<const uint4 *>(img + i);
-        __syncthreads();
-    }
+    match_stage_table<GTAB, HALF>(a);
     const size_t G = (size_t)gridDim.x * blockDim.x;
-    const uint32_t M = a.M, max_spans = a.max_spans;
+    const uint32_t M = a.M;
     size_t b = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     // the lane's current string: first byte p, length n, the aligned chunk q that holds p (sh = p % 16), nck chunks from q hold its bytes,
     // tiles t < nt are walked
     const uint8_t *p = nullptr;
     const uint4 *q = nullptr;
     uint32_t n = 0, sh = 0, nck = 0, nt = 0, t = 0;
-    uint32_t e[D], mx[D], acc_state[D], dead_row[D], err_state[D], err_char[D];
-    uint32_t sid_prev = 0, ov_row = 0xffffffffu;
-    MaskCarry mc = {0, 0, 0, 0};
-    SpanEmitter em;
-    SpanSlots out{nullptr, max_spans};
+    MatchLane<D, GTAB, HALF> lane;
     uint4 win[5], nxt[4] = {};     // the tile's window: the chunk it starts in and the four after it (the last one starts the next tile)
     auto chunk = [&](uint32_t j) { return j < nck ? q[j] : make_uint4(0, 0, 0, 0); };
     // fresh: find the next string with a valid length at or after b (strings passed over get kStatusBadLength, count 0) and reset the lane's state
@@ -99,18 +88,7 @@ __global__ __launch_bounds__(kMatchThreads) void match_ragged_kernel(const Ragge
             nck = n ? (sh + n + 15u) / 16u : 0u;
             nt = min(n, M - 1u) / 64u + 1u;      // through the tile that holds row min(n, M - 1)
             t = 0;
-#pragma unroll
-            for (int d = 0; d < D; ++d) {
-                e[d] = HALF ? a.dc[d].half_row_base + a.dc[d].first_state : a.dc[d].first_entry;       // states[d][0] = first_state_val: lib.rs:807
-                mx[d] = 0;
-                acc_state[d] = a.dc[d].first_state;
-                dead_row[d] = 0xffffffffu;
-            }
-            sid_prev = 0;
-            ov_row = 0xffffffffu;
-            mc = MaskCarry{0, 0, 0, 0};
-            em.init();
-            out.p = a.spans ? a.spans + b * max_spans : nullptr;
+            lane.reset(a, b);
 #pragma unroll
             for (int j = 0; j < 5; ++j) win[j] = chunk((uint32_t)j);
         }
@@ -128,61 +106,15 @@ __global__ __launch_bounds__(kMatchThreads) void match_ragged_kernel(const Ragge
 #pragma unroll
             for (int j = 0; j < 4; ++j) cq[j] = make_uint4(o[4 * j], o[4 * j + 1], o[4 * j + 2], o[4 * j + 3]);
         }
-        uint32_t e0[D], mx0[D];
-#pragma unroll
-        for (int d = 0; d < D; ++d) { e0[d] = e[d]; mx0[d] = mx[d]; }
-        uint64_t nz;
-        uint32_t sidq[16];
         // FULL only where every live lane of the wave has a full tile: lanes end their strings at different tiles, and a wave that ran both
         // forms of the walk for the same tile would pay for two walks (the general form gives the same bits on a full tile)
-        const bool full = __all(t0 + 64u <= n && t0 + 64u < M);
-        const TileBits tb = full ? match_walk_tile<D, true, GTAB, HALF>(cq, a, e, mx, sid_prev, ov_row, acc_state, t0, n, nz, sidq)
-                                 : match_walk_tile<D, false, GTAB, HALF>(cq, a, e, mx, sid_prev, ov_row, acc_state, t0, n, nz, sidq);
-        // the first undefined transition of a def (rare: the tile is walked again row by row, through the string's own bytes)
-#pragma unroll
-        for (int d = 0; d < D; ++d) {
-            if (dead_row[d] == 0xffffffffu && mx[d] >= match_dead<HALF>(a, d) && mx0[d] < match_dead<HALF>(a, d)) {
-                uint32_t x = e0[d];
-                for (uint32_t i = 0; i < 64u && t0 + i < n; ++i) {
-                    const uint32_t ch = p[t0 + i];
-                    const uint32_t ne = match_next<GTAB, HALF>(a, x, ch);
-                    if (ne >= match_dead<HALF>(a, d)) {
-                        dead_row[d] = t0 + i;
-                        err_state[d] = match_state<HALF>(a, d, x);
-                        err_char[d] = ch;
-                        break;
-                    }
-                    x = ne;
-                }
-            }
-        }
-        if (n == M && t + 1 == nt) {   // n == M: row n does not exist, s[n] is the live state
-#pragma unroll
-            for (int d = 0; d < D; ++d) acc_state[d] = match_state<HALF>(a, d, e[d]);
-        }
-        // reveal masks (lib.rs:598-764) and the runs they make
-        const TileMasks tm = tile_masks<64>(tb, mc, t0, tile_is_exact(t0, n, M), rows_below(t0, n));
-        if (max_spans || a.span_counts) em.tile(tm, mc, tb.ch, nz, t0, min(64u, M - t0), [&](int i) { return sid_byte(sidq, i); }, out);
+        lane.tile(a, cq, t0, n, t + 1 == nt, __all(t0 + 64u <= n && t0 + 64u < M), [&](uint32_t i) { return (uint32_t)p[i]; });
         win[0] = win[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) win[j + 1] = nxt[j];
         if (++t < nt) continue;
         // the string's last tile: the padded walk's later tiles hold rows > n only (no tags, no pending range left: this tile is exact)
-        em.finish(M, out);
-        uint64_t status = 0;
-        bool done = false;
-#pragma unroll
-        for (int d = 0; d < D; ++d)   // lowest def wins: the reference walks defs in order (lib.rs:806)
-            if (!done && dead_row[d] != 0xffffffffu) { status = status_invalid((uint32_t)d, dead_row[d], err_state[d], err_char[d]); done = true; }
-        if (!done && D > 1 && ov_row != 0xffffffffu) { status = status_overlap(ov_row); done = true; }
-        if (!done) {
-            uint32_t accept = 0;
-#pragma unroll
-            for (int d = 0; d < D; ++d) accept |= (acc_state[d] == a.dc[d].accepted_state ? 1u : 0u) << d;
-            status = status_ok(accept);
-        }
-        a.status[b] = status;
-        if (a.span_counts) a.span_counts[b] = done ? 0u : em.count;
+        lane.finish(a, b);
         b += G;
         fresh = true;
     }
@@ -223,37 +155,25 @@ __global__ __launch_bounds__(256) void ragged_to_pm_kernel(const uint8_t *values
     if (blockIdx.y == 0 && threadIdx.x < 64u) lens[b] = ok ? len : 0xffffffffu;
 }
 
-template <int D, bool GTAB, bool HALF>
-static hipError_t launch_ragged_one(const RaggedMatchArgs &r, const MatchPlan &p, int num_cus, hipStream_t stream) {
-    static std::atomic<size_t> granted{0};
-    if (p.lds_bytes) {
-        const hipError_t e = ensure_lds(match_ragged_kernel<D, GTAB, HALF>, granted, p.lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    // persistent lanes: as many workgroups as the device holds at once (no more than the batch needs)
-    int per_cu = 0;
-    hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, match_ragged_kernel<D, GTAB, HALF>, p.threads, p.lds_bytes);
-    if (e != hipSuccess) return e;
-    const size_t need = ((size_t)r.m.B + p.threads - 1) / p.threads;
-    const size_t grid = std::min(need, (size_t)std::max(1, per_cu) * (size_t)std::max(1, num_cus));
-    hipLaunchKernelGGL((match_ragged_kernel<D, GTAB, HALF>), dim3((unsigned)grid), dim3(p.threads), p.lds_bytes, stream, r);
-    return hipGetLastError();
-}
-template <int D>
-static hipError_t launch_ragged_d(const RaggedMatchArgs &r, const MatchPlan &p, int num_cus, hipStream_t stream) {
-    if (p.half) return launch_ragged_one<D, false, true>(r, p, num_cus, stream);
-    if (p.gtab) return launch_ragged_one<D, true, false>(r, p, num_cus, stream);
-    return launch_ragged_one<D, false, false>(r, p, num_cus, stream);
-}
+// names the ragged kernel template for fused_kernel (hrx_match_tile.h)
+struct MatchRaggedKernels {
+    using fn = void (*)(RaggedMatchArgs);
+    template <int D, bool GTAB, bool HALF> static fn get() { return match_ragged_kernel<D, GTAB, HALF>; }
+};
 
 hipError_t launch_match_ragged(const RaggedMatchArgs &r, const MatchPlan &p, int num_cus, hipStream_t stream) {
     if (r.m.B == 0) return hipSuccess;
-    switch (r.m.D) {
-    case 1: return launch_ragged_d<1>(r, p, num_cus, stream);
-    case 2: return launch_ragged_d<2>(r, p, num_cus, stream);
-    case 3: return launch_ragged_d<3>(r, p, num_cus, stream);
-    default: return hipErrorInvalidValue;
-    }
+    MatchRaggedKernels::fn k;
+    hipError_t e = fused_kernel<MatchRaggedKernels>(r.m.D, p, k);
+    if (e != hipSuccess) return e;
+    // persistent lanes: as many workgroups as the device holds at once (no more than the batch needs)
+    int per_cu = 0;
+    e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k, p.threads, p.lds_bytes);
+    if (e != hipSuccess) return e;
+    const size_t need = ((size_t)r.m.B + p.threads - 1) / p.threads;
+    const size_t grid = std::min(need, (size_t)std::max(1, per_cu) * (size_t)std::max(1, num_cus));
+    hipLaunchKernelGGL(k, dim3((unsigned)grid), dim3(p.threads), p.lds_bytes, stream, r);
+    return hipGetLastError();
 }
 
 hipError_t launch_ragged_slice(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t b0, size_t n, uint32_t limit, size_t stride,

@@ -1,25 +1,38 @@
-// hrx_match_api.cpp — hrx_match_batch_device / hrx_match_batch_host: the status word and the revealed runs of every string, without the witness
-// rows (include/hrx.h MATCH).  The fused kernel where plan_match_launch allows it (hrx_kernel_match.hip), "via rows" otherwise: the position-major
-// witness launch (launch_batch) slice by slice into context scratch, then the masked rows' runs.  DESIGN.md §11.
+// hrx_match_api.cpp — hrx_match_batch_device / hrx_match_batch_host and their _ragged forms: the status word and the revealed runs of every string,
+// without the witness rows (include/hrx.h MATCH, RAGGED).  The fused kernel where plan_match_launch allows it (hrx_kernel_match.hip padded,
+// hrx_kernel_ragged.hip ragged), "via rows" otherwise: the position-major witness launch (launch_batch) slice by slice into context scratch, then
+// the masked rows' runs.  The two input forms share the argument rules, the fused arguments, the via-rows driver (plan_via_rows, via_rows_scratch,
+// match_via_rows: a form brings only the step that stages a slice's input) and the host entries' copy-out; they differ in the staging step and in
+// how a host entry cuts its chunks.  DESIGN.md §11, §12.
 #include "hrx_ctx.hpp"
 #include "hrx_host_walk.hpp"
 #include "hrx_lane.h"
 
 using namespace hrx;
 
-static int check_match_args(const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M, const uint64_t *status,
-                            const uint32_t *span_counts, const uint64_t *spans, size_t max_spans) {
+// the argument rules both input forms share, in the order the errors are reported; the entry's own part: its input pointers (in_null), its
+// 4- or 8-byte aligned one (in_misaligned) and the text of the alignment error
+static int check_common_args(bool in_null, bool in_misaligned, const char *align_msg, size_t B, size_t M, const uint64_t *status,
+                             const uint32_t *span_counts, const uint64_t *spans, size_t max_spans) {
     if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
     if (B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "batch too large");
     if (max_spans > kMatchMaxSpans) return fail(HRX_ERR_ARG, "max_spans must be <= 2^16");
     if (B == 0) return HRX_OK;
-    if (!chars || !lens || !status) return fail(HRX_ERR_ARG, "NULL buffer");
+    if (in_null || !status) return fail(HRX_ERR_ARG, "NULL buffer");
     if (max_spans == 0 && spans) return fail(HRX_ERR_ARG, "spans must be NULL when max_spans == 0");
     if (max_spans && (!spans || !span_counts)) return fail(HRX_ERR_ARG, "span_counts and spans are needed when max_spans > 0");
-    if (((uintptr_t)status & 7) || ((uintptr_t)span_counts & 7) || ((uintptr_t)spans & 7) || ((uintptr_t)lens & 3))
-        return fail(HRX_ERR_ARG, "status, span_counts and spans must be 8-byte aligned");
-    (void)stride;
+    if (((uintptr_t)status & 7) || ((uintptr_t)span_counts & 7) || ((uintptr_t)spans & 7) || in_misaligned) return fail(HRX_ERR_ARG, align_msg);
     return HRX_OK;
+}
+static int check_match_args(const uint8_t *chars, const uint32_t *lens, size_t B, size_t M, const uint64_t *status, const uint32_t *span_counts,
+                            const uint64_t *spans, size_t max_spans) {
+    return check_common_args(!chars || !lens, (uintptr_t)lens & 3, "status, span_counts and spans must be 8-byte aligned", B, M, status, span_counts, spans, max_spans);
+}
+// RAGGED input (include/hrx.h RAGGED; hrx_kernel_ragged.hip): string b is values + (offsets[b] - base), offsets[b + 1] - offsets[b] bytes
+static int check_ragged_args(const uint8_t *values, const uint64_t *offsets, size_t B, size_t M, const uint64_t *status, const uint32_t *span_counts,
+                             const uint64_t *spans, size_t max_spans) {
+    return check_common_args(!values || !offsets, (uintptr_t)offsets & 7, "offsets, status, span_counts and spans must be 8-byte aligned", B, M, status, span_counts,
+                             spans, max_spans);
 }
 
 // the planner's view of a context's config for the match entry points (describe and launch agree by construction)
@@ -42,133 +55,56 @@ static bool match_plan(const DefsSet &s, uint32_t dbg, bool via_rows, int layout
     return plan_match_launch(a, num_cus, via_rows, p);
 }
 
-// strings per "via rows" slice: the witness rows of a slice fit the scratch; slices of more than one block are whole blocks.  0: not even one string's rows fit
-static size_t via_rows_slice(size_t B, size_t M, size_t D) {
-    const size_t per = ((M + 3) / 4) * 4 * D * 4 + ((M + 7) / 8) * 8 * 2;
+// the fused kernels' arguments but for the input (the entry's own: stride, lens, in_pm / offsets, base)
+static MatchArgs fused_args(const hrx_ctx *ctx, const MatchPlan &p, const uint8_t *chars, size_t B, size_t M, uint64_t *status, uint32_t *span_counts,
+                            uint64_t *spans, size_t max_spans) {
+    MatchArgs m{};
+    m.chars = chars; m.B = (uint32_t)B; m.M = (uint32_t)M; m.D = (uint32_t)ctx->s.defs.size(); m.max_spans = (uint32_t)max_spans;
+    m.table_image = ctx->d_table; m.half_image = ctx->d_half; m.table_bytes = (uint32_t)p.lds_bytes;
+    m.status = status; m.span_counts = span_counts; m.spans = spans;
+    for (uint32_t d = 0; d < m.D; ++d) m.dc[d] = ctx->s.consts[d];
+    return m;
+}
+
+// ---- "via rows".  Strings per slice: the witness rows of a slice, and `extra` staged bytes per string, fit the scratch; slices of more than one
+// block are whole blocks.  0: not even one string's rows fit
+static size_t via_rows_slice(size_t B, size_t M, size_t D, size_t extra) {
+    const size_t per = ((M + 3) / 4) * 4 * D * 4 + ((M + 7) / 8) * 8 * 2 + extra;
     size_t n = kMatchScratchBytes / per;
     if (n == 0) return 0;
     if (n >= kPmBlock) n = n / kPmBlock * kPmBlock;
     return std::min(n, B);
 }
 
-// the device part (device pointers; ctx->mu held, the device selected)
-static int match_device_locked(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
-                               uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
-    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
-    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
-        return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR or HRX_LAYOUT_INPUT_POSITION_MAJOR");
-    if ((stride & 15) || stride < 16 || ((uintptr_t)chars & 15))
-        return fail(HRX_ERR_ARG, "chars must be 16-byte aligned with stride % 16 == 0 and stride >= 16");
-    if (B == 0) return HRX_OK;
+// how a via-rows call cuts and stages its batch: the launch and the describe functions both read it here
+struct ViaRows {
+    size_t slice;       // strings per slice
+    size_t stride;      // of the staged string-major input (ragged: round_up(M, 16); gather: the caller's)
+    bool ragged;        // ragged_slice_kernel stages every slice (string-major input + lens, counted in the slice size)
+    bool gather;        // slices inside a block of position-major input: pm_input_slice_kernel makes its strings string-major first
+    int layout;         // of the witness launch
+};
+static ViaRows plan_via_rows(int layout, size_t stride, size_t B, size_t M, size_t D) {
+    ViaRows v{};
+    v.ragged = layout == HRX_LAYOUT_INPUT_RAGGED;
+    v.stride = v.ragged ? (M + 15) & ~(size_t)15 : stride;
+    v.slice = via_rows_slice(B, M, D, v.ragged ? v.stride + 4 : 0);
     const bool in_pm = layout == HRX_LAYOUT_INPUT_POSITION_MAJOR;
-    MatchPlan p;
-    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, layout, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
-    MatchArgs m{};
-    m.stride = stride; m.M = (uint32_t)M; m.max_spans = (uint32_t)max_spans;
-    if (p.fused) {
-        m.chars = chars; m.lens = lens; m.B = (uint32_t)B; m.D = (uint32_t)ctx->s.defs.size(); m.in_pm = in_pm ? 1u : 0u;
-        m.table_image = ctx->d_table; m.half_image = ctx->d_half; m.table_bytes = (uint32_t)p.lds_bytes;
-        m.status = status; m.span_counts = span_counts; m.spans = spans;
-        for (uint32_t d = 0; d < m.D; ++d) m.dc[d] = ctx->s.consts[d];
-        HIP_TRY(launch_match_lane(m, p, st));
-        return HRX_OK;
-    }
-    // ---- via rows.  The scratch is this context's: a launch on another stream first waits for the one that used it last (not possible inside a capture)
+    v.gather = in_pm && v.slice < B && v.slice < kPmBlock;
+    v.layout = HRX_LAYOUT_POSITION_MAJOR | (in_pm && !v.gather ? HRX_LAYOUT_INPUT_POSITION_MAJOR : 0);
+    return v;
+}
+
+// The scratch of a via-rows call, ready for use on stream st.  It is this context's: allocated at first use (not inside a capture), and a launch on
+// another stream first waits for the one that used it last (not possible inside a capture)
+static int via_rows_scratch(hrx_ctx *ctx, const ViaRows &v, size_t M, hipStream_t st) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing(st, &cap));
     const bool capturing = cap != hipStreamCaptureStatusNone;
-    const size_t D = ctx->s.defs.size();
-    const size_t slice = via_rows_slice(B, M, D);
-    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
-    const size_t noct = (M + 7) / 8, nquad = (M + 3) / 4;
-    const bool gather = in_pm && slice < B && slice < kPmBlock;      // slices inside a block of position-major input: its strings go string-major first
-    const size_t rec_bytes = nquad * 4 * D * 4 * slice, msk_bytes = noct * 8 * 2 * slice, chr_bytes = gather ? slice * stride : 0;
-    if (rec_bytes > ctx->match_rec.cap || msk_bytes > ctx->match_msk.cap || chr_bytes > ctx->match_chars.cap) {
-        if (capturing) return fail(HRX_ERR_STATE, "match via rows: the context's scratch is allocated at first use, not inside a stream capture");
-        HIP_TRY(hipDeviceSynchronize());     // (the buffers may be in use by earlier launches)
-        HIP_TRY(ctx->match_rec.reserve(rec_bytes));
-        HIP_TRY(ctx->match_msk.reserve(msk_bytes));
-        if (chr_bytes) HIP_TRY(ctx->match_chars.reserve(chr_bytes));
-    }
-    if (ctx->match_used && ctx->match_stream != st) {
-        if (capturing) return fail(HRX_ERR_STATE, "match via rows: the scratch was last used on another stream");
-        HIP_TRY(hipStreamSynchronize(ctx->match_stream));
-    }
-    ctx->match_used = true;
-    ctx->match_stream = st;
-    for (size_t b0 = 0; b0 < B; b0 += slice) {
-        const size_t n = std::min(slice, B - b0);
-        const uint8_t *c = chars + b0 * stride;
-        int lay = HRX_LAYOUT_POSITION_MAJOR;
-        if (in_pm && !gather) { c = chars + b0 * stride; lay |= HRX_LAYOUT_INPUT_POSITION_MAJOR; }      // (whole blocks: b0 % kPmBlock == 0)
-        if (gather) {
-            HIP_TRY(launch_pm_input_slice(chars, stride, B, b0, n, (uint8_t *)ctx->match_chars.p, st));
-            c = (const uint8_t *)ctx->match_chars.p;
-        }
-        if (int rc = launch_batch(ctx, c, stride, lens + b0, n, M, (uint32_t *)ctx->match_rec.p, (uint16_t *)ctx->match_msk.p, status + b0, st, 0, 0, lay)) return rc;
-        if (max_spans || span_counts) {
-            m.B = (uint32_t)n; m.masked = (const uint16_t *)ctx->match_msk.p; m.status = status + b0;
-            m.span_counts = span_counts ? span_counts + b0 : nullptr; m.spans = spans ? spans + b0 * max_spans : nullptr;
-            HIP_TRY(launch_spans_from_masked(m, st));
-        }
-    }
-    return HRX_OK;
-}
-
-// ---- RAGGED input (include/hrx.h RAGGED; hrx_kernel_ragged.hip).  String b: values + (offsets[b] - base), offsets[b + 1] - offsets[b] bytes.
-static int check_ragged_args(const uint8_t *values, const uint64_t *offsets, size_t B, size_t M, const uint64_t *status, const uint32_t *span_counts,
-                             const uint64_t *spans, size_t max_spans) {
-    if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
-    if (B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "batch too large");
-    if (max_spans > kMatchMaxSpans) return fail(HRX_ERR_ARG, "max_spans must be <= 2^16");
-    if (B == 0) return HRX_OK;
-    if (!values || !offsets || !status) return fail(HRX_ERR_ARG, "NULL buffer");
-    if (max_spans == 0 && spans) return fail(HRX_ERR_ARG, "spans must be NULL when max_spans == 0");
-    if (max_spans && (!spans || !span_counts)) return fail(HRX_ERR_ARG, "span_counts and spans are needed when max_spans > 0");
-    if (((uintptr_t)status & 7) || ((uintptr_t)span_counts & 7) || ((uintptr_t)spans & 7) || ((uintptr_t)offsets & 7))
-        return fail(HRX_ERR_ARG, "offsets, status, span_counts and spans must be 8-byte aligned");
-    return HRX_OK;
-}
-
-// ragged "via rows": strings per slice, so that the witness rows and the slice's string-major input (+ lens) fit the scratch bound together
-static size_t ragged_via_rows_slice(size_t B, size_t M, size_t D) {
-    const size_t stride = (M + 15) & ~(size_t)15;
-    const size_t per = ((M + 3) / 4) * 4 * D * 4 + ((M + 7) / 8) * 8 * 2 + stride + 4;
-    size_t n = kMatchScratchBytes / per;
-    if (n == 0) return 0;
-    if (n >= kPmBlock) n = n / kPmBlock * kPmBlock;
-    return std::min(n, B);
-}
-
-// the device part of the ragged match (device pointers; ctx->mu held, the device selected)
-static int match_ragged_device_locked(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t M,
-                                      uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
-    if (B == 0) return HRX_OK;
-    MatchPlan p;
-    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, HRX_LAYOUT_STRING_MAJOR, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
-    MatchArgs m{};
-    m.M = (uint32_t)M; m.max_spans = (uint32_t)max_spans;
-    if (p.fused) {
-        RaggedMatchArgs r{};
-        r.m = m;
-        r.m.chars = values; r.m.B = (uint32_t)B; r.m.D = (uint32_t)ctx->s.defs.size();
-        r.m.table_image = ctx->d_table; r.m.half_image = ctx->d_half; r.m.table_bytes = (uint32_t)p.lds_bytes;
-        r.m.status = status; r.m.span_counts = span_counts; r.m.spans = spans;
-        for (uint32_t d = 0; d < r.m.D; ++d) r.m.dc[d] = ctx->s.consts[d];
-        r.offsets = offsets; r.base = base;
-        HIP_TRY(launch_match_ragged(r, p, ctx->num_cus, st));
-        return HRX_OK;
-    }
-    // ---- via rows: each slice's strings string-major into scratch (ragged_slice_kernel), then the steps of the padded path.  Scratch rules as there
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(st, &cap));
-    const bool capturing = cap != hipStreamCaptureStatusNone;
-    const size_t D = ctx->s.defs.size();
-    const size_t slice = ragged_via_rows_slice(B, M, D);
-    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
-    const size_t stride = (M + 15) & ~(size_t)15;
-    const size_t noct = (M + 7) / 8, nquad = (M + 3) / 4;
-    const size_t rec_bytes = nquad * 4 * D * 4 * slice, msk_bytes = noct * 8 * 2 * slice, chr_bytes = slice * stride, len_bytes = slice * 4;
+    if (v.slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
+    const size_t D = ctx->s.defs.size(), noct = (M + 7) / 8, nquad = (M + 3) / 4;
+    const size_t rec_bytes = nquad * 4 * D * 4 * v.slice, msk_bytes = noct * 8 * 2 * v.slice;
+    const size_t chr_bytes = v.ragged || v.gather ? v.slice * v.stride : 0, len_bytes = v.ragged ? v.slice * 4 : 0;
     if (rec_bytes > ctx->match_rec.cap || msk_bytes > ctx->match_msk.cap || chr_bytes > ctx->match_chars.cap || len_bytes > ctx->match_lens.cap) {
         if (capturing) return fail(HRX_ERR_STATE, "match via rows: the context's scratch is allocated at first use, not inside a stream capture");
         HIP_TRY(hipDeviceSynchronize());     // (the buffers may be in use by earlier launches)
@@ -183,18 +119,99 @@ static int match_ragged_device_locked(hrx_ctx *ctx, const uint8_t *values, const
     }
     ctx->match_used = true;
     ctx->match_stream = st;
-    for (size_t b0 = 0; b0 < B; b0 += slice) {
-        const size_t n = std::min(slice, B - b0);
-        uint8_t *c = (uint8_t *)ctx->match_chars.p;
-        uint32_t *lens = (uint32_t *)ctx->match_lens.p;
-        HIP_TRY(launch_ragged_slice(values, offsets, base, b0, n, (uint32_t)M, stride, c, lens, st));
-        if (int rc = launch_batch(ctx, c, stride, lens, n, M, (uint32_t *)ctx->match_rec.p, (uint16_t *)ctx->match_msk.p, status + b0, st, 0, 0, HRX_LAYOUT_POSITION_MAJOR)) return rc;
+    return HRX_OK;
+}
+
+// slice by slice: stage(b0, n, chars, lens) gives the input of strings [b0, b0 + n) as the witness launch reads it (v.layout, v.stride), then the
+// position-major witness launch into the scratch and the runs of its masked rows
+template <class Stage>
+static int match_via_rows(hrx_ctx *ctx, const ViaRows &v, size_t B, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans,
+                          hipStream_t st, const Stage &stage) {
+    if (int rc = via_rows_scratch(ctx, v, M, st)) return rc;      // first: it may allocate the buffers read below
+    MatchArgs m{};
+    m.M = (uint32_t)M; m.max_spans = (uint32_t)max_spans; m.masked = (const uint16_t *)ctx->match_msk.p;
+    for (size_t b0 = 0; b0 < B; b0 += v.slice) {
+        const size_t n = std::min(v.slice, B - b0);
+        const uint8_t *c = nullptr;
+        const uint32_t *lens = nullptr;
+        if (int rc = stage(b0, n, c, lens)) return rc;
+        if (int rc = launch_batch(ctx, c, v.stride, lens, n, M, (uint32_t *)ctx->match_rec.p, (uint16_t *)ctx->match_msk.p, status + b0, st, 0, 0, v.layout)) return rc;
         if (max_spans || span_counts) {
-            m.B = (uint32_t)n; m.masked = (const uint16_t *)ctx->match_msk.p; m.status = status + b0;
+            m.B = (uint32_t)n; m.status = status + b0;
             m.span_counts = span_counts ? span_counts + b0 : nullptr; m.spans = spans ? spans + b0 * max_spans : nullptr;
             HIP_TRY(launch_spans_from_masked(m, st));
         }
     }
+    return HRX_OK;
+}
+
+// the device part (device pointers; ctx->mu held, the device selected)
+static int match_device_locked(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
+                               uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
+    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
+        return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR or HRX_LAYOUT_INPUT_POSITION_MAJOR");
+    if ((stride & 15) || stride < 16 || ((uintptr_t)chars & 15))
+        return fail(HRX_ERR_ARG, "chars must be 16-byte aligned with stride % 16 == 0 and stride >= 16");
+    if (B == 0) return HRX_OK;
+    MatchPlan p;
+    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, layout, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.fused) {
+        MatchArgs m = fused_args(ctx, p, chars, B, M, status, span_counts, spans, max_spans);
+        m.stride = stride; m.lens = lens; m.in_pm = layout == HRX_LAYOUT_INPUT_POSITION_MAJOR ? 1u : 0u;
+        HIP_TRY(launch_match_lane(m, p, st));
+        return HRX_OK;
+    }
+    const ViaRows v = plan_via_rows(layout, stride, B, M, ctx->s.defs.size());
+    return match_via_rows(ctx, v, B, M, status, span_counts, spans, max_spans, st, [&](size_t b0, size_t n, const uint8_t *&c, const uint32_t *&l) -> int {
+        c = chars + b0 * stride;      // (position-major input: whole blocks, b0 % kPmBlock == 0)
+        l = lens + b0;
+        if (v.gather) {
+            HIP_TRY(launch_pm_input_slice(chars, stride, B, b0, n, (uint8_t *)ctx->match_chars.p, st));
+            c = (const uint8_t *)ctx->match_chars.p;
+        }
+        return HRX_OK;
+    });
+}
+
+// the device part of the ragged match (device pointers; ctx->mu held, the device selected)
+static int match_ragged_device_locked(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t M,
+                                      uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
+    if (B == 0) return HRX_OK;
+    MatchPlan p;
+    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, HRX_LAYOUT_STRING_MAJOR, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.fused) {
+        RaggedMatchArgs r{};
+        r.m = fused_args(ctx, p, values, B, M, status, span_counts, spans, max_spans);
+        r.offsets = offsets; r.base = base;
+        HIP_TRY(launch_match_ragged(r, p, ctx->num_cus, st));
+        return HRX_OK;
+    }
+    const ViaRows v = plan_via_rows(HRX_LAYOUT_INPUT_RAGGED, 0, B, M, ctx->s.defs.size());
+    return match_via_rows(ctx, v, B, M, status, span_counts, spans, max_spans, st, [&](size_t b0, size_t n, const uint8_t *&c, const uint32_t *&l) -> int {
+        c = (const uint8_t *)ctx->match_chars.p;
+        l = (const uint32_t *)ctx->match_lens.p;
+        HIP_TRY(launch_ragged_slice(values, offsets, base, b0, n, (uint32_t)M, v.stride, (uint8_t *)ctx->match_chars.p, (uint32_t *)ctx->match_lens.p, st));
+        return HRX_OK;
+    });
+}
+
+// the host entry points' device buffers for the results of a chunk of n strings (d_counts / d_spans: NULL where nothing is to come back) ...
+static int host_result_bufs(hrx_ctx *ctx, size_t n, bool want_counts, size_t max_spans, uint32_t *&d_counts, uint64_t *&d_spans) {
+    HIP_TRY(ctx->status.reserve(8 * n));
+    HIP_TRY(ctx->match_counts.reserve(4 * n + 8));
+    if (max_spans) HIP_TRY(ctx->match_spans.reserve(8 * n * max_spans));
+    d_counts = (want_counts || max_spans) ? (uint32_t *)ctx->match_counts.p : nullptr;
+    d_spans = max_spans ? (uint64_t *)ctx->match_spans.p : nullptr;
+    return HRX_OK;
+}
+// ... and their way back: strings [b0, b0 + n) of the caller's arrays, complete when this returns
+static int host_results_out(hrx_ctx *ctx, size_t b0, size_t n, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans,
+                            const uint32_t *d_counts, const uint64_t *d_spans, hipStream_t st) {
+    HIP_TRY(hipMemcpyAsync(status + b0, ctx->status.p, 8 * n, hipMemcpyDeviceToHost, st));
+    if (span_counts) HIP_TRY(hipMemcpyAsync(span_counts + b0, d_counts, 4 * n, hipMemcpyDeviceToHost, st));
+    if (max_spans) HIP_TRY(hipMemcpyAsync(spans + b0 * max_spans, d_spans, 8 * n * max_spans, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     return HRX_OK;
 }
 
@@ -203,7 +220,7 @@ extern "C" {
 int hrx_match_batch_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
                            uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
-    if (int rc = check_match_args(chars, stride, lens, B, M, status, span_counts, spans, max_spans)) return rc;
+    if (int rc = check_match_args(chars, lens, B, M, status, span_counts, spans, max_spans)) return rc;
     if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
@@ -214,7 +231,7 @@ int hrx_match_batch_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_
 int hrx_match_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
                          uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
-    if (int rc = check_match_args(chars, stride, lens, B, M, status, span_counts, spans, max_spans)) return rc;
+    if (int rc = check_match_args(chars, lens, B, M, status, span_counts, spans, max_spans)) return rc;
     if (B == 0) return HRX_OK;
     for (size_t b = 0; b < B; ++b)
         if (lens[b] <= M && lens[b] > stride) return fail(HRX_ERR_ARG, "a string is longer than the stride");
@@ -232,24 +249,19 @@ int hrx_match_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, cons
     cb = std::min(cb, B);
     HIP_TRY(ctx->chars.reserve(dstride * cb + 16));
     HIP_TRY(ctx->lens.reserve(4 * cb));
-    HIP_TRY(ctx->status.reserve(8 * cb));
-    HIP_TRY(ctx->match_counts.reserve(4 * cb + 8));
-    if (max_spans) HIP_TRY(ctx->match_spans.reserve(8 * cb * max_spans));
+    uint32_t *d_counts;
+    uint64_t *d_spans;
+    if (int rc = host_result_bufs(ctx, cb, span_counts != nullptr, max_spans, d_counts, d_spans)) return rc;
     hipStream_t st = ctx->stream;
     for (size_t b0 = 0; b0 < B; b0 += cb) {
         const size_t n = std::min(cb, B - b0);
         if (dstride != stride) HIP_TRY(hipMemsetAsync(ctx->chars.p, 0, dstride * n, st));
         HIP_TRY(hipMemcpy2DAsync(ctx->chars.p, dstride, chars + b0 * stride, stride, stride, n, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ctx->lens.p, lens + b0, 4 * n, hipMemcpyHostToDevice, st));
-        uint32_t *d_counts = (span_counts || max_spans) ? (uint32_t *)ctx->match_counts.p : nullptr;
-        uint64_t *d_spans = max_spans ? (uint64_t *)ctx->match_spans.p : nullptr;
         if (int rc = match_device_locked(ctx, HRX_LAYOUT_STRING_MAJOR, (const uint8_t *)ctx->chars.p, dstride, (const uint32_t *)ctx->lens.p, n, M,
                                          (uint64_t *)ctx->status.p, d_counts, d_spans, max_spans, st))
             return rc;
-        HIP_TRY(hipMemcpyAsync(status + b0, ctx->status.p, 8 * n, hipMemcpyDeviceToHost, st));
-        if (span_counts) HIP_TRY(hipMemcpyAsync(span_counts + b0, d_counts, 4 * n, hipMemcpyDeviceToHost, st));
-        if (max_spans) HIP_TRY(hipMemcpyAsync(spans + b0 * max_spans, d_spans, 8 * n * max_spans, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = host_results_out(ctx, b0, n, status, span_counts, spans, max_spans, d_counts, d_spans, st)) return rc;
     }
     return HRX_OK;
 }
@@ -303,20 +315,15 @@ int hrx_match_batch_host_ragged(hrx_ctx *ctx, const uint8_t *values, const uint6
         const size_t bytes = (size_t)(hi - lo);
         HIP_TRY(ctx->chars.reserve(((bytes + 15) & ~(size_t)15) + 16));
         HIP_TRY(ctx->lens.reserve(8 * (n + 1)));
-        HIP_TRY(ctx->status.reserve(8 * n));
-        HIP_TRY(ctx->match_counts.reserve(4 * n + 8));
-        if (max_spans) HIP_TRY(ctx->match_spans.reserve(8 * n * max_spans));
+        uint32_t *d_counts;
+        uint64_t *d_spans;
+        if (int rc = host_result_bufs(ctx, n, span_counts != nullptr, max_spans, d_counts, d_spans)) return rc;
         if (bytes) HIP_TRY(hipMemcpyAsync(ctx->chars.p, values + lo, bytes, hipMemcpyHostToDevice, st));
         HIP_TRY(hipMemcpyAsync(ctx->lens.p, offsets + b0, 8 * (n + 1), hipMemcpyHostToDevice, st));
-        uint32_t *d_counts = (span_counts || max_spans) ? (uint32_t *)ctx->match_counts.p : nullptr;
-        uint64_t *d_spans = max_spans ? (uint64_t *)ctx->match_spans.p : nullptr;
         if (int rc = match_ragged_device_locked(ctx, (const uint8_t *)ctx->chars.p, (const uint64_t *)ctx->lens.p, lo, n, M, (uint64_t *)ctx->status.p,
                                                 d_counts, d_spans, max_spans, st))
             return rc;
-        HIP_TRY(hipMemcpyAsync(status + b0, ctx->status.p, 8 * n, hipMemcpyDeviceToHost, st));
-        if (span_counts) HIP_TRY(hipMemcpyAsync(span_counts + b0, d_counts, 4 * n, hipMemcpyDeviceToHost, st));
-        if (max_spans) HIP_TRY(hipMemcpyAsync(spans + b0 * max_spans, d_spans, 8 * n * max_spans, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = host_results_out(ctx, b0, n, status, span_counts, spans, max_spans, d_counts, d_spans, st)) return rc;
         b0 = b1;
     }
     return HRX_OK;
@@ -337,43 +344,24 @@ int hrx_ragged_to_position_major_device(hrx_ctx *ctx, const uint8_t *values, con
     return HRX_OK;
 }
 
-static int describe_match_ragged(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_rows, size_t B, size_t M, int num_cus, char *out, size_t cap) {
-    MatchPlan p;
-    if (!match_plan(s, dbg, via_rows, HRX_LAYOUT_STRING_MAJOR, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
-    if (p.fused) {
-        std::snprintf(out, cap, "hrx::match_ragged_kernel<%zu, %s, %s> grid=persistent threads=%d lds=%zu", s.defs.size(), p.gtab ? "true" : "false",
-                      p.half ? "true" : "false", p.threads, p.lds_bytes);
-        return HRX_OK;
-    }
-    const size_t slice = ragged_via_rows_slice(B, M, s.defs.size());
-    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
-    char w[3072];
-    if (int rc = describe_config(s, dbg, 0u, mpc_on, HRX_LAYOUT_POSITION_MAJOR, slice, M, num_cus, w, sizeof w)) return rc;
-    std::snprintf(out, cap, "via rows, %zu slice(s) of %zu strings: hrx::ragged_slice_kernel + %s + hrx::spans_from_masked_pm_kernel",
-                  (B + slice - 1) / slice, slice, w);
-    return HRX_OK;
-}
-
 static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_rows, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
-    if (layout == HRX_LAYOUT_INPUT_RAGGED) return describe_match_ragged(s, dbg, mpc_on, via_rows, B, M, num_cus, out, cap);
-    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
+    const bool ragged = layout == HRX_LAYOUT_INPUT_RAGGED;
+    if (!ragged && layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
         return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR, HRX_LAYOUT_INPUT_POSITION_MAJOR or HRX_LAYOUT_INPUT_RAGGED");
     MatchPlan p;
-    if (!match_plan(s, dbg, via_rows, layout, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (!match_plan(s, dbg, via_rows, ragged ? HRX_LAYOUT_STRING_MAJOR : layout, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
     if (p.fused) {
-        std::snprintf(out, cap, "hrx::match_lane_kernel<%zu, %s, %s> grid=%d threads=%d lds=%zu", s.defs.size(), p.gtab ? "true" : "false", p.half ? "true" : "false",
-                      p.grid, p.threads, p.lds_bytes);
+        const char *g = p.gtab ? "true" : "false", *h = p.half ? "true" : "false";
+        if (ragged) std::snprintf(out, cap, "hrx::match_ragged_kernel<%zu, %s, %s> grid=persistent threads=%d lds=%zu", s.defs.size(), g, h, p.threads, p.lds_bytes);
+        else std::snprintf(out, cap, "hrx::match_lane_kernel<%zu, %s, %s> grid=%d threads=%d lds=%zu", s.defs.size(), g, h, p.grid, p.threads, p.lds_bytes);
         return HRX_OK;
     }
-    const size_t slice = via_rows_slice(B, M, s.defs.size());
-    if (slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
-    const bool in_pm = layout == HRX_LAYOUT_INPUT_POSITION_MAJOR;
-    const bool gather = in_pm && slice < B && slice < kPmBlock;
+    const ViaRows v = plan_via_rows(layout, 0, B, M, s.defs.size());
+    if (v.slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
     char w[3072];
-    const int wl = HRX_LAYOUT_POSITION_MAJOR | (in_pm && !gather ? HRX_LAYOUT_INPUT_POSITION_MAJOR : 0);
-    if (int rc = describe_config(s, dbg, 0u, mpc_on, wl, slice, M, num_cus, w, sizeof w)) return rc;
-    std::snprintf(out, cap, "via rows, %zu slice(s) of %zu strings: %s%s + hrx::spans_from_masked_pm_kernel", (B + slice - 1) / std::max<size_t>(1, slice), slice,
-                  gather ? "hrx::pm_input_slice_kernel + " : "", w);
+    if (int rc = describe_config(s, dbg, 0u, mpc_on, v.layout, v.slice, M, num_cus, w, sizeof w)) return rc;
+    std::snprintf(out, cap, "via rows, %zu slice(s) of %zu strings: %s%s + hrx::spans_from_masked_pm_kernel", (B + v.slice - 1) / v.slice, v.slice,
+                  ragged ? "hrx::ragged_slice_kernel + " : v.gather ? "hrx::pm_input_slice_kernel + " : "", w);
     return HRX_OK;
 }
 

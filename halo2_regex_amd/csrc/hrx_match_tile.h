@@ -1,6 +1,11 @@
-// hrx_match_tile.h — the tile walk of the fused MATCH kernels (hrx_kernel_match.hip: padded input, hrx_kernel_ragged.hip: ragged input):
-// one lane walks 64 rows of one string over every def and returns the tile's bitvectors and substr-id bytes; the kernels differ only in where
-// the 64 input bytes come from.  Included after hrx_device.h and hrx_walk_pm.h.
+// hrx_match_tile.h — the lane core of the fused MATCH kernels (hrx_kernel_match.hip: padded input, hrx_kernel_ragged.hip: ragged input).
+//   match_stage_table   the table into LDS, once per workgroup
+//   match_walk_tile     one lane walks 64 rows of one string over every def and returns the tile's bitvectors and substr-id bytes
+//   MatchLane           a lane's state for one string: reset, one tile (walk, first undefined transition, masks, runs), finish (status word, count)
+//   fused_kernel<K>     host side: the launch ladder of both kernels, D x {narrow LDS, HALF, global table} with the dynamic-LDS grant
+// The kernels keep what differs: where a tile's 64 input bytes come from, the loop around the tile and the FULL decision.  MatchLane's arrays are
+// indexed by unrolled loops only and every member function is inlined into the kernel, so the state lives in registers (no scratch memory).
+// Included after hrx_device.h and hrx_walk_pm.h.
 #pragma once
 
 namespace hrx {
@@ -78,6 +83,128 @@ __device__ __forceinline__ TileBits match_walk_tile(const uint4 (&cq)[4], const 
     tb.en1 = (uint64_t)en1[0] | ((uint64_t)en1[1] << 32);
     tb.ch = (uint64_t)ch[0] | ((uint64_t)ch[1] << 32);
     return tb;
+}
+
+// the table at LDS offset 0 (the kernels declare no static LDS)
+template <bool GTAB, bool HALF>
+__device__ __forceinline__ void match_stage_table(const MatchArgs &a) {
+    if (GTAB) return;
+    const uint32_t tab16 = (a.table_bytes + 15u) & ~15u;
+    const uint8_t *img = HALF ? reinterpret_cast<const uint8_t *>(a.half_image) : reinterpret_cast<const uint8_t *>(a.table_image);
+    for (uint32_t i = threadIdx.x * 16u; i < tab16; i += blockDim.x * 16u)
+        *reinterpret_cast<uint4 *>(smem + i) = *reinterpret_cast<const uint4 *>(img + i);
+    __syncthreads();
+}
+
+// one lane's walk of one string
+template <int D, bool GTAB, bool HALF>
+struct MatchLane {
+    uint32_t e[D], mx[D], acc_state[D], dead_row[D], err_state[D], err_char[D];
+    uint32_t sid_prev, ov_row;
+    MaskCarry mc;
+    SpanEmitter em;
+    uint64_t *slots;        // the string's run slots (NULL: none)
+
+    // the start of string b
+    __device__ __forceinline__ void reset(const MatchArgs &a, size_t b) {
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            e[d] = HALF ? a.dc[d].half_row_base + a.dc[d].first_state : a.dc[d].first_entry;       // states[d][0] = first_state_val: lib.rs:807
+            mx[d] = 0;
+            acc_state[d] = a.dc[d].first_state;
+            dead_row[d] = 0xffffffffu;
+        }
+        sid_prev = 0;
+        ov_row = 0xffffffffu;
+        mc = MaskCarry{0, 0, 0, 0};
+        em.init();
+        slots = a.spans ? a.spans + b * a.max_spans : nullptr;
+    }
+
+    // rows [t0, t0 + 64) of a string of n bytes: cq holds the tile's bytes (zero past n), byte_at(r) is byte r < n of the string.
+    // full: every row of the tile is < n and < M - 1 (the caller may pass false for such a tile: the general walk gives the same bits).
+    // last: no tile of this string is walked after this one
+    template <class ByteAt>
+    __device__ __forceinline__ void tile(const MatchArgs &a, const uint4 (&cq)[4], uint32_t t0, uint32_t n, bool last, bool full, const ByteAt &byte_at) {
+        const uint32_t M = a.M;
+        uint32_t e0[D], mx0[D];
+#pragma unroll
+        for (int d = 0; d < D; ++d) { e0[d] = e[d]; mx0[d] = mx[d]; }
+        uint64_t nz;
+        uint32_t sidq[16];
+        const TileBits tb = full ? match_walk_tile<D, true, GTAB, HALF>(cq, a, e, mx, sid_prev, ov_row, acc_state, t0, n, nz, sidq)
+                                 : match_walk_tile<D, false, GTAB, HALF>(cq, a, e, mx, sid_prev, ov_row, acc_state, t0, n, nz, sidq);
+        // the first undefined transition of a def (rare: the tile is walked again row by row to find its row, state and byte)
+#pragma unroll
+        for (int d = 0; d < D; ++d) {
+            if (dead_row[d] == 0xffffffffu && mx[d] >= match_dead<HALF>(a, d) && mx0[d] < match_dead<HALF>(a, d)) {
+                uint32_t x = e0[d];
+                for (uint32_t p = 0; p < 64u && t0 + p < n; ++p) {
+                    const uint32_t ch = byte_at(t0 + p);
+                    const uint32_t ne = match_next<GTAB, HALF>(a, x, ch);
+                    if (ne >= match_dead<HALF>(a, d)) {
+                        dead_row[d] = t0 + p;
+                        err_state[d] = match_state<HALF>(a, d, x);
+                        err_char[d] = ch;
+                        break;
+                    }
+                    x = ne;
+                }
+            }
+        }
+        if (n == M && last) {   // n == M: row n does not exist, s[n] is the live state
+#pragma unroll
+            for (int d = 0; d < D; ++d) acc_state[d] = match_state<HALF>(a, d, e[d]);
+        }
+        // reveal masks (lib.rs:598-764) and the runs they make
+        const TileMasks tm = tile_masks<64>(tb, mc, t0, tile_is_exact(t0, n, M), rows_below(t0, n));
+        SpanSlots out{slots, a.max_spans};
+        if (a.max_spans || a.span_counts) em.tile(tm, mc, tb.ch, nz, t0, min(64u, M - t0), [&](int p) { return sid_byte(sidq, p); }, out);
+    }
+
+    // after the last tile: the status word and the run count of string b
+    __device__ __forceinline__ void finish(const MatchArgs &a, size_t b) {
+        SpanSlots out{slots, a.max_spans};
+        em.finish(a.M, out);
+        uint64_t status = 0;
+        bool done = false;
+#pragma unroll
+        for (int d = 0; d < D; ++d)   // lowest def wins: the reference walks defs in order (lib.rs:806)
+            if (!done && dead_row[d] != 0xffffffffu) { status = status_invalid((uint32_t)d, dead_row[d], err_state[d], err_char[d]); done = true; }
+        if (!done && D > 1 && ov_row != 0xffffffffu) { status = status_overlap(ov_row); done = true; }
+        if (!done) {
+            uint32_t accept = 0;
+#pragma unroll
+            for (int d = 0; d < D; ++d) accept |= (acc_state[d] == a.dc[d].accepted_state ? 1u : 0u) << d;
+            status = status_ok(accept);
+        }
+        a.status[b] = status;
+        if (a.span_counts) a.span_counts[b] = done ? 0u : em.count;
+    }
+};
+
+// the kernel a fused launch runs: K::get<D, GTAB, HALF>() for the plan's table form, with the plan's dynamic LDS granted (host side; K names
+// one of the two kernel templates, K::fn is its function-pointer type)
+template <class K, int D, bool GTAB, bool HALF>
+static hipError_t fused_kernel_one(const MatchPlan &p, typename K::fn &k) {
+    static std::atomic<size_t> granted{0};
+    k = K::template get<D, GTAB, HALF>();
+    return p.lds_bytes ? ensure_lds(k, granted, p.lds_bytes) : hipSuccess;
+}
+template <class K, int D>
+static hipError_t fused_kernel_d(const MatchPlan &p, typename K::fn &k) {
+    if (p.half) return fused_kernel_one<K, D, false, true>(p, k);
+    if (p.gtab) return fused_kernel_one<K, D, true, false>(p, k);
+    return fused_kernel_one<K, D, false, false>(p, k);
+}
+template <class K>
+static hipError_t fused_kernel(uint32_t D, const MatchPlan &p, typename K::fn &k) {
+    switch (D) {
+    case 1: return fused_kernel_d<K, 1>(p, k);
+    case 2: return fused_kernel_d<K, 2>(p, k);
+    case 3: return fused_kernel_d<K, 3>(p, k);
+    default: return hipErrorInvalidValue;
+    }
 }
 
 }  // namespace hrx

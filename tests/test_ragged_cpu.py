@@ -187,6 +187,25 @@ def test_describe_match_ragged_names_the_kernels():
     assert _cfg(CFG_1, 1024).describe_match(65536).startswith("hrx::match_lane_kernel<1, false, false> grid=256 threads=256 ")
 
 
+def test_describe_match_text_in_full():
+    """hrx_describe_match, the complete text (DESCRIBE_MATCH_TEXT below, recorded before the padded and the ragged form came to share their via-rows
+    arithmetic): the fused kernel and its launch shape, the slice counts and sizes of both via-rows forms, the gather decision"""
+    import ctypes as C
+    cfgs = {"regex1": CFG_1, "regex23": CFG_23, "headers3": CFG_H3, "headers4": CFG_H4}
+    built = {}
+    assert len(DESCRIBE_MATCH_TEXT) == 4 * 3 * 4 * 2
+    for (name, layout, B, M, via_rows), want in DESCRIBE_MATCH_TEXT.items():
+        cfg = built.get((name, M)) or built.setdefault((name, M), _cfg(cfgs[name], M))
+        buf = C.create_string_buffer(4096)
+        if via_rows:
+            os.environ["HRX_DEBUG_FLAGS"] = str(1 << 32)
+        try:
+            rc = hra.lib.hrx_describe_match(cfg._defs.h, layout, B, M, 256, buf, 4096)
+        finally:
+            os.environ.pop("HRX_DEBUG_FLAGS", None)
+        assert rc == hra.HRX_OK and buf.value.decode() == want, (name, layout, B, M, via_rows)
+
+
 def test_pack_strings_and_match_strings_round_trip(oracle):
     strings = [b"", b"a", b"email was meant for @y.", bytes(range(256)), b"x" * 1000, b"email was meant for @bob. tail"]
     values, offsets = hra.pack_strings(strings)
@@ -202,3 +221,104 @@ def test_pack_strings_and_match_strings_round_trip(oracle):
     assert got[2] == [(1, 21, b"y")] and got[5] == [(1, 21, b"bob")]
     assert got == hra.revealed_substrings(*_padded(strings, M), st, cnt, sp)
     check_ragged(oracle, CFG_1, strings, M)
+
+
+# (config, layout, B, M, HRX_DEBUG_FLAGS bit 32) -> hrx_describe_match with num_cus = 256.  Layouts: 0 string-major, 2 position-major input, 8 ragged
+DESCRIBE_MATCH_TEXT = {
+    ('regex1', 0, 65536, 1024, False): 'hrx::match_lane_kernel<1, false, false> grid=256 threads=256 lds=31744',
+    ('regex1', 0, 65536, 1024, True): 'via rows, 1 slice(s) of 65536 strings: hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 2, 65536, 1024, False): 'hrx::match_lane_kernel<1, false, false> grid=256 threads=256 lds=31744',
+    ('regex1', 2, 65536, 1024, True): 'via rows, 1 slice(s) of 65536 strings: hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 8, 65536, 1024, False): 'hrx::match_ragged_kernel<1, false, false> grid=persistent threads=256 lds=31744',
+    ('regex1', 8, 65536, 1024, True): 'via rows, 1 slice(s) of 65536 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 0, 300, 1024, False): 'hrx::match_lane_kernel<1, false, false> grid=5 threads=64 lds=31744',
+    ('regex1', 0, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pp_kernel grid=5 waves=3 ring=4 lds=117056 + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 2, 300, 1024, False): 'hrx::match_lane_kernel<1, false, false> grid=5 threads=64 lds=31744',
+    ('regex1', 2, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pp_kernel grid=5 waves=3 ring=4 lds=117056 + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 8, 300, 1024, False): 'hrx::match_ragged_kernel<1, false, false> grid=persistent threads=64 lds=31744',
+    ('regex1', 8, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::ragged_slice_kernel + hrx::witness_pp_kernel grid=5 waves=3 ring=4 lds=117056 + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 0, 4500, 32768, False): 'via rows, 2 slice(s) of 4096 strings: hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 0, 4500, 32768, True): 'via rows, 2 slice(s) of 4096 strings: hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 2, 4500, 32768, False): 'via rows, 2 slice(s) of 4096 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 2, 4500, 32768, True): 'via rows, 2 slice(s) of 4096 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 8, 4500, 32768, False): 'via rows, 2 slice(s) of 3510 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 8, 4500, 32768, True): 'via rows, 2 slice(s) of 3510 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 0, 8192, 32768, False): 'via rows, 2 slice(s) of 4096 strings: hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 0, 8192, 32768, True): 'via rows, 2 slice(s) of 4096 strings: hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 2, 8192, 32768, False): 'via rows, 2 slice(s) of 4096 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 2, 8192, 32768, True): 'via rows, 2 slice(s) of 4096 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 8, 8192, 32768, False): 'via rows, 3 slice(s) of 3510 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex1', 8, 8192, 32768, True): 'via rows, 3 slice(s) of 3510 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<1, false, false, false, false, false> grid=256 waves=12 ring=4 lds=138752 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 0, 65536, 1024, False): 'hrx::match_lane_kernel<2, false, false> grid=256 threads=256 lds=37888',
+    ('regex23', 0, 65536, 1024, True): 'via rows, 1 slice(s) of 65536 strings: hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 2, 65536, 1024, False): 'hrx::match_lane_kernel<2, false, false> grid=256 threads=256 lds=37888',
+    ('regex23', 2, 65536, 1024, True): 'via rows, 1 slice(s) of 65536 strings: hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 8, 65536, 1024, False): 'hrx::match_ragged_kernel<2, false, false> grid=persistent threads=256 lds=37888',
+    ('regex23', 8, 65536, 1024, True): 'via rows, 1 slice(s) of 65536 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 0, 300, 1024, False): 'hrx::match_lane_kernel<2, false, false> grid=5 threads=64 lds=37888',
+    ('regex23', 0, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<2, false, false, false> grid=5 waves=3 ring=4 lds=66752 + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 2, 300, 1024, False): 'hrx::match_lane_kernel<2, false, false> grid=5 threads=64 lds=37888',
+    ('regex23', 2, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<2, false, false, false> grid=5 waves=3 ring=4 lds=66752 + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 8, 300, 1024, False): 'hrx::match_ragged_kernel<2, false, false> grid=persistent threads=64 lds=37888',
+    ('regex23', 8, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<2, false, false, false> grid=5 waves=3 ring=4 lds=66752 + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 0, 4500, 32768, False): 'via rows, 2 slice(s) of 2457 strings: hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 0, 4500, 32768, True): 'via rows, 2 slice(s) of 2457 strings: hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 2, 4500, 32768, False): 'via rows, 2 slice(s) of 2457 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 2, 4500, 32768, True): 'via rows, 2 slice(s) of 2457 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 8, 4500, 32768, False): 'via rows, 3 slice(s) of 2234 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 8, 4500, 32768, True): 'via rows, 3 slice(s) of 2234 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 0, 8192, 32768, False): 'via rows, 4 slice(s) of 2457 strings: hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 0, 8192, 32768, True): 'via rows, 4 slice(s) of 2457 strings: hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 2, 8192, 32768, False): 'via rows, 4 slice(s) of 2457 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 2, 8192, 32768, True): 'via rows, 4 slice(s) of 2457 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 8, 8192, 32768, False): 'via rows, 4 slice(s) of 2234 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('regex23', 8, 8192, 32768, True): 'via rows, 4 slice(s) of 2234 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<2, false, true, false, false, false> grid=256 waves=12 ring=4 lds=144896 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 0, 65536, 1024, False): 'hrx::match_lane_kernel<3, false, false> grid=256 threads=256 lds=76800',
+    ('headers3', 0, 65536, 1024, True): 'via rows, 2 slice(s) of 56173 strings: hrx::witness_pm_kernel<3, false, true, false, false, false> grid=220 waves=12 ring=2 lds=151040 + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 2, 65536, 1024, False): 'hrx::match_lane_kernel<3, false, false> grid=256 threads=256 lds=76800',
+    ('headers3', 2, 65536, 1024, True): 'via rows, 2 slice(s) of 56173 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=220 waves=12 ring=2 lds=151040 + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 8, 65536, 1024, False): 'hrx::match_ragged_kernel<3, false, false> grid=persistent threads=256 lds=76800',
+    ('headers3', 8, 65536, 1024, True): 'via rows, 2 slice(s) of 52415 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=205 waves=12 ring=2 lds=151040 + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 0, 300, 1024, False): 'hrx::match_lane_kernel<3, false, false> grid=5 threads=64 lds=76800',
+    ('headers3', 0, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<3, false, false, false> grid=5 waves=4 ring=4 lds=117952 + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 2, 300, 1024, False): 'hrx::match_lane_kernel<3, false, false> grid=5 threads=64 lds=76800',
+    ('headers3', 2, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<3, false, false, false> grid=5 waves=4 ring=4 lds=117952 + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 8, 300, 1024, False): 'hrx::match_ragged_kernel<3, false, false> grid=persistent threads=64 lds=76800',
+    ('headers3', 8, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<3, false, false, false> grid=5 waves=4 ring=4 lds=117952 + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 0, 4500, 32768, False): 'via rows, 3 slice(s) of 1755 strings: hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 0, 4500, 32768, True): 'via rows, 3 slice(s) of 1755 strings: hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 2, 4500, 32768, False): 'via rows, 3 slice(s) of 1755 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 2, 4500, 32768, True): 'via rows, 3 slice(s) of 1755 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 8, 4500, 32768, False): 'via rows, 3 slice(s) of 1638 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=208 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 8, 4500, 32768, True): 'via rows, 3 slice(s) of 1638 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=208 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 0, 8192, 32768, False): 'via rows, 5 slice(s) of 1755 strings: hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 0, 8192, 32768, True): 'via rows, 5 slice(s) of 1755 strings: hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 2, 8192, 32768, False): 'via rows, 5 slice(s) of 1755 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 2, 8192, 32768, True): 'via rows, 5 slice(s) of 1755 strings: hrx::pm_input_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=224 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 8, 8192, 32768, False): 'via rows, 6 slice(s) of 1638 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=208 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers3', 8, 8192, 32768, True): 'via rows, 6 slice(s) of 1638 strings: hrx::ragged_slice_kernel + hrx::witness_pm_kernel<3, false, true, false, false, false> grid=208 waves=12 ring=2 lds=151040 chunked=32x16 tiles: hrx::spec_scout_kernel + hrx::spec_compose_kernel before, hrx::spec_stitch_kernel behind + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 65536, 1024, False): 'via rows, 2 slice(s) of 43690 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=256 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 65536, 1024, True): 'via rows, 2 slice(s) of 43690 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=256 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 65536, 1024, False): 'via rows, 2 slice(s) of 43690 strings: hrx::pm_input_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=256 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 65536, 1024, True): 'via rows, 2 slice(s) of 43690 strings: hrx::pm_input_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=256 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 65536, 1024, False): 'via rows, 2 slice(s) of 41382 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=256 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 65536, 1024, True): 'via rows, 2 slice(s) of 41382 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=256 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 300, 1024, False): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=5 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=5 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 300, 1024, False): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=5 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=5 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 300, 1024, False): 'via rows, 1 slice(s) of 300 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=5 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 300, 1024, True): 'via rows, 1 slice(s) of 300 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=5 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 4500, 32768, False): 'via rows, 4 slice(s) of 1365 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 4500, 32768, True): 'via rows, 4 slice(s) of 1365 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 4500, 32768, False): 'via rows, 4 slice(s) of 1365 strings: hrx::pm_input_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 4500, 32768, True): 'via rows, 4 slice(s) of 1365 strings: hrx::pm_input_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 4500, 32768, False): 'via rows, 4 slice(s) of 1293 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=21 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 4500, 32768, True): 'via rows, 4 slice(s) of 1293 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=21 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 8192, 32768, False): 'via rows, 7 slice(s) of 1365 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 0, 8192, 32768, True): 'via rows, 7 slice(s) of 1365 strings: hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 8192, 32768, False): 'via rows, 7 slice(s) of 1365 strings: hrx::pm_input_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 2, 8192, 32768, True): 'via rows, 7 slice(s) of 1365 strings: hrx::pm_input_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=22 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 8192, 32768, False): 'via rows, 7 slice(s) of 1293 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=21 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+    ('headers4', 8, 8192, 32768, True): 'via rows, 7 slice(s) of 1293 strings: hrx::ragged_slice_kernel + hrx::witness_pmd_kernel<4, true, true, false> grid=21 waves=6 ring=4 lds=93888 + hrx::spans_from_masked_pm_kernel',
+}

@@ -101,6 +101,17 @@ def test_shapes_and_length_mixes(oracle, name, names, B, M, gen):
     _triple(oracle, cfg, names, chars, lens, M, lead=3)
 
 
+def test_via_rows_in_several_slices(oracle):
+    """ragged strings whose witness rows and staged input fill the scratch more than once: a string costs 131072 (records) + 65536 (masked rows) +
+    32768 (staged input) + 4 (its length) = 229380 bytes of the 768 MiB, so a slice is 3510 strings and 4500 strings take two (3510 + 990)"""
+    M, B = 32768, 4500
+    chars, _ = synth.regex1_planted(B, M, seed=4, stride=-(-(M + 1) // 16) * 16)
+    lens = _mixed_lengths(B, M, seed=B)
+    cfg = _cfg(CFG_1, M, 1 << 32)
+    assert cfg.describe_match(B, layout=hra.LAYOUT_INPUT_RAGGED).startswith("via rows, 2 slice(s) of 3510 strings")
+    _triple(oracle, cfg, CFG_1, chars, lens, M, lead=3)
+
+
 def test_half_table_dfa(oracle):
     M, B = 1024, 16384
     a_txt, sub = synth.random_dfa(256, seed=2, alphabet=np.arange(256, dtype=np.uint8), n_substr_pairs=40)

@@ -3,7 +3,8 @@ of one kind, the kinds taking turns.  Per length mix: hrx_match_batch_device_rag
 and position-major as the headline feeds it); then hrx_ragged_to_position_major_device against hrx_chars_to_position_major_device on full-length
 strings.  The ragged and padded results are compared after the timed region.  One JSON line per mix.
 
-  python tools/ragged_bench.py [--mixes all_M,uniform,skewed] [--B 65536] [--M 1024] [--steps 20]
+  python tools/ragged_bench.py [--config regex1|regex23|headers3] [--mixes all_M,uniform,skewed] [--B 65536] [--M 1024] [--steps 20]
+  (with HRX_DEBUG_FLAGS=0x40000 / 0x400000 in the environment: the global-table / HALF form of both kernels)
   rocprofv3 --kernel-trace --stats -d OUT -- python tools/ragged_bench.py      (a run of its own)
 """
 import argparse
@@ -21,7 +22,11 @@ import halo2_regex_amd as hra  # noqa: E402
 from halo2_regex_amd import synth  # noqa: E402
 from oracle_lib import DFA_DIR  # noqa: E402
 
-NAMES = [["regex1_test_lookup.txt", ["substr1_test_lookup.txt"]]]
+HDR = lambda n, ns: [n + "_lookup.txt", ["%s_substr%d.txt" % (n, k) for k in range(ns)]]
+# config: (defs, generator of planted strings) — one, two and three defs, so D = 1, 2, 3 of both fused kernels
+CONFIGS = {"regex1": ([["regex1_test_lookup.txt", ["substr1_test_lookup.txt"]]], synth.regex1_planted),
+           "regex23": ([["regex2_test_lookup.txt", ["substr2_test_lookup.txt"]], ["regex3_test_lookup.txt", ["substr3_test_lookup.txt"]]], synth.regex23_planted),
+           "headers3": ([HDR("header_from", 1), HDR("header_to", 1), HDR("header_subject", 3)], synth.headers_planted)}
 
 
 def lengths(mix, B, M, rng):
@@ -67,7 +72,7 @@ def timed(kinds, steps, K, dev):
 def one_mix(mix, args, cfg, dev):
     B, M, KS = args.B, args.M, args.max_spans
     rng = np.random.default_rng(0)
-    chars, _ = synth.regex1_planted(B, M, seed=0, stride=M)
+    chars, _ = CONFIGS[args.config][1](B, M, seed=0, stride=M)
     lens = lengths(mix, B, M, rng)
     chars[np.arange(M)[None, :] >= lens.astype(np.int64)[:, None]] = 0
     values, offsets = hra.pack_strings([chars[b, :lens[b]].tobytes() for b in range(B)])
@@ -84,7 +89,7 @@ def one_mix(mix, args, cfg, dev):
     same = all(np.array_equal(res["ragged"][j], res[k][j]) for k in ("padded_sm", "padded_pm") for j in (0, 1)) and \
         hra.decode_spans(res["ragged"][1].view(np.uint32), res["ragged"][2].view(np.uint64)) == \
         hra.decode_spans(res["padded_pm"][1].view(np.uint32), res["padded_pm"][2].view(np.uint64))
-    out = {"mix": mix, "B": B, "M": M, "mean_len": float(lens.mean()), "values_bytes": int(offsets[-1]),
+    out = {"config": args.config, "mix": mix, "B": B, "M": M, "mean_len": float(lens.mean()), "values_bytes": int(offsets[-1]),
            "ragged": cfg.describe_match(B, layout=hra.LAYOUT_INPUT_RAGGED), "padded": cfg.describe_match(B, layout=hra.LAYOUT_INPUT_POSITION_MAJOR),
            "ragged_us": t["ragged"], "padded_sm_us": t["padded_sm"], "padded_pm_us": t["padded_pm"],
            "ratio_vs_padded_sm": t["ragged"] / t["padded_sm"], "ratio_vs_padded_pm": t["ragged"] / t["padded_pm"], "same_results": bool(same)}
@@ -102,6 +107,7 @@ def one_mix(mix, args, cfg, dev):
 
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--config", default="regex1", choices=list(CONFIGS))
     ap.add_argument("--mixes", default="all_M,uniform,skewed")
     ap.add_argument("--B", type=int, default=65536)
     ap.add_argument("--M", type=int, default=1024)
@@ -111,7 +117,7 @@ def main():
     args = ap.parse_args()
     dev = torch.device("cuda", 0)
     defs = [hra.RegexDefs(hra.AllstrRegexDef.read_from_text(os.path.join(DFA_DIR, a)), [hra.SubstrRegexDef.read_from_text(os.path.join(DFA_DIR, s)) for s in subs])
-            for a, subs in NAMES]
+            for a, subs in CONFIGS[args.config][0]]
     cfg = hra.RegexVerifyConfig.configure(args.M, defs, device=0)
     for mix in args.mixes.split(","):
         print(json.dumps(one_mix(mix, args, cfg, dev)), flush=True)
