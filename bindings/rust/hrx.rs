@@ -15,6 +15,11 @@ pub struct hrx_place_report {
     pub probe_bytes: usize, pub peak_candidate_bytes: usize, pub search_ms: f64,
     pub capped: c_int,   // HRX_PLACE_CAPPED_* or-ed: which bound ended the walk (0: the acceptance rule itself)
 }
+#[repr(C)] #[derive(Clone, Copy)]
+pub struct hrx_extract_out {   // the output arrays of hrx_extract_spans_* and their capacities (include/hrx.h EXTRACT)
+    pub run_offsets: *mut u64, pub runs: *mut u64, pub byte_offsets: *mut u64, pub values: *mut u8,
+    pub totals: *mut u64, pub runs_cap: usize, pub values_cap: usize,
+}
 pub const HRX_PLACE_OFF: c_int = 0;
 pub const HRX_PLACE_WALK: c_int = 1;
 pub const HRX_PLACE_CAPPED_STEPS: c_int = 1;
@@ -53,6 +58,14 @@ extern "C" {
                                        status: *mut u64, span_counts: *mut u32, spans: *mut u64, max_spans: usize) -> c_int;
     pub fn hrx_ragged_to_position_major_device(ctx: *mut hrx_ctx, values: *const u8, offsets: *const u64, b: usize, stride: usize,
                                                chars_pm: *mut u8, lens: *mut u32, stream: *mut c_void) -> c_int;
+    // EXTRACT: a match call's outputs -> the revealed bytes as a list<large_binary> column (include/hrx.h); the device form runs in the caller's workspace
+    pub fn hrx_extract_workspace_bytes(b: usize) -> usize;
+    pub fn hrx_extract_spans_device(ctx: *mut hrx_ctx, layout: c_int, src: *const u8, stride: usize, offsets: *const u64, b: usize,
+                                    status: *const u64, span_counts: *const u32, spans: *const u64, max_spans: usize, require_accept: u32,
+                                    out: *const hrx_extract_out, workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_extract_spans_host(layout: c_int, src: *const u8, stride: usize, offsets: *const u64, b: usize,
+                                  status: *const u64, span_counts: *const u32, spans: *const u64, max_spans: usize, require_accept: u32,
+                                  out: *const hrx_extract_out, threads: c_int) -> c_int;
     pub fn hrx_witness_batch_device(ctx: *mut hrx_ctx, chars: *const u8, stride: usize, lens: *const u32, b: usize,
                                     m: usize, records: *mut u32, masked: *mut u16, status: *mut u64,
                                     stream: *mut c_void) -> c_int;

@@ -6,6 +6,7 @@ Rust surface for the path (src/defs.rs, src/table.rs, src/lib.rs:96-113,311-318,
 parity tests read like the reference's own tests.  There is no CPU implementation of the compute
 path: without the HIP library the import fails, and without a gfx950 device RegexVerifyConfig raises.
 """
+import collections
 import ctypes as C
 import os
 
@@ -40,6 +41,11 @@ class _HostRouteReportC(C.Structure):    # hrx_host_route_report of include/hrx.
     _fields_ = [("route", C.c_int), ("device_strings", C.c_size_t), ("host_strings", C.c_size_t), ("device_ms", C.c_double), ("host_ms", C.c_double), ("call_ms", C.c_double),
                 ("device_alone_ns_per_row", C.c_double), ("host_alone_ns_per_row", C.c_double), ("split_ns_per_row", C.c_double),
                 ("device_ns_per_row", C.c_double), ("host_ns_per_row", C.c_double), ("host_threads", C.c_int), ("device_pipelined", C.c_int)]
+
+
+class _ExtractOutC(C.Structure):       # hrx_extract_out of include/hrx.h
+    _fields_ = [("run_offsets", C.c_void_p), ("runs", C.c_void_p), ("byte_offsets", C.c_void_p), ("values", C.c_void_p), ("totals", C.c_void_p),
+                ("runs_cap", C.c_size_t), ("values_cap", C.c_size_t)]
 
 
 class _PlaceReportC(C.Structure):    # hrx_place_report of include/hrx.h
@@ -141,6 +147,9 @@ def _load():
         "hrx_match_batch_device_ragged": (i, [vp, vp, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host_ragged": (i, [vp, _u8p, _u64p, sz, sz, _u64p, _u32p, _u64p, sz]),
         "hrx_ragged_to_position_major_device": (i, [vp, vp, vp, sz, sz, vp, vp, vp]),
+        "hrx_extract_workspace_bytes": (sz, [sz]),
+        "hrx_extract_spans_device": (i, [vp, i, vp, sz, vp, sz, vp, vp, vp, sz, C.c_uint32, C.POINTER(_ExtractOutC), vp, sz, vp]),
+        "hrx_extract_spans_host": (i, [i, vp, sz, vp, sz, vp, vp, vp, sz, C.c_uint32, C.POINTER(_ExtractOutC), i]),
         "hrx_shard_range": (None, [sz, i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hrx_derive_states": (i, [vp, _u8p, sz, _u64p]),
         "hrx_derive_substr_ids": (i, [vp, _u64p, sz, _u64p]),
@@ -823,6 +832,73 @@ class RegexVerifyConfig:
                                                        stride, chars_pm.data_ptr(), lens.data_ptr(), s.cuda_stream))
         return chars_pm, lens
 
+    # -- extract: the revealed bytes as a list column (include/hrx.h EXTRACT) ------------------------------------------------
+    def alloc_extract(self, B, max_spans, values_cap, runs_cap=None, device=None):
+        """Device tensors for extract_spans / extract_batch*: (status, counts, spans, run_offsets, runs, byte_offsets, values, totals, workspace);
+        runs_cap defaults to B * max_spans, which always suffices, as values_cap = the input's byte count does."""
+        dev = torch.device("cuda", self.device) if device is None else torch.device(device)
+        runs_cap = B * max_spans if runs_cap is None else int(runs_cap)
+        i64 = lambda n: torch.empty(int(n), dtype=torch.int64, device=dev)
+        return (i64(B), torch.empty(B, dtype=torch.int32, device=dev), torch.empty((B, max_spans), dtype=torch.int64, device=dev), i64(B + 1), i64(runs_cap),
+                i64(runs_cap + 1), torch.empty(int(values_cap), dtype=torch.uint8, device=dev), i64(4), i64(extract_workspace_bytes(B) // 8))
+
+    def extract_spans(self, src, status, counts, spans, out, offsets=None, chars_pm_stride=None, require_accept=0, stream=None):
+        """hrx_extract_spans_device on the outputs of a match call: src = chars (B, stride), the position-major buffer (chars_pm_stride) or ragged values
+        (offsets); out = the tensors of alloc_extract from run_offsets on (run_offsets, runs, byte_offsets, values, totals, workspace): the caps are their
+        sizes.  Asynchronous on `stream`; four launches, nothing allocated."""
+        ro, runs, bo, vals, tot, ws = out
+        B, max_spans = status.numel(), spans.shape[1]
+        if offsets is not None:
+            layout, stride = LAYOUT_INPUT_RAGGED, 0
+        elif chars_pm_stride is not None:
+            layout, stride = LAYOUT_INPUT_POSITION_MAJOR, int(chars_pm_stride)
+        else:
+            assert src.stride(1) == 1
+            layout, stride = LAYOUT_STRING_MAJOR, src.stride(0)
+        assert ro.numel() == B + 1 and bo.numel() == runs.numel() + 1 and tot.numel() == 4 and spans.is_contiguous()
+        o = _ExtractOutC(ro.data_ptr(), runs.data_ptr(), bo.data_ptr(), vals.data_ptr(), tot.data_ptr(), runs.numel(), vals.numel())
+        s = torch.cuda.current_stream(status.device) if stream is None else stream
+        _check(lib.hrx_extract_spans_device(self._need_device(src, offsets, status, counts, spans, ro, runs, bo, vals, tot, ws), layout, src.data_ptr(), stride,
+                                            offsets.data_ptr() if offsets is not None else None, B, status.data_ptr(), counts.data_ptr(), spans.data_ptr(), max_spans,
+                                            int(require_accept), C.byref(o), ws.data_ptr(), ws.numel() * 8, s.cuda_stream))
+        return Extracted(status, counts, ro, runs, bo, vals, tot)
+
+    def extract_batch(self, chars, lens, max_spans=16, chars_pm_stride=None, require_accept=0, caps=None, stream=None, out=None):
+        """match_batch + extract_spans on one stream: a device-resident batch -> Extracted(status, counts, run_offsets, runs, byte_offsets, values, totals),
+        CUDA tensors holding the words of include/hrx.h EXTRACT.  caps = (runs_cap, values_cap), default the always-sufficient B * max_spans and the input's
+        byte count; out: the nine tensors of alloc_extract (its sizes are the caps then).  Nothing but the revealed bytes has to leave the device:
+        totals says how much of runs / byte_offsets / values is filled."""
+        B = lens.numel()
+        if out is None:
+            caps = caps or (B * max_spans, chars.numel())
+            out = self.alloc_extract(B, max_spans, caps[1], caps[0], chars.device)
+        st, cnt, sp = self.match_batch(chars, lens, max_spans=max_spans, stream=stream, chars_pm_stride=chars_pm_stride, out=out[:3])
+        return self.extract_spans(chars, st, cnt, sp, out[3:], chars_pm_stride=chars_pm_stride, require_accept=require_accept, stream=stream)
+
+    def extract_batch_ragged(self, values, offsets, max_spans=16, require_accept=0, caps=None, stream=None, out=None):
+        """extract_batch for a device-resident ragged batch (match_batch_ragged + extract_spans): a column in, a column out."""
+        B = offsets.numel() - 1
+        if out is None:
+            caps = caps or (B * max_spans, values.numel())
+            out = self.alloc_extract(B, max_spans, caps[1], caps[0], values.device)
+        st, cnt, sp = self.match_batch_ragged(values, offsets, max_spans=max_spans, stream=stream, out=out[:3])
+        return self.extract_spans(values, st, cnt, sp, out[3:], offsets=offsets, require_accept=require_accept, stream=stream)
+
+    def extract_batch_host(self, chars2d, lens, max_spans=16, require_accept=0, caps=None, out=None):
+        """Host arrays in, host arrays out, on either kind of context: match_batch_host, then hrx_extract_spans_host on the bytes where they are."""
+        chars2d = _np(chars2d, np.uint8)
+        st, cnt, sp = self.match_batch_host(chars2d, lens, max_spans=max_spans)
+        return extract_spans_host(chars2d, st, cnt, sp, require_accept=require_accept, caps=caps, out=out)
+
+    def extract_batch_host_ragged(self, values, offsets, max_spans=16, require_accept=0, caps=None, out=None):
+        values, offsets = _np(values, np.uint8), _np(offsets, np.uint64)
+        st, cnt, sp = self.match_batch_host_ragged(values, offsets, max_spans=max_spans)
+        return extract_spans_host(values, st, cnt, sp, offsets=offsets, require_accept=require_accept, caps=caps, out=out)
+
+    def extract_strings(self, strings, max_spans=16, require_accept=0):
+        """A list of bytes on the host -> Extracted (extract_batch_host_ragged of pack_strings(strings)); extracted_lists gives it per string."""
+        return self.extract_batch_host_ragged(*pack_strings(strings), max_spans=max_spans, require_accept=require_accept)
+
     def describe_match(self, B, layout=0, num_cus=256):
         """hrx_ctx_describe_match (or hrx_describe_match without a context): the kernel(s) match_batch runs for B strings, as text."""
         buf = C.create_string_buffer(4096)
@@ -1227,6 +1303,76 @@ def revealed_substrings_ragged(values, offsets, status, counts, spans):
         o = int(offsets[b])
         res.append([(sid, start, bytes(values[o + start:o + start + length])) for sid, start, length in runs])
     return res
+
+
+#: what the extract calls return (include/hrx.h EXTRACT): the match call's status / counts and the list column — torch tensors (int64 / int32 / uint8 holding the
+#: u64 / u32 / u8 words) from the device forms, numpy arrays from the host forms
+Extracted = collections.namedtuple("Extracted", "status counts run_offsets runs byte_offsets values totals")
+
+
+def extract_workspace_bytes(B):
+    return lib.hrx_extract_workspace_bytes(int(B))
+
+
+def extract_spans_host(src, status, counts, spans, offsets=None, require_accept=0, caps=None, out=None, threads=0):
+    """hrx_extract_spans_host (no context): src = chars (B, stride) uint8, or ragged values with offsets (B + 1) uint64; status / counts / spans: the outputs of
+    a match call on it.  caps = (runs_cap, values_cap), default B * max_spans and the input's byte count; out = (run_offsets, runs, byte_offsets, values,
+    totals): the caller's arrays (their sizes are the caps then).  -> Extracted of numpy arrays."""
+    src = _np(src, np.uint8)
+    status, counts, spans = _np(status, np.uint64), _np(counts, np.uint32), _np(spans, np.uint64)
+    B, max_spans = len(status), spans.shape[1]
+    if offsets is not None:
+        offsets = _np(offsets, np.uint64)
+        layout, stride = LAYOUT_INPUT_RAGGED, 0
+    else:
+        layout, stride = LAYOUT_STRING_MAJOR, src.shape[1]
+    if out is None:
+        runs_cap, values_cap = caps or (B * max_spans, src.size)
+        out = (np.zeros(B + 1, np.uint64), np.zeros(runs_cap, np.uint64), np.zeros(runs_cap + 1, np.uint64), np.zeros(values_cap, np.uint8), np.zeros(4, np.uint64))
+    ro, runs, bo, vals, tot = out
+    assert len(ro) == B + 1 and len(bo) == len(runs) + 1 and len(tot) == 4
+    o = _ExtractOutC(ro.ctypes.data, runs.ctypes.data, bo.ctypes.data, vals.ctypes.data, tot.ctypes.data, len(runs), len(vals))
+    _check(lib.hrx_extract_spans_host(layout, src.ctypes.data, stride, offsets.ctypes.data if offsets is not None else None, B, status.ctypes.data,
+                                      counts.ctypes.data, spans.ctypes.data, max_spans, int(require_accept), C.byref(o), int(threads)))
+    return Extracted(status, counts, ro, runs, bo, vals, tot)
+
+
+def _extracted_host(ex):
+    """the arrays of an Extracted on the host as unsigned numpy; raises where the caps were too small (totals says what is needed)"""
+    a = [x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x) for x in ex]
+    st, cnt, ro, runs, bo, vals, tot = [x.view(dt) if x.dtype != dt else x for x, dt in zip(a, (np.uint64, np.uint32, np.uint64, np.uint64, np.uint64, np.uint8, np.uint64))]
+    R, nbytes = int(tot[0]), int(tot[1])
+    if R > len(runs) or nbytes > len(vals):
+        raise ValueError("extract: %d runs / %d bytes needed, caps %d / %d" % (R, nbytes, len(runs), len(vals)))
+    return ro, runs[:R], bo[:R + 1], vals[:nbytes]
+
+
+def extracted_lists(ex):
+    """An Extracted -> per string a list of (substr_id, start, bytes): the shape revealed_substrings returns, so the two compare directly."""
+    ro, runs, bo, vals = _extracted_host(ex)
+    raw = vals.tobytes()
+    res = []
+    for b in range(len(ro) - 1):
+        row = []
+        for j in range(int(ro[b]), int(ro[b + 1])):
+            w = int(runs[j])
+            row.append((w >> 56, w & 0xFFFFFFF, raw[int(bo[j]):int(bo[j + 1])]))
+        res.append(row)
+    return res
+
+
+def extracted_column(ex, substr_id):
+    """An Extracted -> (values uint8, offsets uint64 (B + 1)): per string the concatenation of its runs with this masked_substr_id, back to back — the
+    large-binary column an indexer stores for one public part."""
+    ro, runs, bo, vals = _extracted_host(ex)
+    B = len(ro) - 1
+    keep = (runs >> np.uint64(56)) == np.uint64(substr_id)
+    lens = np.where(keep, bo[1:] - bo[:-1], np.uint64(0)).astype(np.uint64)
+    csum = np.concatenate((np.zeros(1, np.uint64), np.cumsum(lens, dtype=np.uint64)))
+    offsets = csum[ro.astype(np.int64)]                     # bytes of this id in front of each string's first run
+    pick = np.repeat(keep, (bo[1:] - bo[:-1]).astype(np.int64))
+    assert len(offsets) == B + 1
+    return vals[pick], offsets
 
 
 def decode_status(s):

@@ -143,6 +143,40 @@ class RegexVerifyConfig {
         return r;
     }
 
+    // EXTRACT (include/hrx.h): the revealed bytes of a list of strings as a list column, on the host: the ragged host match, then hrx_extract_spans_host
+    struct Extracted {
+        std::vector<uint64_t> status, run_offsets, runs, byte_offsets;
+        std::vector<uint8_t> values;
+    };
+    Extracted extract_strings(const std::vector<std::vector<uint8_t>> &strings, size_t max_spans = 16, uint32_t require_accept = 0) const {
+        const size_t B = strings.size();
+        std::vector<uint64_t> offsets(B + 1, 0);
+        std::vector<uint8_t> bytes;
+        for (size_t b = 0; b < B; ++b) {
+            bytes.insert(bytes.end(), strings[b].begin(), strings[b].end());
+            offsets[b + 1] = bytes.size();
+        }
+        bytes.resize(bytes.size() + 16);
+        Extracted e;
+        e.status.resize(B);
+        std::vector<uint32_t> counts(B + 2);
+        std::vector<uint64_t> spans(B * max_spans + 1), totals(4);
+        check(hrx_match_batch_host_ragged(ctx_, bytes.data(), offsets.data(), B, max_chars_size_, e.status.data(), counts.data(), spans.data(), max_spans));
+        e.run_offsets.resize(B + 1); e.runs.resize(B * max_spans); e.byte_offsets.resize(B * max_spans + 1); e.values.resize(bytes.size());
+        const hrx_extract_out out{e.run_offsets.data(), e.runs.data(), e.byte_offsets.data(), e.values.data(), totals.data(), e.runs.size(), e.values.size()};
+        check(hrx_extract_spans_host(HRX_LAYOUT_INPUT_RAGGED, bytes.data(), 0, offsets.data(), B, e.status.data(), counts.data(), spans.data(), max_spans,
+                                     require_accept, &out, 0));
+        e.runs.resize(totals[0]); e.byte_offsets.resize(totals[0] + 1); e.values.resize(totals[1]);
+        return e;
+    }
+    // ... and the device form as it is (device pointers; `workspace` of hrx_extract_workspace_bytes(B) bytes; asynchronous on `stream`)
+    static size_t extract_workspace_bytes(size_t B) { return hrx_extract_workspace_bytes(B); }
+    void extract_spans_device(int layout, const uint8_t *src, size_t stride, const uint64_t *offsets, size_t B, const uint64_t *status, const uint32_t *span_counts,
+                              const uint64_t *spans, size_t max_spans, uint32_t require_accept, const hrx_extract_out &out, void *workspace, size_t workspace_bytes,
+                              void *stream) const {
+        check(hrx_extract_spans_device(ctx_, layout, src, stride, offsets, B, status, span_counts, spans, max_spans, require_accept, &out, workspace, workspace_bytes, stream));
+    }
+
    private:
     static std::vector<std::vector<uint64_t>> split(const std::vector<uint64_t> &f, size_t D, size_t len) {
         std::vector<std::vector<uint64_t>> o(D);

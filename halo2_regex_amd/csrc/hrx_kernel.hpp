@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "hrx_defs.hpp"
+#include "hrx_extract.hpp"
 
 namespace hrx {
 
@@ -335,6 +336,22 @@ hipError_t launch_ragged_slice(const uint8_t *values, const uint64_t *offsets, u
 // the batch -> HRX_LAYOUT_INPUT_POSITION_MAJOR [stride/16][nb][16] per block, zero-padded, lens [B] (UINT32_MAX: as above, limit = stride)
 hipError_t launch_ragged_to_position_major(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t stride, uint8_t *chars_pm,
                                            uint32_t *lens, hipStream_t stream);
+
+// EXTRACT (include/hrx.h hrx_extract_spans_device; hrx_kernel_extract.hip): the runs of a match call -> run_offsets / runs / byte_offsets / values / totals.
+// Count, scan, apply, gather: four launches, nothing but the caller's workspace in between (extract_workspace_bytes: 3 words per kExtractThreads strings + 4)
+constexpr uint32_t kExtractThreads = 256;       // strings per workgroup of the count and apply launches; the scan launch takes this many partials per round
+struct ExtractArgs {
+    ExtractIn in;                   // hrx_extract.hpp: layout, input, the match call's outputs, max_spans, require_accept
+    uint64_t *run_offsets;          // [B + 1]
+    uint64_t *runs;                 // [runs_cap]
+    uint64_t *byte_offsets;         // [runs_cap + 1]
+    uint8_t *values;                // [values_cap]
+    uint64_t *totals;               // [4]
+    uint64_t runs_cap, values_cap;
+    uint64_t *ws;                   // the caller's workspace
+};
+size_t extract_workspace_bytes(size_t B);
+hipError_t launch_extract(const ExtractArgs &a, hipStream_t stream);
 
 // position-major -> string-major (hrx_kernel_tp.hip): string-major callers served by the position-major path
 struct TransposeArgs {

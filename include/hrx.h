@@ -448,6 +448,48 @@ int hrx_ragged_to_position_major_device(hrx_ctx *ctx, const uint8_t *values, con
                                         size_t stride, uint8_t *chars_pm, uint32_t *lens, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* EXTRACT: the revealed bytes of a matched batch as an Arrow list<large_binary> column */
+/* ------------------------------------------------------------------ */
+/*
+ * A match call reports WHERE a string reveals something (row numbers); this turns its outputs into WHAT is revealed, without the input leaving
+ * the memory it is in.  For B strings with R revealed runs in total:
+ *   run_offsets   [B + 1] u64         string b's runs are run indices [run_offsets[b], run_offsets[b + 1]); run_offsets[B] = R
+ *   runs          [runs_cap] u64      run j's span word as the match call packed it (start row, length, masked_substr_id), in string order, then start order
+ *   byte_offsets  [runs_cap + 1] u64  run j's bytes are values[byte_offsets[j] .. byte_offsets[j + 1])
+ *   values        [values_cap] u8     the revealed bytes back to back, no padding
+ *   totals        [4] u64             [0] R needed, [1] bytes needed, [2] contributing strings whose span_counts[b] > max_spans (the match call
+ *                                     truncated them), [3] 0
+ * String b contributes k_b = min(span_counts[b], max_spans) runs where its status code is 0 and ((status[b] >> 8) & require_accept) == require_accept,
+ * else none: require_accept = 0 takes every string with status code 0, the mask of all defs only strings the circuit would accept.
+ * CAPACITY: run_offsets and totals are always complete.  Run j is stored (runs[j], byte_offsets[j], byte_offsets[j + 1], its bytes) iff j < runs_cap and
+ * byte_offsets[j + 1] <= values_cap; both conditions are monotone, so the stored runs are a prefix [0, J), byte_offsets[0 .. J] is written (byte_offsets[0] = 0)
+ * and nothing at or beyond runs[runs_cap], byte_offsets[runs_cap + 1] or values[values_cap].  The caller compares totals with its caps; caps that always
+ * suffice: runs_cap = B * max_spans, values_cap = the input's byte count (B * stride, or offsets[B] - offsets[0]).
+ * DEFENSIVE: the span words are caller memory.  A run whose range leaves its string — [0, stride) of a padded slot, [0, n_b) of a ragged string — is clipped to
+ * it (byte_offsets shows the clipped length; runs[j] stays the word as given); a ragged string with decreasing offsets contributes nothing.  No byte is read
+ * that a match call on the same input may not read.
+ *   layout        HRX_LAYOUT_STRING_MAJOR (src [B][stride]), HRX_LAYOUT_INPUT_POSITION_MAJOR (blocked by HRX_PM_BLOCK, stride % 16 == 0; device form only) or
+ *                 HRX_LAYOUT_INPUT_RAGGED (src = values, offsets [B + 1], stride ignored); otherwise offsets is ignored
+ *   status, span_counts, spans   the outputs of a match call on the same input with the same max_spans, 1 <= max_spans <= 2^16
+ * All u64 arrays 8-byte aligned, span_counts 4-byte; stride <= 2^28.
+ * Device form: device pointers, asynchronous on `stream`: four kernel launches and nothing else — no allocation, no context scratch, no synchronisation — so it is
+ * legal inside a stream capture whatever def set the context holds, and deterministic.  Its temporaries live in `workspace` (8-byte aligned device memory of
+ * at least hrx_extract_workspace_bytes(B) bytes; too small: HRX_ERR_ARG).  HRX_ERR_HIP on a host-only context.
+ * Host form: host pointers, no context, re-entrant; threads <= 0: as many as the host has.  It serves host-only and device contexts alike, since the input
+ * bytes are in host memory already: the host route is a host match call followed by this, and no values travel back over the link. */
+typedef struct hrx_extract_out {
+    uint64_t *run_offsets; uint64_t *runs; uint64_t *byte_offsets; uint8_t *values;
+    uint64_t *totals; size_t runs_cap; size_t values_cap;
+} hrx_extract_out;
+size_t hrx_extract_workspace_bytes(size_t B);
+int hrx_extract_spans_device(hrx_ctx *ctx, int layout, const uint8_t *src, size_t stride, const uint64_t *offsets, size_t B,
+                             const uint64_t *status, const uint32_t *span_counts, const uint64_t *spans, size_t max_spans,
+                             uint32_t require_accept, const hrx_extract_out *out, void *workspace, size_t workspace_bytes, void *stream);
+int hrx_extract_spans_host(int layout, const uint8_t *src, size_t stride, const uint64_t *offsets, size_t B,
+                           const uint64_t *status, const uint32_t *span_counts, const uint64_t *spans, size_t max_spans,
+                           uint32_t require_accept, const hrx_extract_out *out, int threads);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f4 — compact witness -> field cells (the step after the path)        */
 /* ------------------------------------------------------------------ */
 /* Expands the compact rows of strings [b_begin, b_begin + b_count) of a finished batch into what
