@@ -1088,15 +1088,20 @@ class RegexVerifyConfig:
         return rec, msk, st
 
     def fr_columns(self, chars, lens, out, b_begin=0, b_count=None, position_major=False, chars_pm_stride=None, canonical=False,
-                   stream=None):
+                   stream=None, cells=None):
         """expand the compact rows `out` = (records, masked, status) of a finished witness_batch* call into
-        bn256::Fr cells for strings [b_begin, b_begin + b_count): int64 CUDA tensor [4 + 4 D][b_count][M][4] (limbs)."""
+        bn256::Fr cells for strings [b_begin, b_begin + b_count): int64 CUDA tensor [4 + 4 D][b_count][M][4] (limbs).
+        cells: the caller's contiguous int64 tensor of exactly that many elements, written in place and returned.  Type, contiguity and size are checked
+        here; that it lies on this config's device is _need_device's check, and that it is 16-byte aligned the library's own (HrxError from either)."""
         rec, msk, _ = out
         B = lens.numel()
         b_count = B - b_begin if b_count is None else b_count
         M, D = self.max_chars_size, self.num_defs
         ncols = lib.hrx_fr_num_columns(D)
-        cells = torch.empty((ncols, b_count, M, 4), dtype=torch.int64, device=lens.device)
+        if cells is None:
+            cells = torch.empty((ncols, b_count, M, 4), dtype=torch.int64, device=lens.device)
+        elif cells.dtype != torch.int64 or not cells.is_contiguous() or cells.numel() != ncols * b_count * M * 4:
+            raise HrxError(HRX_ERR_ARG, "cells: a contiguous int64 tensor of [%d][%d][%d][4] elements" % (ncols, b_count, M))
         layout, rp, mp = LAYOUT_STRING_MAJOR, 0, 0
         if position_major:
             layout = LAYOUT_POSITION_MAJOR
@@ -1105,6 +1110,8 @@ class RegexVerifyConfig:
                 stride = int(chars_pm_stride)
             else:
                 stride = chars.stride(0)
+        elif isinstance(rec, (list, tuple)):      # (record planes are a position-major layout: the library refuses)
+            stride = chars.stride(0)
         else:
             stride, rp, mp = chars.stride(0), rec.stride(0) // D, msk.stride(0)
         s = torch.cuda.current_stream(lens.device) if stream is None else stream
