@@ -66,6 +66,17 @@ extern "C" {
     pub fn hrx_extract_spans_host(layout: c_int, src: *const u8, stride: usize, offsets: *const u64, b: usize,
                                   status: *const u64, span_counts: *const u32, spans: *const u64, max_spans: usize, require_accept: u32,
                                   out: *const hrx_extract_out, threads: c_int) -> c_int;
+    // ROUTE: a screened batch -> a stable partition by circuit-size bucket (bounds: a HOST array of at most HRX_MAX_BUCKETS = 8 sizes; exactly one of lens
+    // and offsets is non-null), then the strings of a bucket (sel = order + bucket_offsets[j]) as position-major witness input (include/hrx.h)
+    pub fn hrx_route_workspace_bytes(b: usize) -> usize;
+    pub fn hrx_route_device(ctx: *mut hrx_ctx, status: *const u64, require_accept: u32, lens: *const u32, offsets: *const u64, b: usize,
+                            bounds: *const u32, n_buckets: usize, order: *mut u32, bucket_offsets: *mut u64,
+                            workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_route_host(status: *const u64, require_accept: u32, lens: *const u32, offsets: *const u64, b: usize,
+                          bounds: *const u32, n_buckets: usize, order: *mut u32, bucket_offsets: *mut u64) -> c_int;
+    pub fn hrx_gather_to_position_major_device(ctx: *mut hrx_ctx, layout: c_int, src: *const u8, src_stride: usize, lens: *const u32,
+                                               offsets: *const u64, b: usize, sel: *const u32, n_sel: usize, stride: usize,
+                                               chars_pm: *mut u8, lens_out: *mut u32, stream: *mut c_void) -> c_int;
     pub fn hrx_witness_batch_device(ctx: *mut hrx_ctx, chars: *const u8, stride: usize, lens: *const u32, b: usize,
                                     m: usize, records: *mut u32, masked: *mut u16, status: *mut u64,
                                     stream: *mut c_void) -> c_int;

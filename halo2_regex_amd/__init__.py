@@ -7,6 +7,7 @@ parity tests read like the reference's own tests.  There is no CPU implementatio
 path: without the HIP library the import fails, and without a gfx950 device RegexVerifyConfig raises.
 """
 import collections
+import contextlib
 import ctypes as C
 import os
 
@@ -150,6 +151,10 @@ def _load():
         "hrx_extract_workspace_bytes": (sz, [sz]),
         "hrx_extract_spans_device": (i, [vp, i, vp, sz, vp, sz, vp, vp, vp, sz, C.c_uint32, C.POINTER(_ExtractOutC), vp, sz, vp]),
         "hrx_extract_spans_host": (i, [i, vp, sz, vp, sz, vp, vp, vp, sz, C.c_uint32, C.POINTER(_ExtractOutC), i]),
+        "hrx_route_workspace_bytes": (sz, [sz]),
+        "hrx_route_device": (i, [vp, vp, C.c_uint32, vp, vp, sz, _u32p, sz, vp, vp, vp, sz, vp]),
+        "hrx_route_host": (i, [vp, C.c_uint32, vp, vp, sz, _u32p, sz, vp, vp]),
+        "hrx_gather_to_position_major_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, vp, vp, vp]),
         "hrx_shard_range": (None, [sz, i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hrx_derive_states": (i, [vp, _u8p, sz, _u64p]),
         "hrx_derive_substr_ids": (i, [vp, _u64p, sz, _u64p]),
@@ -899,6 +904,68 @@ class RegexVerifyConfig:
         """A list of bytes on the host -> Extracted (extract_batch_host_ragged of pack_strings(strings)); extracted_lists gives it per string."""
         return self.extract_batch_host_ragged(*pack_strings(strings), max_spans=max_spans, require_accept=require_accept)
 
+    # -- route: the screened batch by circuit-size bucket, each bucket staged for the witness (include/hrx.h ROUTE) --------------
+    def route(self, status, lens=None, offsets=None, bounds=None, require_accept=0, stream=None, out=None):
+        """hrx_route_device: status (B,) int64 of a match call (or None: no screening) and the strings' lengths — lens (B,) int32 or ragged offsets
+        (B + 1,) int64, exactly one of them — -> Routed(order (B,) int32, bucket_offsets (n_buckets + 2,) int64): bucket j (strings that pass the screen
+        with n <= bounds[j], and > bounds[j - 1]) is order[bucket_offsets[j]:bucket_offsets[j + 1]], range n_buckets the strings that were not kept, every
+        range in increasing b.  bounds: a host list of at most MAX_BUCKETS circuit sizes, default [max_chars_size].  Asynchronous on `stream`; three
+        launches, nothing allocated when out=(order, bucket_offsets, workspace int64 of route_workspace_bytes(B) // 8 words) is given."""
+        bounds = _np([self.max_chars_size] if bounds is None else bounds, np.uint32)
+        src = lens if lens is not None else offsets
+        if src is None or (lens is not None and offsets is not None):
+            raise HrxError(HRX_ERR_ARG, "route: exactly one of lens and offsets")
+        B = lens.numel() if lens is not None else offsets.numel() - 1
+        assert src.is_cuda and src.is_contiguous() and src.dtype == (torch.int32 if lens is not None else torch.int64)
+        assert status is None or (status.dtype == torch.int64 and status.is_contiguous() and status.numel() == B)
+        if out is None:
+            out = (torch.empty(B, dtype=torch.int32, device=src.device), torch.empty(len(bounds) + 2, dtype=torch.int64, device=src.device),
+                   torch.empty(route_workspace_bytes(B) // 8, dtype=torch.int64, device=src.device))
+        order, bo, ws = out
+        assert order.numel() == B and bo.numel() == len(bounds) + 2 and order.dtype == torch.int32 and bo.dtype == torch.int64
+        s = torch.cuda.current_stream(src.device) if stream is None else stream
+        # (an empty tensor has no address, and the C rule names the form by its non-NULL pointer: nothing is read at B = 0, any device address does)
+        at = lambda t: None if t is None else (t.data_ptr() or bo.data_ptr())
+        _check(lib.hrx_route_device(self._need_device(status, src, order, bo, ws), status.data_ptr() if status is not None else None, int(require_accept),
+                                    at(lens), at(offsets), B,
+                                    _ptr(bounds, _u32p), len(bounds), order.data_ptr(), bo.data_ptr(), ws.data_ptr(), ws.numel() * 8, s.cuda_stream))
+        return Routed(order, bo)
+
+    def gather_to_position_major(self, src, sel, stride, lens=None, offsets=None, out=None, stream=None):
+        """hrx_gather_to_position_major_device: the strings sel (int32 CUDA tensor of string indices, e.g. order[bucket_offsets[j]:bucket_offsets[j + 1]])
+        of a string-major batch (src (B, src_stride) uint8 with lens (B,) int32) or a ragged one (src = values with offsets (B + 1,) int64) ->
+        (chars_pm, lens_out): the flat HRX_LAYOUT_INPUT_POSITION_MAJOR buffer of len(sel) slots of `stride` bytes and lens_out int32 (-1 = UINT32_MAX: an
+        index past the batch, or a string that does not fit), the input of witness_batch_position_major / match_batch with chars_pm_stride=stride."""
+        assert src.is_cuda and sel.is_cuda and src.dtype == torch.uint8 and sel.dtype == torch.int32 and sel.is_contiguous() and sel.dim() == 1
+        if (lens is None) == (offsets is None):
+            raise HrxError(HRX_ERR_ARG, "gather_to_position_major: exactly one of lens and offsets")
+        if offsets is not None:
+            assert offsets.dtype == torch.int64 and offsets.is_contiguous() and src.is_contiguous()
+            layout, B, src_stride = LAYOUT_INPUT_RAGGED, offsets.numel() - 1, 0
+        else:
+            assert lens.dtype == torch.int32 and lens.is_contiguous() and src.dim() == 2 and src.stride(1) == 1
+            layout, B, src_stride = LAYOUT_STRING_MAJOR, lens.numel(), src.stride(0)
+        n_sel, stride = sel.numel(), int(stride)
+        if out is None:
+            out = (torch.empty((n_sel * stride,), dtype=torch.uint8, device=src.device), torch.empty(n_sel, dtype=torch.int32, device=src.device))
+        chars_pm, lens_out = out
+        assert chars_pm.numel() == n_sel * stride and lens_out.numel() == n_sel
+        s = torch.cuda.current_stream(src.device) if stream is None else stream
+        _check(lib.hrx_gather_to_position_major_device(self._need_device(src, sel, lens, offsets, chars_pm, lens_out), layout, src.data_ptr(), src_stride,
+                                                       lens.data_ptr() if lens is not None else None, offsets.data_ptr() if offsets is not None else None,
+                                                       B, sel.data_ptr(), n_sel, stride, chars_pm.data_ptr(), lens_out.data_ptr(), s.cuda_stream))
+        return chars_pm, lens_out
+
+    @contextlib.contextmanager
+    def circuit_size(self, M):
+        """`with cfg.circuit_size(M):` — this config's calls at another max_chars_size.  M is a per-call argument of every entry point of include/hrx.h, so
+        one context serves every circuit size a router sorts strings into."""
+        old, self.max_chars_size = self.max_chars_size, int(M)
+        try:
+            yield self
+        finally:
+            self.max_chars_size = old
+
     def describe_match(self, B, layout=0, num_cus=256):
         """hrx_ctx_describe_match (or hrx_describe_match without a context): the kernel(s) match_batch runs for B strings, as text."""
         buf = C.create_string_buffer(4096)
@@ -1342,6 +1409,39 @@ def extract_spans_host(src, status, counts, spans, offsets=None, require_accept=
     _check(lib.hrx_extract_spans_host(layout, src.ctypes.data, stride, offsets.ctypes.data if offsets is not None else None, B, status.ctypes.data,
                                       counts.ctypes.data, spans.ctypes.data, max_spans, int(require_accept), C.byref(o), int(threads)))
     return Extracted(status, counts, ro, runs, bo, vals, tot)
+
+
+#: what route / route_host return (include/hrx.h ROUTE): bucket j is order[bucket_offsets[j]:bucket_offsets[j + 1]], range n_buckets the strings not kept
+Routed = collections.namedtuple("Routed", "order bucket_offsets")
+MAX_BUCKETS = 8                      # HRX_MAX_BUCKETS
+
+
+def route_workspace_bytes(B):
+    return lib.hrx_route_workspace_bytes(int(B))
+
+
+def route_host(status, lens=None, offsets=None, bounds=None, require_accept=0, out=None):
+    """hrx_route_host (no context): status (B,) uint64 of a match call or None, lens (B,) uint32 or ragged offsets (B + 1,) uint64 (exactly one), bounds: the
+    circuit sizes (required here: there is no config to take a default from); out = (order uint32 (B,), bucket_offsets uint64 (n_buckets + 2,)): the
+    caller's arrays.  -> Routed of numpy arrays."""
+    bounds = _np([] if bounds is None else bounds, np.uint32)
+    status = None if status is None else _np(status, np.uint64)
+    lens = None if lens is None else _np(lens, np.uint32)
+    offsets = None if offsets is None else _np(offsets, np.uint64)
+    if lens is not None:
+        B = len(lens)
+    elif offsets is not None:
+        B = len(offsets) - 1
+    else:
+        B = 0 if status is None else len(status)
+    assert B >= 0 and (status is None or len(status) == B)
+    if out is None:
+        out = np.zeros(B, np.uint32), np.zeros(len(bounds) + 2, np.uint64)
+    order, bo = out
+    assert len(order) == B and len(bo) == len(bounds) + 2 and order.dtype == np.uint32 and bo.dtype == np.uint64
+    _check(lib.hrx_route_host(status.ctypes.data if status is not None else None, int(require_accept), lens.ctypes.data if lens is not None else None,
+                              offsets.ctypes.data if offsets is not None else None, B, _ptr(bounds, _u32p), len(bounds), order.ctypes.data, bo.ctypes.data))
+    return Routed(order, bo)
 
 
 def _extracted_host(ex):

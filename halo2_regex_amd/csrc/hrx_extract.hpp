@@ -5,11 +5,7 @@
 #include <stddef.h>
 #include <stdint.h>
 
-#if defined(__HIP__)  // clang in HIP mode (hipcc), host and device passes alike
-#define HRX_XHD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
-#else
-#define HRX_XHD inline
-#endif
+#include "hrx_route.hpp"      // HRX_XHD, passes_screen: the screen ROUTE shares
 
 namespace hrx {
 
@@ -61,8 +57,7 @@ HRX_XHD bool string_limit(const ExtractIn &in, uint64_t b, uint64_t &limit) {
 HRX_XHD uint64_t contributed_runs(const ExtractIn &in, uint64_t b, uint64_t &limit, bool &truncated) {
     truncated = false;
     if (!string_limit(in, b, limit)) return 0;
-    const uint64_t st = in.status[b];
-    if ((st & 0xffu) != 0 || ((uint32_t)(st >> 8) & in.require_accept) != in.require_accept) return 0;
+    if (!passes_screen(in.status[b], in.require_accept)) return 0;
     const uint64_t c = in.span_counts[b];
     truncated = c > in.max_spans;
     return truncated ? in.max_spans : c;

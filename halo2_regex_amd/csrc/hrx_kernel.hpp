@@ -7,6 +7,7 @@
 
 #include "hrx_defs.hpp"
 #include "hrx_extract.hpp"
+#include "hrx_route.hpp"
 
 namespace hrx {
 
@@ -352,6 +353,23 @@ struct ExtractArgs {
 };
 size_t extract_workspace_bytes(size_t B);
 hipError_t launch_extract(const ExtractArgs &a, hipStream_t stream);
+
+// ROUTE (include/hrx.h hrx_route_device; hrx_kernel_route.hip): a stable partition of the batch by (kept?, length bucket) -> order / bucket_offsets.
+// Count, scan, apply: three launches of kExtractThreads lanes, nothing but the caller's workspace in between
+// (route_workspace_bytes: kRouteBins words per kExtractThreads strings + kRouteBins)
+struct RouteArgs {
+    RouteIn in;                     // hrx_route.hpp: status, require_accept, lens or offsets, B, the bounds by value
+    uint32_t *order;                // [B]
+    uint64_t *bucket_offsets;       // [bounds.n + 2]
+    uint64_t *ws;                   // the caller's workspace
+};
+size_t route_workspace_bytes(size_t B);
+hipError_t launch_route(const RouteArgs &a, hipStream_t stream);
+// GATHERED STAGING (include/hrx.h hrx_gather_to_position_major_device; hrx_kernel_ragged.hip): slot k of the position-major output = source string sel[k]
+// of a ragged (offsets) or string-major (lens, src_stride) batch of B strings; lens_out[k] = UINT32_MAX and a zero slot where sel[k] >= B or the
+// string does not fit (launch_ragged_to_position_major is the same kernel without sel)
+hipError_t launch_gather_to_position_major(const uint8_t *src, size_t src_stride, const uint32_t *lens, const uint64_t *offsets, size_t B,
+                                           const uint32_t *sel, size_t n_sel, size_t stride, uint8_t *chars_pm, uint32_t *lens_out, hipStream_t stream);
 
 // position-major -> string-major (hrx_kernel_tp.hip): string-major callers served by the position-major path
 struct TransposeArgs {

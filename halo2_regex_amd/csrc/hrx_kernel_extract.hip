@@ -16,37 +16,14 @@
 
 #include <algorithm>
 
+#include "hrx_block_scan.h"
 #include "hrx_kernel.hpp"
 
 namespace hrx {
 
-constexpr uint32_t kXT = kExtractThreads;        // lanes (strings) per workgroup of count / apply, partials per round of scan
+constexpr uint32_t kXT = kScanThreads;           // lanes (strings) per workgroup of count / apply, partials per round of scan (block_scan: hrx_block_scan.h)
 constexpr uint32_t kGatherStrings = 64;          // strings per gather workgroup
 constexpr uint32_t kGatherRuns = 256;            // runs in LDS at a time
-
-// v[n] -> the exclusive prefix over the workgroup's lanes, total[n] the workgroup's sum (sh: N x kXT words of LDS)
-template <int N>
-__device__ __forceinline__ void block_scan(uint64_t (&v)[N], uint64_t (&total)[N], uint64_t (*sh)[kXT]) {
-    const uint32_t tid = threadIdx.x;
-#pragma unroll
-    for (int n = 0; n < N; ++n) sh[n][tid] = v[n];
-    __syncthreads();
-    for (uint32_t off = 1; off < kXT; off <<= 1) {
-        uint64_t t[N];
-#pragma unroll
-        for (int n = 0; n < N; ++n) t[n] = tid >= off ? sh[n][tid - off] : 0;
-        __syncthreads();
-#pragma unroll
-        for (int n = 0; n < N; ++n) sh[n][tid] += t[n];
-        __syncthreads();
-    }
-#pragma unroll
-    for (int n = 0; n < N; ++n) {
-        total[n] = sh[n][kXT - 1];
-        v[n] = sh[n][tid] - v[n];
-    }
-    __syncthreads();
-}
 
 // string b's runs, clipped bytes and whether it was truncated
 __device__ __forceinline__ void string_sums(const ExtractIn &in, uint64_t b, uint64_t &k, uint64_t &bytes, uint64_t &trunc, uint64_t &limit) {

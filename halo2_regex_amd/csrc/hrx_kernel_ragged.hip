@@ -6,7 +6,8 @@
 //                                 that ends a short string starts its next at once.  A string stops after the tile that holds row min(n, M - 1)
 //                                 (the padded kernel's later tiles change nothing).  No atomics, no counters, no scratch.
 //   ragged_slice_kernel           "via rows": strings [b0, b0 + n) -> string-major [n][stride] zero-padded + lens, the input of the witness launch.
-//   ragged_to_pm_kernel           hrx_ragged_to_position_major_device: the batch -> HRX_LAYOUT_INPUT_POSITION_MAJOR + lens, one thread per output chunk.
+//   ragged_to_pm_kernel<Src, SEL> hrx_ragged_to_position_major_device (<RaggedSrc, false>): the batch -> HRX_LAYOUT_INPUT_POSITION_MAJOR + lens, one thread
+//                                 per output chunk; hrx_gather_to_position_major_device (SEL): slot k = string sel[k] of a ragged or string-major batch.
 // A string whose offsets decrease or whose length passes the limit (M; the stride for the staging kernels) has none of its bytes read.
 #include "hrx_device.h"
 #include "hrx_walk_pm.h"
@@ -134,16 +135,47 @@ __global__ __launch_bounds__(256) void ragged_slice_kernel(const uint8_t *values
     if (c == 0) lens[s] = ok ? len : 0xffffffffu;
 }
 
-// a workgroup: 64 strings x 8 output chunks (wave w writes chunks c0 + w and c0 + 4 + w of its 64 strings: 1 KiB contiguous per store, as
-// chars_sm_to_pm_kernel); the four waves read the same 128 bytes of each string, so the strided reads share cache lines
-__global__ __launch_bounds__(256) void ragged_to_pm_kernel(const uint8_t *values, const uint64_t *offsets, uint64_t base, uint32_t B, uint32_t units,
-                                                           uint8_t *chars_pm, uint32_t *lens) {
+// where a string of the staging kernel lies: string(b, limit, p, n) -> its first byte and length; false where it has no valid length or the length
+// passes `limit` (none of its bytes is read then)
+struct RaggedSrc {          // values + offsets
+    const uint8_t *values;
+    const uint64_t *offsets;
+    uint64_t base;
+    __device__ __forceinline__ bool string(size_t b, uint64_t limit, const uint8_t *&p, uint32_t &n) const {
+        return ragged_string(values, offsets, base, b, limit, p, n);
+    }
+};
+struct PaddedSrc {          // chars + b * src_stride with lens[b]: 16-byte aligned slots, the sh = 0 case of ragged_chunk (bytes past n are never kept)
+    const uint8_t *chars;
+    const uint32_t *lens;
+    uint64_t src_stride;
+    __device__ __forceinline__ bool string(size_t b, uint64_t limit, const uint8_t *&p, uint32_t &n) const {
+        const uint32_t len = lens[b];
+        if (len > limit || len > src_stride) return false;
+        p = chars + b * src_stride;
+        n = len;
+        return true;
+    }
+};
+
+// a workgroup: 64 output slots x 8 output chunks (wave w writes chunks c0 + w and c0 + 4 + w of its 64 strings: 1 KiB contiguous per store, as
+// chars_sm_to_pm_kernel); the four waves read the same 128 bytes of each string, so the strided reads share cache lines.
+// SEL: slot b holds source string sel[b] of the B_src the source has (an index at or past B_src: a zero slot, nothing read); else string b itself
+template <class Src, bool SEL>
+__global__ __launch_bounds__(256) void ragged_to_pm_kernel(const Src src, const uint32_t *sel, uint32_t B_src, uint32_t B, uint32_t units, uint8_t *chars_pm,
+                                                    uint32_t *lens) {
     const uint32_t b = blockIdx.x * 64u + (threadIdx.x & 63u);
     if (b >= B) return;
     const uint32_t blk0 = b / kPmBlock * kPmBlock, nb = min(kPmBlock, B - blk0);
     const uint8_t *p;
     uint32_t len;
-    const bool ok = ragged_string(values, offsets, base, b, (uint64_t)units * 16u, p, len);
+    bool ok;
+    if constexpr (SEL) {
+        const uint32_t s = sel[b];
+        ok = s < B_src && src.string(s, (uint64_t)units * 16u, p, len);
+    } else {
+        ok = src.string(b, (uint64_t)units * 16u, p, len);
+    }
     uint4 *dst = reinterpret_cast<uint4 *>(chars_pm) + (size_t)blk0 * units + (b - blk0);
     for (uint32_t cg = blockIdx.y; cg * 8u < units; cg += gridDim.y) {
 #pragma unroll
@@ -184,14 +216,26 @@ hipError_t launch_ragged_slice(const uint8_t *values, const uint64_t *offsets, u
     return hipGetLastError();
 }
 
-hipError_t launch_ragged_to_position_major(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t stride, uint8_t *chars_pm,
-                                           uint32_t *lens, hipStream_t stream) {
+template <class Src, bool SEL>
+static hipError_t launch_to_pm(const Src &src, const uint32_t *sel, size_t B_src, size_t B, size_t stride, uint8_t *chars_pm, uint32_t *lens,
+                               hipStream_t stream) {
     if (B == 0) return hipSuccess;
     const uint32_t units = (uint32_t)(stride / 16);
     const size_t cgroups = (units + 7u) / 8u;
-    hipLaunchKernelGGL(ragged_to_pm_kernel, dim3((unsigned)((B + 63) / 64), (unsigned)std::min<size_t>(cgroups, 65535)), dim3(256), 0, stream,
-                       values, offsets, base, (uint32_t)B, units, chars_pm, lens);
+    hipLaunchKernelGGL((ragged_to_pm_kernel<Src, SEL>), dim3((unsigned)((B + 63) / 64), (unsigned)std::min<size_t>(cgroups, 65535)), dim3(256), 0, stream,
+                       src, sel, (uint32_t)B_src, (uint32_t)B, units, chars_pm, lens);
     return hipGetLastError();
+}
+
+hipError_t launch_ragged_to_position_major(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t stride, uint8_t *chars_pm,
+                                           uint32_t *lens, hipStream_t stream) {
+    return launch_to_pm<RaggedSrc, false>(RaggedSrc{values, offsets, base}, nullptr, B, B, stride, chars_pm, lens, stream);
+}
+
+hipError_t launch_gather_to_position_major(const uint8_t *src, size_t src_stride, const uint32_t *lens, const uint64_t *offsets, size_t B,
+                                           const uint32_t *sel, size_t n_sel, size_t stride, uint8_t *chars_pm, uint32_t *lens_out, hipStream_t stream) {
+    if (offsets) return launch_to_pm<RaggedSrc, true>(RaggedSrc{src, offsets, 0}, sel, B, n_sel, stride, chars_pm, lens_out, stream);
+    return launch_to_pm<PaddedSrc, true>(PaddedSrc{src, lens, src_stride}, sel, B, n_sel, stride, chars_pm, lens_out, stream);
 }
 
 }  // namespace hrx

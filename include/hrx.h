@@ -490,6 +490,62 @@ int hrx_extract_spans_host(int layout, const uint8_t *src, size_t stride, const 
                            uint32_t require_accept, const hrx_extract_out *out, int threads);
 
 /* ------------------------------------------------------------------ */
+/* ROUTE: a screened batch sorted into circuit-size buckets and staged as witness input */
+/* ------------------------------------------------------------------ */
+/*
+ * The step between "screen" (a match call) and "prove" (a witness call per circuit size): M is a per-call argument of every witness entry point and the
+ * witness writes (4 D + 2) * M bytes per string whatever n_b is, so a caller with proving keys for several sizes wants each string witnessed at the smallest
+ * size that takes it, and the strings the circuit would not accept not witnessed at all — without status, offsets or bytes leaving the device.
+ *
+ * hrx_route_device / hrx_route_host: a stable partition of strings 0..B by (kept?, length bucket).
+ *   lens / offsets  exactly one is non-NULL (else HRX_ERR_ARG): lens [B] u32 as the padded entry points take it, n_b = lens[b]; or offsets [B + 1] u64 as the
+ *                   ragged ones take it, n_b = offsets[b+1] - offsets[b] (a string whose offsets decrease has no valid length)
+ *   status          [B] u64 of a match call on the same strings, or NULL: no screening.  String b passes the screen iff its status code is 0 and
+ *                   ((status[b] >> 8) & require_accept) == require_accept — the rule of hrx_extract_spans_*
+ *   bounds          [n_buckets] u32, a HOST array in both forms (read at call time): the circuit sizes, 1 <= n_buckets <= HRX_MAX_BUCKETS, strictly
+ *                   increasing, bounds[n_buckets - 1] <= 2^24; B < 2^32.  Anything else: HRX_ERR_ARG
+ * String b is KEPT iff it passes the screen, its length is valid and n_b <= bounds[n_buckets - 1]; its bucket is the least j with n_b <= bounds[j]
+ * (n_b == bounds[j] belongs to bucket j: the witness accepts n == M).
+ *   order           [B] u32: a permutation of 0..B
+ *   bucket_offsets  [n_buckets + 2] u64: bucket j is order[bucket_offsets[j] .. bucket_offsets[j+1]); range j == n_buckets holds the strings that were NOT
+ *                   kept, so that a front-end can report its rejects.  bucket_offsets[0] = 0, bucket_offsets[n_buckets + 1] = B.
+ * Every range is in increasing b: the partition is stable, and the result is deterministic.
+ * status, offsets and bucket_offsets 8-byte aligned, lens and order 4-byte.
+ * Device form: device pointers (bounds excepted), asynchronous on `stream`: three kernel launches and nothing else — no allocation, no context scratch, no
+ * synchronisation, no atomics — so it is legal inside a stream capture whatever def set the context holds.  Its temporaries live in `workspace` (8-byte
+ * aligned device memory of at least hrx_route_workspace_bytes(B) bytes; too small: HRX_ERR_ARG).  HRX_ERR_HIP on a host-only context.  B == 0 writes
+ * bucket_offsets (all zero) and reads nothing.
+ * Host form: host pointers, no context, re-entrant, sequential, nothing allocated.
+ *
+ * hrx_gather_to_position_major_device: the strings sel[0 .. n_sel) of a batch of B as HRX_LAYOUT_INPUT_POSITION_MAJOR input blocked by HRX_PM_BLOCK over the
+ * OUTPUT index k, per-string capacity `stride` (stride % 16 == 0, >= 16): chars_pm [n_sel * stride] bytes (16-byte aligned), slot k holds source string
+ * sel[k], the bytes past its n zero, lens_out[k] = n.  Typically sel = order + bucket_offsets[j] and stride = round_up(bounds[j], 16), after the caller has
+ * read bucket_offsets back ((n_buckets + 2) * 8 bytes).  The output feeds hrx_witness_batch_device_layout, hrx_witness_batch_device_planes,
+ * hrx_fr_columns_device* and hrx_match_batch_device unchanged, called with M = bounds[j].
+ *   layout  HRX_LAYOUT_STRING_MAJOR: src [B][src_stride] (16-byte aligned, src_stride % 16 == 0), lens [B]; offsets ignored
+ *           HRX_LAYOUT_INPUT_RAGGED: src = values, offsets [B + 1]; alignment and readable range as for hrx_ragged_to_position_major_device; src_stride, lens ignored
+ *   sel     [n_sel] u32 device array of string indices, in any order, repeats allowed
+ * DEFENSIVE: sel is caller memory.  Slot k is all zero with lens_out[k] = UINT32_MAX, and none of that string's bytes is read, when sel[k] >= B, a ragged
+ * string's offsets decrease, n > stride, or (string-major) lens[sel[k]] > src_stride; every consumer then reports kStatusBadLength for that slot.
+ * Asynchronous on `stream`, one launch, no scratch, capturable.  HRX_ERR_HIP on a host-only context.  (hrx_ragged_to_position_major_device is the same kernel
+ * without sel; hrx_chars_to_position_major_device stays the faster route for a dense, unselected string-major batch.) */
+#define HRX_MAX_BUCKETS 8
+size_t hrx_route_workspace_bytes(size_t B);
+int hrx_route_device(hrx_ctx *ctx, const uint64_t *status, uint32_t require_accept,
+                     const uint32_t *lens, const uint64_t *offsets, size_t B,
+                     const uint32_t *bounds, size_t n_buckets,
+                     uint32_t *order, uint64_t *bucket_offsets,
+                     void *workspace, size_t workspace_bytes, void *stream);
+int hrx_route_host(const uint64_t *status, uint32_t require_accept,
+                   const uint32_t *lens, const uint64_t *offsets, size_t B,
+                   const uint32_t *bounds, size_t n_buckets,
+                   uint32_t *order, uint64_t *bucket_offsets);
+int hrx_gather_to_position_major_device(hrx_ctx *ctx, int layout, const uint8_t *src, size_t src_stride,
+                                        const uint32_t *lens, const uint64_t *offsets, size_t B,
+                                        const uint32_t *sel, size_t n_sel,
+                                        size_t stride, uint8_t *chars_pm, uint32_t *lens_out, void *stream);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f4 — compact witness -> field cells (the step after the path)        */
 /* ------------------------------------------------------------------ */
 /* Expands the compact rows of strings [b_begin, b_begin + b_count) of a finished batch into what
