@@ -77,6 +77,12 @@ extern "C" {
     pub fn hrx_gather_to_position_major_device(ctx: *mut hrx_ctx, layout: c_int, src: *const u8, src_stride: usize, lens: *const u32,
                                                offsets: *const u64, b: usize, sel: *const u32, n_sel: usize, stride: usize,
                                                chars_pm: *mut u8, lens_out: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hrx_match_selected_device(ctx: *mut hrx_ctx, layout: c_int, src: *const u8, src_stride: usize, lens: *const u32,
+                                     offsets: *const u64, b: usize, sel: *const u32, n_sel: usize, m: usize, status: *mut u64,
+                                     span_counts: *mut u32, spans: *mut u64, max_spans: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_match_selected_host(ctx: *mut hrx_ctx, layout: c_int, src: *const u8, src_stride: usize, lens: *const u32,
+                                   offsets: *const u64, b: usize, sel: *const u32, n_sel: usize, m: usize, status: *mut u64,
+                                   span_counts: *mut u32, spans: *mut u64, max_spans: usize) -> c_int;
     pub fn hrx_witness_batch_device(ctx: *mut hrx_ctx, chars: *const u8, stride: usize, lens: *const u32, b: usize,
                                     m: usize, records: *mut u32, masked: *mut u16, status: *mut u64,
                                     stream: *mut c_void) -> c_int;

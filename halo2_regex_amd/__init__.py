@@ -155,6 +155,8 @@ def _load():
         "hrx_route_device": (i, [vp, vp, C.c_uint32, vp, vp, sz, _u32p, sz, vp, vp, vp, sz, vp]),
         "hrx_route_host": (i, [vp, C.c_uint32, vp, vp, sz, _u32p, sz, vp, vp]),
         "hrx_gather_to_position_major_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, vp, vp, vp]),
+        "hrx_match_selected_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
+        "hrx_match_selected_host": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, vp, vp, vp, sz]),
         "hrx_shard_range": (None, [sz, i, i, C.POINTER(sz), C.POINTER(sz)]),
         "hrx_derive_states": (i, [vp, _u8p, sz, _u64p]),
         "hrx_derive_substr_ids": (i, [vp, _u64p, sz, _u64p]),
@@ -459,6 +461,7 @@ def recommended_pitches(M):
 LAYOUT_STRING_MAJOR, LAYOUT_POSITION_MAJOR, LAYOUT_INPUT_POSITION_MAJOR = 0, 1, 2
 LAYOUT_RECORD_PLANES = 4      # describe_launch only: the launch witness_batch_planes makes
 LAYOUT_INPUT_RAGGED = 8       # describe_match only: the launch match_batch_ragged makes (values + offsets, include/hrx.h RAGGED)
+LAYOUT_INPUT_SELECTED = 16    # describe_match only, or-ed with LAYOUT_STRING_MAJOR or LAYOUT_INPUT_RAGGED: the launch match_selected makes, B = len(sel)
 
 
 PLACE_OFF, PLACE_WALK = 0, 1     # hrx_ctx_set_placement modes
@@ -955,6 +958,60 @@ class RegexVerifyConfig:
                                                        lens.data_ptr() if lens is not None else None, offsets.data_ptr() if offsets is not None else None,
                                                        B, sel.data_ptr(), n_sel, stride, chars_pm.data_ptr(), lens_out.data_ptr(), s.cuda_stream))
         return chars_pm, lens_out
+
+    # -- selected: the match of a selection of a batch, in its order (include/hrx.h SELECTED) ------------------------------------
+    def match_selected(self, src, sel, lens=None, offsets=None, max_spans=16, stream=None, out=None):
+        """hrx_match_selected_device: the match of the strings sel (int32 CUDA tensor of string indices, as route returns them in order) of a string-major
+        batch (src (B, src_stride) uint8 with lens (B,) int32) or a ragged one (src = values with offsets (B + 1,) int64), walked in sel's order ->
+        (status (B,), counts (B,), spans (B, max_spans)) indexed by STRING as match_batch / match_batch_ragged return them: the entries of the strings
+        in sel are what those calls give, every other entry is left as it was (out=(status, counts, spans): the caller's pre-filled tensors; without
+        out the tensors are fresh and unselected entries hold nothing meaningful).  An index >= B is skipped.  Asynchronous on `stream`."""
+        assert src.is_cuda and sel.is_cuda and src.dtype == torch.uint8 and sel.dtype == torch.int32 and sel.is_contiguous() and sel.dim() == 1
+        if (lens is None) == (offsets is None):
+            raise HrxError(HRX_ERR_ARG, "match_selected: exactly one of lens and offsets")
+        if offsets is not None:
+            assert offsets.dtype == torch.int64 and offsets.is_contiguous() and src.is_contiguous()
+            layout, B, src_stride = LAYOUT_INPUT_RAGGED, offsets.numel() - 1, 0
+        else:
+            assert lens.dtype == torch.int32 and lens.is_contiguous() and src.dim() == 2 and src.stride(1) == 1
+            layout, B, src_stride = LAYOUT_STRING_MAJOR, lens.numel(), src.stride(0)
+        if out is None:
+            out = (torch.empty(B, dtype=torch.int64, device=src.device), torch.empty(B, dtype=torch.int32, device=src.device),
+                   torch.empty((B, max(max_spans, 1)), dtype=torch.int64, device=src.device))
+        st, cnt, sp = out
+        assert st.numel() == B and cnt.numel() == B and sp.shape[0] == B and sp.is_contiguous()
+        s = torch.cuda.current_stream(src.device) if stream is None else stream
+        _check(lib.hrx_match_selected_device(self._need_device(src, sel, lens, offsets, st, cnt, sp), layout, src.data_ptr(), src_stride,
+                                             lens.data_ptr() if lens is not None else None, offsets.data_ptr() if offsets is not None else None, B,
+                                             sel.data_ptr() if sel.numel() else None, sel.numel(), self.max_chars_size, st.data_ptr(), cnt.data_ptr(),
+                                             sp.data_ptr() if max_spans else None, max_spans, s.cuda_stream))
+        return st, cnt, sp
+
+    def match_selected_host(self, src, sel, lens=None, offsets=None, max_spans=16, out=None):
+        """hrx_match_selected_host: host arrays — src (B, stride) uint8 with lens (B,), or src = values with offsets (B + 1,) uint64 — and sel (uint32
+        string indices) -> (status (B,) u64, counts (B,) u32, spans (B, max_spans) u64) indexed by string; entries of strings not in sel keep what
+        out=(status, counts, spans) held (fresh arrays: zero)."""
+        if (lens is None) == (offsets is None):
+            raise HrxError(HRX_ERR_ARG, "match_selected_host: exactly one of lens and offsets")
+        src = _np(src, np.uint8)
+        sel = _np(sel, np.uint32)
+        if offsets is not None:
+            offsets = _np(offsets, np.uint64)
+            layout, B, stride = LAYOUT_INPUT_RAGGED, len(offsets) - 1, 0
+            if not src.size:
+                src = np.zeros(16, np.uint8)
+        else:
+            lens = _np(lens, np.uint32)
+            layout, (B, stride) = LAYOUT_STRING_MAJOR, src.shape
+        if out is None:
+            out = np.zeros(B, np.uint64), np.zeros(B, np.uint32), np.zeros((B, max_spans), np.uint64)
+        st, cnt, sp = out
+        assert st.shape == (B,) and cnt.shape == (B,) and sp.shape == (B, max_spans) and st.dtype == np.uint64 and cnt.dtype == np.uint32 and sp.dtype == np.uint64
+        assert sp.flags.c_contiguous
+        _check(lib.hrx_match_selected_host(self._need_ctx(), layout, src.ctypes.data, stride, lens.ctypes.data if lens is not None else None,
+                                           offsets.ctypes.data if offsets is not None else None, B, sel.ctypes.data if sel.size else None, sel.size,
+                                           self.max_chars_size, st.ctypes.data, cnt.ctypes.data, sp.ctypes.data if max_spans else None, max_spans))
+        return st, cnt, sp
 
     @contextlib.contextmanager
     def circuit_size(self, M):

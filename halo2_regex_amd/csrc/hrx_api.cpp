@@ -342,7 +342,7 @@ void hrx_ctx_destroy(hrx_ctx *c) {
     for (uint8_t *p : c->d_member) (void)hipFree(p);
     c->chars.release(); c->lens.release(); c->records.release(); c->masked.release();
     c->status.release(); c->states.release(); c->tags.release();
-    c->match_rec.release(); c->match_msk.release(); c->match_chars.release(); c->match_counts.release(); c->match_spans.release(); c->match_lens.release();
+    c->match_rec.release(); c->match_msk.release(); c->match_chars.release(); c->match_counts.release(); c->match_spans.release(); c->match_lens.release(); c->match_status.release();
     delete c;
 }
 

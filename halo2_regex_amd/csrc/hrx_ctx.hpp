@@ -146,6 +146,7 @@ struct hrx_ctx {
     bool match_via_rows = false;
     DevBuf match_rec, match_msk, match_chars, match_counts, match_spans;
     DevBuf match_lens;               // ragged "via rows": the slice's lens (hrx_match_batch_device_ragged)
+    DevBuf match_status;             // selected "via rows": the slice's status words by slot (hrx_match_selected_device)
     hipStream_t match_stream = nullptr;
     bool match_used = false;
     DevBuf d_cw;                    // CLASS-WIDE image of a config of 4 .. 7 defs (DefsSet::cw_image): the single-launch def-parallel path

@@ -220,10 +220,13 @@ void host_witness_batch(const DefsSet &s, const uint8_t *chars, size_t stride, c
     host_batch_run(B, M, threads, [&](size_t b) { status[b] = host_witness_one(s, chars + b * stride, lens[b], M, records + b * M * D, masked + b * M); });
 }
 
-// host_match_one over a batch whose string b is the n bytes at string(b, n)
-template <class String>
-static void host_match_strings(const DefsSet &s, size_t B, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads, const String &string) {
-    host_batch_run(B, M, threads, [&](size_t b) {
+// host_match_one over `count` positions of a batch: position k is string b = where(k) (SIZE_MAX: passed over), the n bytes at string(b, n); results at index b
+template <class String, class Where>
+static void host_match_strings(const DefsSet &s, size_t count, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads,
+                               const String &string, const Where &where) {
+    host_batch_run(count, M, threads, [&](size_t k) {
+        const size_t b = where(k);
+        if (b == SIZE_MAX) return;
         size_t n;
         const uint8_t *p = string(b, n);
         uint32_t c = 0;
@@ -231,10 +234,11 @@ static void host_match_strings(const DefsSet &s, size_t B, size_t M, uint64_t *s
         if (span_counts) span_counts[b] = c;
     });
 }
+static size_t every_string(size_t k) { return k; }
 
 void host_match_batch(const DefsSet &s, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
                       uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads) {
-    host_match_strings(s, B, M, status, span_counts, spans, max_spans, threads, [&](size_t b, size_t &n) { n = lens[b]; return chars + b * stride; });
+    host_match_strings(s, B, M, status, span_counts, spans, max_spans, threads, [&](size_t b, size_t &n) { n = lens[b]; return chars + b * stride; }, every_string);
 }
 
 // ragged batch: string b is values[offsets[b] .. offsets[b + 1]) (decreasing offsets: kStatusBadLength, nothing read)
@@ -243,7 +247,24 @@ void host_match_batch_ragged(const DefsSet &s, const uint8_t *values, const uint
     host_match_strings(s, B, M, status, span_counts, spans, max_spans, threads, [&](size_t b, size_t &n) {
         n = offsets[b + 1] >= offsets[b] ? (size_t)(offsets[b + 1] - offsets[b]) : SIZE_MAX;
         return values + offsets[b];
-    });
+    }, every_string);
+}
+
+// the strings sel[0 .. n_sel) of a ragged (offsets) or padded (lens, stride) batch of B; an index at or past B is passed over, a padded string
+// longer than its slot has no valid length
+void host_match_selected(const DefsSet &s, const uint8_t *src, size_t stride, const uint32_t *lens, const uint64_t *offsets, size_t B, const uint32_t *sel,
+                         size_t n_sel, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads) {
+    const auto where = [&](size_t k) { return sel[k] < B ? (size_t)sel[k] : SIZE_MAX; };
+    if (offsets)
+        host_match_strings(s, n_sel, M, status, span_counts, spans, max_spans, threads, [&](size_t b, size_t &n) {
+            n = offsets[b + 1] >= offsets[b] ? (size_t)(offsets[b + 1] - offsets[b]) : SIZE_MAX;
+            return src + offsets[b];
+        }, where);
+    else
+        host_match_strings(s, n_sel, M, status, span_counts, spans, max_spans, threads, [&](size_t b, size_t &n) {
+            n = lens[b] <= stride ? (size_t)lens[b] : SIZE_MAX;
+            return src + b * stride;
+        }, where);
 }
 
 // derive_states (lib.rs:804-823) for one string: states[d * (n + 1) + i]; false + (state, char) of the reference's panic

@@ -20,6 +20,9 @@ void host_match_batch(const DefsSet &s, const uint8_t *chars, size_t stride, con
 // ragged batch (include/hrx.h RAGGED): string b is values[offsets[b] .. offsets[b + 1])
 void host_match_batch_ragged(const DefsSet &s, const uint8_t *values, const uint64_t *offsets, size_t B, size_t M,
                              uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads);
+// a selection of either batch form (include/hrx.h hrx_match_selected_host): offsets non-NULL: ragged; results at index sel[k]
+void host_match_selected(const DefsSet &s, const uint8_t *src, size_t stride, const uint32_t *lens, const uint64_t *offsets, size_t B, const uint32_t *sel,
+                         size_t n_sel, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, int threads);
 bool host_derive_states(const DefsSet &s, const uint8_t *chars, size_t n, uint64_t *states, uint32_t &bad_state, uint32_t &bad_char);
 void host_pair_tags(const DefsSet &s, const uint64_t *states, size_t n, uint16_t *tags);
 void host_endpoint_flags(const DefsSet &s, const uint64_t *states, const uint64_t *substr_ids, size_t n, uint8_t *flags);

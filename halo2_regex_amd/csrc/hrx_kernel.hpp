@@ -338,6 +338,32 @@ hipError_t launch_ragged_slice(const uint8_t *values, const uint64_t *offsets, u
 hipError_t launch_ragged_to_position_major(const uint8_t *values, const uint64_t *offsets, uint64_t base, size_t B, size_t stride, uint8_t *chars_pm,
                                            uint32_t *lens, hipStream_t stream);
 
+// SELECTED match (include/hrx.h hrx_match_selected_device): the strings sel[0 .. n_sel) of a ragged (offsets) or string-major (lens,
+// src_stride) batch of B, walked in that order, results at index sel[k]; an index at or past B is passed over.
+//   fused:     match_selected_kernel<D, GTAB, HALF, Src> — the ragged kernel's persistent-lane walk with the string's place and the lane's next
+//              string as parameters (a kernel of its own: match_ragged_kernel stays the code it was); a.chars / stride / lens / in_pm unused, a.B = B
+//   via rows:  selected_slice_kernel<Src> stages slot s = string sel[k0 + s]; the witness launch writes the slots' status words into scratch;
+//              spans_from_masked_selected_kernel reads slot s and writes status, count and runs at sel[k0 + s]
+struct SelectedSrc {
+    const uint8_t *src;
+    const uint64_t *offsets;        // ragged: [B + 1]; NULL: string-major
+    const uint32_t *lens;           // string-major: [B]
+    uint64_t src_stride;
+};
+hipError_t launch_match_selected(const MatchArgs &a, const SelectedSrc &s, const uint32_t *sel, size_t n_sel, const MatchPlan &p, int num_cus,
+                                 hipStream_t stream);
+hipError_t launch_selected_slice(const SelectedSrc &s, size_t B, const uint32_t *sel, size_t k0, size_t n, uint32_t limit, size_t stride, uint8_t *out,
+                                 uint32_t *lens, hipStream_t stream);
+// where the scan of a selected via-rows slice writes: slot s of the slice (a.status, a.masked, a.B slots) -> index sel[s] < B_src of these arrays
+struct SpanScatter {
+    const uint32_t *sel;            // the slice's part of the selection
+    uint32_t B_src;
+    uint64_t *status;
+    uint32_t *span_counts;          // may be NULL
+    uint64_t *spans;                // [B_src][max_spans], NULL when max_spans == 0
+};
+hipError_t launch_spans_from_masked_selected(const MatchArgs &a, const SpanScatter &o, hipStream_t stream);
+
 // EXTRACT (include/hrx.h hrx_extract_spans_device; hrx_kernel_extract.hip): the runs of a match call -> run_offsets / runs / byte_offsets / values / totals.
 // Count, scan, apply, gather: four launches, nothing but the caller's workspace in between (extract_workspace_bytes: 3 words per kExtractThreads strings + 4)
 constexpr uint32_t kExtractThreads = 256;       // strings per workgroup of the count and apply launches; the scan launch takes this many partials per round

@@ -6,6 +6,7 @@
 //                                 What leaves the chip is the status word, the run count and the runs: ~1 input byte read per row, nothing written per row.
 //                                 The kernel is the padded input's addressing and prefetch around the lane core (hrx_match_tile.h MatchLane).
 //   spans_from_masked_pm_kernel   "via rows": one lane per string over the masked rows [ceil(M/8)][nb][8] of a position-major witness launch.
+//   spans_from_masked_selected_kernel   the same scan for hrx_match_selected_device: slot s of the slice -> the outputs of string sel[s].
 //   pm_input_slice_kernel         "via rows" slices inside one block of position-major input -> string-major scratch.
 #include "hrx_device.h"
 #include "hrx_walk_pm.h"
@@ -60,25 +61,37 @@ __global__ __launch_bounds__(kMatchThreads) void match_lane_kernel(const MatchAr
     lane.finish(a, b);
 }
 
-// "via rows": the runs of string b from its masked rows (exact: no optimistic masks to undo)
-__global__ __launch_bounds__(256) void spans_from_masked_pm_kernel(const MatchArgs a) {
+// "via rows": the runs of slot b of a slice from its masked rows (exact: no optimistic masks to undo).  SEL: the slot's status word, count and runs go
+// to index o.sel[b] of o's arrays (an index at or past o.B_src: nothing is written); else to index b of a's own
+template <bool SEL>
+__device__ __forceinline__ void spans_from_masked(const MatchArgs &a, const SpanScatter &o) {
     const size_t b = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (b >= a.B) return;
+    size_t ob = b;
+    uint64_t *ospans = a.spans;
+    uint32_t *ocounts = a.span_counts;
+    if constexpr (SEL) {
+        ob = o.sel[b];
+        if (ob >= o.B_src) return;
+        ospans = o.spans;
+        ocounts = o.span_counts;
+    }
     const size_t k = b / kPmBlock, bb = b % kPmBlock;
     const size_t nb = min((size_t)kPmBlock, (size_t)a.B - k * kPmBlock);
     const uint32_t M = a.M, noct = (M + 7u) / 8u;
     const uint16_t *mk = a.masked + k * kPmBlock * (size_t)noct * 8 + bb * 8;
     SpanEmitter em;
     em.init();
-    SpanSlots out{a.spans ? a.spans + b * a.max_spans : nullptr, a.max_spans};
-    const bool ok = (a.status[b] & 0xffu) == kStatusOk;
-    if (ok && (a.max_spans || a.span_counts)) {
-        for (uint32_t o = 0; o < noct; ++o) {
-            const uint4 q = *reinterpret_cast<const uint4 *>(mk + (size_t)o * nb * 8);
+    SpanSlots out{ospans ? ospans + ob * a.max_spans : nullptr, a.max_spans};
+    const uint64_t st = a.status[b];
+    const bool ok = (st & 0xffu) == kStatusOk;
+    if (ok && (a.max_spans || ocounts)) {
+        for (uint32_t oc = 0; oc < noct; ++oc) {
+            const uint4 q = *reinterpret_cast<const uint4 *>(mk + (size_t)oc * nb * 8);
             const uint32_t w[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
-                const uint32_t r = o * 8u + (uint32_t)i;
+                const uint32_t r = oc * 8u + (uint32_t)i;
                 if (r >= M) break;
                 const uint32_t v = (w[i >> 1] >> (16 * (i & 1) + 8)) & 0xffu;   // masked_substr_id (lib.rs:752-761)
                 if (v != (em.open ? em.o_sid : 0u)) {
@@ -89,8 +102,12 @@ __global__ __launch_bounds__(256) void spans_from_masked_pm_kernel(const MatchAr
         }
         em.finish(M, out);
     }
-    if (a.span_counts) a.span_counts[b] = ok ? em.count : 0u;
+    if constexpr (SEL) o.status[ob] = st;
+    if (ocounts) ocounts[ob] = ok ? em.count : 0u;
 }
+
+__global__ __launch_bounds__(256) void spans_from_masked_pm_kernel(const MatchArgs a) { spans_from_masked<false>(a, SpanScatter{}); }
+__global__ __launch_bounds__(256) void spans_from_masked_selected_kernel(const MatchArgs a, const SpanScatter o) { spans_from_masked<true>(a, o); }
 
 __global__ __launch_bounds__(256) void pm_input_slice_kernel(const uint8_t *chars_pm, size_t stride, size_t B, size_t b0, size_t n, uint8_t *outp) {
     const size_t chunks = stride / 16;
@@ -120,6 +137,12 @@ hipError_t launch_match_lane(const MatchArgs &a, const MatchPlan &p, hipStream_t
 hipError_t launch_spans_from_masked(const MatchArgs &a, hipStream_t stream) {
     if (a.B == 0) return hipSuccess;
     hipLaunchKernelGGL(spans_from_masked_pm_kernel, dim3((unsigned)(((size_t)a.B + 255) / 256)), dim3(256), 0, stream, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_spans_from_masked_selected(const MatchArgs &a, const SpanScatter &o, hipStream_t stream) {
+    if (a.B == 0) return hipSuccess;
+    hipLaunchKernelGGL(spans_from_masked_selected_kernel, dim3((unsigned)(((size_t)a.B + 255) / 256)), dim3(256), 0, stream, a, o);
     return hipGetLastError();
 }
 

@@ -4,6 +4,9 @@
 // the masked rows' runs.  The two input forms share the argument rules, the fused arguments, the via-rows driver (plan_via_rows, via_rows_scratch,
 // match_via_rows: a form brings only the step that stages a slice's input) and the host entries' copy-out; they differ in the staging step and in
 // how a host entry cuts its chunks.  DESIGN.md §11, §12.
+// hrx_match_selected_device / _host (include/hrx.h SELECTED): the same two routes over an index array — the fused selected kernel, or via
+// rows with an indexed staging step and a scan that scatters slot s of a slice to string sel[k0 + s]; the host entry packs the selected strings of a
+// chunk back to back and runs the ragged chunk path on them.
 #include "hrx_ctx.hpp"
 #include "hrx_host_walk.hpp"
 #include "hrx_lane.h"
@@ -80,13 +83,15 @@ static size_t via_rows_slice(size_t B, size_t M, size_t D, size_t extra) {
 struct ViaRows {
     size_t slice;       // strings per slice
     size_t stride;      // of the staged string-major input (ragged: round_up(M, 16); gather: the caller's)
-    bool ragged;        // ragged_slice_kernel stages every slice (string-major input + lens, counted in the slice size)
+    bool ragged;        // a staging kernel makes every slice (string-major input + lens, counted in the slice size): ragged_slice_kernel, or
+    bool selected;      // selected_slice_kernel over either source, the slice's status words by slot in scratch and a scattering scan
     bool gather;        // slices inside a block of position-major input: pm_input_slice_kernel makes its strings string-major first
     int layout;         // of the witness launch
 };
-static ViaRows plan_via_rows(int layout, size_t stride, size_t B, size_t M, size_t D) {
+static ViaRows plan_via_rows(int layout, size_t stride, size_t B, size_t M, size_t D, bool selected = false) {
     ViaRows v{};
-    v.ragged = layout == HRX_LAYOUT_INPUT_RAGGED;
+    v.selected = selected;
+    v.ragged = layout == HRX_LAYOUT_INPUT_RAGGED || selected;
     v.stride = v.ragged ? (M + 15) & ~(size_t)15 : stride;
     v.slice = via_rows_slice(B, M, D, v.ragged ? v.stride + 4 : 0);
     const bool in_pm = layout == HRX_LAYOUT_INPUT_POSITION_MAJOR;
@@ -105,13 +110,16 @@ static int via_rows_scratch(hrx_ctx *ctx, const ViaRows &v, size_t M, hipStream_
     const size_t D = ctx->s.defs.size(), noct = (M + 7) / 8, nquad = (M + 3) / 4;
     const size_t rec_bytes = nquad * 4 * D * 4 * v.slice, msk_bytes = noct * 8 * 2 * v.slice;
     const size_t chr_bytes = v.ragged || v.gather ? v.slice * v.stride : 0, len_bytes = v.ragged ? v.slice * 4 : 0;
-    if (rec_bytes > ctx->match_rec.cap || msk_bytes > ctx->match_msk.cap || chr_bytes > ctx->match_chars.cap || len_bytes > ctx->match_lens.cap) {
+    const size_t sta_bytes = v.selected ? v.slice * 8 : 0;
+    if (rec_bytes > ctx->match_rec.cap || msk_bytes > ctx->match_msk.cap || chr_bytes > ctx->match_chars.cap || len_bytes > ctx->match_lens.cap ||
+        sta_bytes > ctx->match_status.cap) {
         if (capturing) return fail(HRX_ERR_STATE, "match via rows: the context's scratch is allocated at first use, not inside a stream capture");
         HIP_TRY(hipDeviceSynchronize());     // (the buffers may be in use by earlier launches)
         HIP_TRY(ctx->match_rec.reserve(rec_bytes));
         HIP_TRY(ctx->match_msk.reserve(msk_bytes));
         HIP_TRY(ctx->match_chars.reserve(chr_bytes));
         HIP_TRY(ctx->match_lens.reserve(len_bytes));
+        HIP_TRY(ctx->match_status.reserve(sta_bytes));
     }
     if (ctx->match_used && ctx->match_stream != st) {
         if (capturing) return fail(HRX_ERR_STATE, "match via rows: the scratch was last used on another stream");
@@ -123,10 +131,11 @@ static int via_rows_scratch(hrx_ctx *ctx, const ViaRows &v, size_t M, hipStream_
 }
 
 // slice by slice: stage(b0, n, chars, lens) gives the input of strings [b0, b0 + n) as the witness launch reads it (v.layout, v.stride), then the
-// position-major witness launch into the scratch and the runs of its masked rows
+// position-major witness launch into the scratch and the runs of its masked rows.  scatter (a selected call: B slots, sel = the whole selection, the
+// caller's outputs): the launch's status words go to scratch by slot and the scan writes slot b0 + s at index sel[b0 + s]
 template <class Stage>
 static int match_via_rows(hrx_ctx *ctx, const ViaRows &v, size_t B, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans,
-                          hipStream_t st, const Stage &stage) {
+                          hipStream_t st, const Stage &stage, const SpanScatter *scatter = nullptr) {
     if (int rc = via_rows_scratch(ctx, v, M, st)) return rc;      // first: it may allocate the buffers read below
     MatchArgs m{};
     m.M = (uint32_t)M; m.max_spans = (uint32_t)max_spans; m.masked = (const uint16_t *)ctx->match_msk.p;
@@ -135,8 +144,14 @@ static int match_via_rows(hrx_ctx *ctx, const ViaRows &v, size_t B, size_t M, ui
         const uint8_t *c = nullptr;
         const uint32_t *lens = nullptr;
         if (int rc = stage(b0, n, c, lens)) return rc;
-        if (int rc = launch_batch(ctx, c, v.stride, lens, n, M, (uint32_t *)ctx->match_rec.p, (uint16_t *)ctx->match_msk.p, status + b0, st, 0, 0, v.layout)) return rc;
-        if (max_spans || span_counts) {
+        uint64_t *const slice_status = scatter ? (uint64_t *)ctx->match_status.p : status + b0;
+        if (int rc = launch_batch(ctx, c, v.stride, lens, n, M, (uint32_t *)ctx->match_rec.p, (uint16_t *)ctx->match_msk.p, slice_status, st, 0, 0, v.layout)) return rc;
+        if (scatter) {
+            m.B = (uint32_t)n; m.status = slice_status;
+            SpanScatter o = *scatter;
+            o.sel += b0;
+            HIP_TRY(launch_spans_from_masked_selected(m, o, st));
+        } else if (max_spans || span_counts) {
             m.B = (uint32_t)n; m.status = status + b0;
             m.span_counts = span_counts ? span_counts + b0 : nullptr; m.spans = spans ? spans + b0 * max_spans : nullptr;
             HIP_TRY(launch_spans_from_masked(m, st));
@@ -194,6 +209,46 @@ static int match_ragged_device_locked(hrx_ctx *ctx, const uint8_t *values, const
         HIP_TRY(launch_ragged_slice(values, offsets, base, b0, n, (uint32_t)M, v.stride, (uint8_t *)ctx->match_chars.p, (uint32_t *)ctx->match_lens.p, st));
         return HRX_OK;
     });
+}
+
+// SELECTED (include/hrx.h): the argument rules of both entries in the order the errors are reported; the device entry's alignment rules come before its
+// device check, so a host-only context reports them too
+static int check_selected_args(int layout, const uint8_t *src, size_t src_stride, const uint32_t *lens, const uint64_t *offsets, size_t B, const uint32_t *sel,
+                               size_t n_sel, size_t M, const uint64_t *status, const uint32_t *span_counts, const uint64_t *spans, size_t max_spans, bool device) {
+    const bool ragged = layout == HRX_LAYOUT_INPUT_RAGGED;
+    if (!ragged && layout != HRX_LAYOUT_STRING_MAJOR) return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR or HRX_LAYOUT_INPUT_RAGGED");
+    if (n_sel > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "selection too large");
+    if (int rc = check_common_args(!src || (ragged ? !offsets : !lens), ragged ? ((uintptr_t)offsets & 7) != 0 : ((uintptr_t)lens & 3) != 0,
+                                   "offsets, status, span_counts and spans must be 8-byte aligned, lens and sel 4-byte", B, M, status, span_counts, spans, max_spans))
+        return rc;
+    if (n_sel && !sel) return fail(HRX_ERR_ARG, "NULL sel");
+    if ((uintptr_t)sel & 3) return fail(HRX_ERR_ARG, "offsets, status, span_counts and spans must be 8-byte aligned, lens and sel 4-byte");
+    if (device && B && n_sel) {
+        if ((uintptr_t)src & 15) return fail(HRX_ERR_ARG, "src must be 16-byte aligned");
+        if (!ragged && ((src_stride & 15) || src_stride < 16)) return fail(HRX_ERR_ARG, "string-major src_stride % 16 == 0 and src_stride >= 16");
+    }
+    return HRX_OK;
+}
+
+// the device part of the selected match (device pointers; ctx->mu held, the device selected)
+static int match_selected_device_locked(hrx_ctx *ctx, const SelectedSrc &src, size_t B, const uint32_t *sel, size_t n_sel, size_t M, uint64_t *status,
+                                        uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
+    if (B == 0 || n_sel == 0) return HRX_OK;
+    MatchPlan p;
+    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, HRX_LAYOUT_STRING_MAJOR, n_sel, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.fused) {
+        const MatchArgs m = fused_args(ctx, p, src.src, B, M, status, span_counts, spans, max_spans);
+        HIP_TRY(launch_match_selected(m, src, sel, n_sel, p, ctx->num_cus, st));
+        return HRX_OK;
+    }
+    const ViaRows v = plan_via_rows(HRX_LAYOUT_INPUT_RAGGED, 0, n_sel, M, ctx->s.defs.size(), true);
+    const SpanScatter scatter{sel, (uint32_t)B, status, span_counts, spans};
+    return match_via_rows(ctx, v, n_sel, M, nullptr, span_counts, spans, max_spans, st, [&](size_t k0, size_t n, const uint8_t *&c, const uint32_t *&l) -> int {
+        c = (const uint8_t *)ctx->match_chars.p;
+        l = (const uint32_t *)ctx->match_lens.p;
+        HIP_TRY(launch_selected_slice(src, B, sel, k0, n, (uint32_t)M, v.stride, (uint8_t *)ctx->match_chars.p, (uint32_t *)ctx->match_lens.p, st));
+        return HRX_OK;
+    }, &scatter);
 }
 
 // the host entry points' device buffers for the results of a chunk of n strings (d_counts / d_spans: NULL where nothing is to come back) ...
@@ -329,6 +384,93 @@ int hrx_match_batch_host_ragged(hrx_ctx *ctx, const uint8_t *values, const uint6
     return HRX_OK;
 }
 
+int hrx_match_selected_device(hrx_ctx *ctx, int layout, const uint8_t *src, size_t src_stride, const uint32_t *lens, const uint64_t *offsets, size_t B,
+                              const uint32_t *sel, size_t n_sel, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (int rc = check_selected_args(layout, src, src_stride, lens, offsets, B, sel, n_sel, M, status, span_counts, spans, max_spans, true)) return rc;
+    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (B == 0 || n_sel == 0) return HRX_OK;
+    const bool ragged = layout == HRX_LAYOUT_INPUT_RAGGED;
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard;
+    HIP_TRY(guard.set(ctx->device));
+    return match_selected_device_locked(ctx, SelectedSrc{src, ragged ? offsets : nullptr, ragged ? nullptr : lens, src_stride}, B, sel, n_sel, M, status,
+                                        span_counts, spans, max_spans, (hipStream_t)stream);
+}
+
+int hrx_match_selected_host(hrx_ctx *ctx, int layout, const uint8_t *src, size_t src_stride, const uint32_t *lens, const uint64_t *offsets, size_t B,
+                            const uint32_t *sel, size_t n_sel, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (int rc = check_selected_args(layout, src, src_stride, lens, offsets, B, sel, n_sel, M, status, span_counts, spans, max_spans, false)) return rc;
+    if (B == 0 || n_sel == 0) return HRX_OK;
+    const bool ragged = layout == HRX_LAYOUT_INPUT_RAGGED;
+    if (ctx->device == HRX_DEVICE_NONE) {     // the native host walk, no row written
+        const size_t threads = std::max<size_t>(1, std::min<size_t>(ctx->host_threads > 0 ? (size_t)ctx->host_threads : std::thread::hardware_concurrency(), n_sel * M / 8192));
+        host_match_selected(ctx->s, src, src_stride, ragged ? nullptr : lens, ragged ? offsets : nullptr, B, sel, n_sel, M, status, span_counts, spans, max_spans,
+                            (int)threads);
+        return HRX_OK;
+    }
+    // through the device: chunks of the selection whose strings' bytes sum to ~64 MiB, packed back to back with offsets
+    // of their own, matched by the ragged chunk path, the results copied out to index sel[k].  Only the selected strings' bytes cross the link; a
+    // string with no valid length gets its status here and an index at or past B is passed over
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard;
+    HIP_TRY(guard.set(ctx->device));
+    const size_t kSpan = (size_t)64 << 20;
+    const size_t max_n = std::max<size_t>(1, std::min<size_t>((size_t)1 << 20, kSpan / (8 * max_spans + 12)));
+    hipStream_t st = ctx->stream;
+    std::vector<uint8_t> packed;
+    std::vector<uint64_t> offs, h_status, h_spans;
+    std::vector<uint32_t> idx, h_counts;
+    for (size_t k = 0; k < n_sel;) {
+        packed.clear(); offs.assign(1, 0); idx.clear();
+        for (; k < n_sel && idx.size() < max_n && packed.size() < kSpan; ++k) {
+            const size_t b = sel[k];
+            if (b >= B) continue;
+            uint64_t n;
+            const uint8_t *p;
+            if (ragged) {
+                n = offsets[b + 1] >= offsets[b] ? offsets[b + 1] - offsets[b] : UINT64_MAX;
+                p = src + offsets[b];
+            } else {
+                n = lens[b] <= src_stride ? lens[b] : UINT64_MAX;
+                p = src + b * src_stride;
+            }
+            if (n > M) {
+                status[b] = kStatusBadLength;
+                if (span_counts) span_counts[b] = 0;
+                continue;
+            }
+            packed.insert(packed.end(), p, p + n);
+            offs.push_back(packed.size());
+            idx.push_back((uint32_t)b);
+        }
+        const size_t n = idx.size();
+        if (n == 0) continue;
+        HIP_TRY(ctx->chars.reserve(((packed.size() + 15) & ~(size_t)15) + 16));
+        HIP_TRY(ctx->lens.reserve(8 * (n + 1)));
+        uint32_t *d_counts;
+        uint64_t *d_spans;
+        if (int rc = host_result_bufs(ctx, n, span_counts != nullptr, max_spans, d_counts, d_spans)) return rc;
+        if (!packed.empty()) HIP_TRY(hipMemcpyAsync(ctx->chars.p, packed.data(), packed.size(), hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ctx->lens.p, offs.data(), 8 * (n + 1), hipMemcpyHostToDevice, st));
+        if (int rc = match_ragged_device_locked(ctx, (const uint8_t *)ctx->chars.p, (const uint64_t *)ctx->lens.p, 0, n, M, (uint64_t *)ctx->status.p, d_counts,
+                                                d_spans, max_spans, st))
+            return rc;
+        h_status.resize(n);
+        if (span_counts) h_counts.resize(n);
+        if (max_spans) h_spans.resize(n * max_spans);
+        if (int rc = host_results_out(ctx, 0, n, h_status.data(), span_counts ? h_counts.data() : nullptr, h_spans.data(), max_spans, d_counts, d_spans, st)) return rc;
+        for (size_t j = 0; j < n; ++j) {
+            const size_t b = idx[j];
+            status[b] = h_status[j];
+            if (span_counts) span_counts[b] = h_counts[j];
+            if (max_spans) std::memcpy(spans + b * max_spans, h_spans.data() + j * max_spans, 8 * max_spans);
+        }
+    }
+    return HRX_OK;
+}
+
 int hrx_ragged_to_position_major_device(hrx_ctx *ctx, const uint8_t *values, const uint64_t *offsets, size_t B, size_t stride, uint8_t *chars_pm,
                                         uint32_t *lens, void *stream) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
@@ -345,6 +487,15 @@ int hrx_ragged_to_position_major_device(hrx_ctx *ctx, const uint8_t *values, con
 }
 
 static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_rows, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
+    // HRX_LAYOUT_INPUT_SELECTED | a source layout: the launch of hrx_match_selected_device with n_sel = B
+    const bool selected = (layout & HRX_LAYOUT_INPUT_SELECTED) != 0;
+    const char *src_name = nullptr;
+    if (selected) {
+        layout &= ~HRX_LAYOUT_INPUT_SELECTED;
+        if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_RAGGED)
+            return fail(HRX_ERR_ARG, "HRX_LAYOUT_INPUT_SELECTED goes with HRX_LAYOUT_STRING_MAJOR or HRX_LAYOUT_INPUT_RAGGED");
+        src_name = layout == HRX_LAYOUT_INPUT_RAGGED ? "hrx::RaggedSrc" : "hrx::PaddedSrc";
+    }
     const bool ragged = layout == HRX_LAYOUT_INPUT_RAGGED;
     if (!ragged && layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
         return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR, HRX_LAYOUT_INPUT_POSITION_MAJOR or HRX_LAYOUT_INPUT_RAGGED");
@@ -352,14 +503,21 @@ static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_
     if (!match_plan(s, dbg, via_rows, ragged ? HRX_LAYOUT_STRING_MAJOR : layout, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
     if (p.fused) {
         const char *g = p.gtab ? "true" : "false", *h = p.half ? "true" : "false";
-        if (ragged) std::snprintf(out, cap, "hrx::match_ragged_kernel<%zu, %s, %s> grid=persistent threads=%d lds=%zu", s.defs.size(), g, h, p.threads, p.lds_bytes);
+        if (selected)
+            std::snprintf(out, cap, "hrx::match_selected_kernel<%zu, %s, %s, %s> grid=persistent threads=%d lds=%zu", s.defs.size(), g, h, src_name, p.threads, p.lds_bytes);
+        else if (ragged) std::snprintf(out, cap, "hrx::match_ragged_kernel<%zu, %s, %s> grid=persistent threads=%d lds=%zu", s.defs.size(), g, h, p.threads, p.lds_bytes);
         else std::snprintf(out, cap, "hrx::match_lane_kernel<%zu, %s, %s> grid=%d threads=%d lds=%zu", s.defs.size(), g, h, p.grid, p.threads, p.lds_bytes);
         return HRX_OK;
     }
-    const ViaRows v = plan_via_rows(layout, 0, B, M, s.defs.size());
+    const ViaRows v = plan_via_rows(selected ? HRX_LAYOUT_INPUT_RAGGED : layout, 0, B, M, s.defs.size(), selected);
     if (v.slice == 0) return fail(HRX_ERR_BOUNDS, "match via rows: one string's witness rows exceed the 768 MiB scratch");
     char w[3072];
     if (int rc = describe_config(s, dbg, 0u, mpc_on, v.layout, v.slice, M, num_cus, w, sizeof w)) return rc;
+    if (selected) {
+        std::snprintf(out, cap, "via rows, %zu slice(s) of %zu strings: hrx::selected_slice_kernel<%s> + %s + hrx::spans_from_masked_selected_kernel",
+                      (B + v.slice - 1) / v.slice, v.slice, src_name, w);
+        return HRX_OK;
+    }
     std::snprintf(out, cap, "via rows, %zu slice(s) of %zu strings: %s%s + hrx::spans_from_masked_pm_kernel", (B + v.slice - 1) / v.slice, v.slice,
                   ragged ? "hrx::ragged_slice_kernel + " : v.gather ? "hrx::pm_input_slice_kernel + " : "", w);
     return HRX_OK;

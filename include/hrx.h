@@ -546,6 +546,43 @@ int hrx_gather_to_position_major_device(hrx_ctx *ctx, int layout, const uint8_t 
                                         size_t stride, uint8_t *chars_pm, uint32_t *lens_out, void *stream);
 
 /* ------------------------------------------------------------------ */
+/* SELECTED: match a selection of a batch through an index array, in its order */
+/* ------------------------------------------------------------------ */
+/*
+ * hrx_match_selected_device / hrx_match_selected_host: the match of strings sel[0 .. n_sel) of a batch of B, and of no other.  What a second, more
+ * expensive screen runs over the survivors of a first one (sel = the kept ranges of hrx_route's order), or what walks a batch in length order
+ * (sel = the order of hrx_route with status = NULL), without a copy of the strings.
+ *   SOURCE     layout, src, src_stride, lens, offsets and B describe the source batch exactly as hrx_gather_to_position_major_device takes it:
+ *              HRX_LAYOUT_STRING_MAJOR (src [B][src_stride], lens [B]; offsets ignored) or HRX_LAYOUT_INPUT_RAGGED (src = values, offsets [B + 1];
+ *              src_stride and lens ignored).  Alignment and readable range are those of hrx_match_batch_device / hrx_match_batch_device_ragged (device
+ *              entry: src 16-byte aligned, src_stride % 16 == 0 and >= 16; the host entry has no alignment rule for src).  Position-major input is
+ *              refused with HRX_ERR_ARG: it is dense by construction, and hrx_match_batch_device serves it.
+ *   SELECTION  sel [n_sel] u32, 4-byte aligned: a device array for the device entry, a host array for the host entry; what hrx_route_device writes as
+ *              `order`.  Entries are distinct: the result for a repeated index is unspecified.  An entry >= B is skipped: nothing is read for it and
+ *              nothing is written.  n_sel == 0 launches nothing; sel == NULL with n_sel > 0 is HRX_ERR_ARG.
+ *   OUTPUTS    are indexed by STRING, not by slot: status [B], span_counts [B], spans [B][max_spans], the sizes and rules of the unselected call.  For
+ *              every b in sel the entries of b are bit for bit what the unselected entry of the same layout writes, kStatusBadLength with count 0
+ *              included: decreasing offsets, n_b > M, or lens[b] > src_stride (none of that string's bytes are read).  Entries of strings not in sel
+ *              are not touched: a caller pre-fills them or reads only the selected ones.  hrx_extract_spans_* and hrx_route_* therefore run behind
+ *              this call unchanged (pre-fill status with kStatusBadLength = 3 and the counts with 0 for "not matched").
+ *   ORDER      the strings are walked in sel order: persistent lane g of G takes sel[g], sel[g + G], ...  Order affects time only.
+ * The device entry is asynchronous on `stream`; stream-capture and scratch rules are those of hrx_match_batch_device_ragged: def sets with a fused
+ * kernel need no scratch and the launch can be captured; "via rows" def sets use the context scratch with the same first-use rule (inside a capture
+ * before that: HRX_ERR_STATE).  No atomics: the call is deterministic.  HRX_ERR_HIP on a host-only context (after the argument rules).
+ * Host entry: host buffers, synchronous.  On a host-only context the native host walk over the selection; on a device context chunks of the selection
+ * whose strings' bytes sum to about 64 MiB are packed back to back, matched on the device and copied out to index sel[k]: only the selected strings'
+ * bytes cross the link.
+ * hrx_describe_match / hrx_ctx_describe_match accept HRX_LAYOUT_INPUT_SELECTED or-ed with one of the two source layouts, with B standing for n_sel, and
+ * name this launch; the flag has a meaning only there. */
+enum { HRX_LAYOUT_INPUT_SELECTED = 16 };
+int hrx_match_selected_device(hrx_ctx *ctx, int layout, const uint8_t *src, size_t src_stride, const uint32_t *lens,
+                              const uint64_t *offsets, size_t B, const uint32_t *sel, size_t n_sel, size_t M,
+                              uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream);
+int hrx_match_selected_host(hrx_ctx *ctx, int layout, const uint8_t *src, size_t src_stride, const uint32_t *lens,
+                            const uint64_t *offsets, size_t B, const uint32_t *sel, size_t n_sel, size_t M,
+                            uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f4 — compact witness -> field cells (the step after the path)        */
 /* ------------------------------------------------------------------ */
 /* Expands the compact rows of strings [b_begin, b_begin + b_count) of a finished batch into what
