@@ -364,7 +364,7 @@ int launch_batch(hrx_ctx *ctx, const uint8_t *chars, size_t stride, const uint32
     if ((stride & 15) || stride < 16 || ((uintptr_t)chars & 15))
         return fail(HRX_ERR_ARG, "chars must be 16-byte aligned with stride % 16 == 0 and stride >= 16");
     if (((uintptr_t)records & 15) || ((uintptr_t)masked & 15) || ((uintptr_t)status & 7) || ((uintptr_t)lens & 3))
-        return fail(HRX_ERR_ARG, "output buffers must be 16-byte aligned");
+        return fail(HRX_ERR_ARG, "records and masked must be 16-byte aligned, status 8-byte, lens 4-byte");
     if (rec_pitch < M || msk_pitch < M || rec_pitch > (1u << 24) || msk_pitch > (1u << 24))
         return fail(HRX_ERR_ARG, "row pitches must be >= max_chars_size");
     if ((M % 8 == 0) && ((rec_pitch % 8) || (msk_pitch % 8)))
@@ -806,8 +806,8 @@ int hrx_witness_batch_device_planes(hrx_ctx *ctx, int layout, const uint8_t *cha
     if (!(layout & HRX_LAYOUT_POSITION_MAJOR)) return fail(HRX_ERR_ARG, "record planes are a position-major layout");
     const size_t Dn = ctx->s.defs.size();
     if (!record_planes || !(n_planes == Dn || (Dn == 1 && n_planes == 2))) return fail(HRX_ERR_ARG, "record planes: one buffer per RegexDefs of the config (one def: one buffer, or two row stripes)");
-    for (size_t d = 0; d < n_planes; ++d)
-        if (!record_planes[d] || ((uintptr_t)record_planes[d] & 15)) return fail(HRX_ERR_ARG, "record planes must be 16-byte aligned device buffers");
+    for (size_t d = 0; d < n_planes; ++d)      // (an empty batch has no buffers: B == 0 writes nothing, as in the other entries)
+        if ((B && !record_planes[d]) || ((uintptr_t)record_planes[d] & 15)) return fail(HRX_ERR_ARG, "record planes must be 16-byte aligned device buffers");
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     if (ctx->device != HRX_DEVICE_NONE) HIP_TRY(guard.set(ctx->device));

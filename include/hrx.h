@@ -190,6 +190,9 @@ const char *hrx_last_error(void);
  *            2 two defs flag the same row (out of contract): bits 40..63 row
  *            3 n_b > M
  *            records/masked of a string whose code != 0 are unspecified.
+ * Alignment (all the device entry points of this section; less is HRX_ERR_ARG, and nothing is written): chars, records, masked and every
+ * record plane / row stripe 16 bytes, status 8 bytes, lens 4 bytes.  More is never needed: a caller may carve the buffers out of a pool
+ * of its own at exactly these alignments.
  * All five pointers are DEVICE pointers on ctx's device; `stream` is a hipStream_t (NULL = the HIP null stream).
  * The call is asynchronous on that stream.
  */

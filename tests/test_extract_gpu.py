@@ -15,6 +15,7 @@ from halo2_regex_amd import synth
 from oracle_lib import OracleDefs
 from test_extract_cpu import GUARD, Batch, batch, check_capped, check_full, column, expect, short_caps
 from test_match_cpu import CFG_1, CFG_H4, _defs, rle_masked
+from test_match_gpu import _placed
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda", 0)
@@ -31,39 +32,51 @@ def dev_cfg(make_cfg):
         os.environ.pop("HRX_DEBUG_FLAGS", None)
 
 
-def _inputs(bt, form):
-    """the batch on the device in one of the three input forms: (args, kwargs) of extract_batch / extract_batch_ragged, input byte count"""
+def _inputs(bt, form, alloc=None):
+    """the batch on the device in one of the three input forms: (args, kwargs) of extract_batch / extract_batch_ragged, input byte count
+    (alloc: the caller's allocator, tests/test_match_gpu.py _placed)"""
     if form == "ragged":
         values, offsets = column(bt.chars, bt.lens, lead=3)          # strings at odd addresses
-        return "ragged", (torch.from_numpy(values).to(DEV), torch.from_numpy(offsets.astype(np.int64)).to(DEV)), {}, len(values)
-    d_chars = torch.from_numpy(np.ascontiguousarray(bt.chars)).to(DEV)
-    d_lens = torch.from_numpy(bt.lens.astype(np.int32)).to(DEV)
+        return "ragged", (_placed(alloc, torch.from_numpy(values).to(DEV), "values"), _placed(alloc, torch.from_numpy(offsets.astype(np.int64)).to(DEV), "offsets")), {}, len(values)
+    d_chars = _placed(alloc, torch.from_numpy(np.ascontiguousarray(bt.chars)).to(DEV), "chars")
+    d_lens = _placed(alloc, torch.from_numpy(bt.lens.astype(np.int32)).to(DEV), "lens")
     if form == "pm":
-        return "padded", (hra.chars_to_position_major(d_chars), d_lens), {"chars_pm_stride": bt.chars.shape[1]}, bt.chars.size
+        return "padded", (_placed(alloc, hra.chars_to_position_major(d_chars), "chars_pm"), d_lens), {"chars_pm_stride": bt.chars.shape[1]}, bt.chars.size
     return "padded", (d_chars, d_lens), {}, bt.chars.size
 
 
-def guarded_out(B, K, runs_cap, values_cap):
-    """the nine tensors of alloc_extract as slices of poisoned buffers with GUARD elements behind each -> (out, full buffers, sizes)"""
+OUT_KINDS = ["status", "counts", "spans", "run_offsets", "runs", "byte_offsets", "bytes_out", "totals", "workspace"]      # (for an allocator by argument kind)
+
+
+def guarded_out(B, K, runs_cap, values_cap, alloc=None):
+    """the nine tensors of alloc_extract as slices of poisoned buffers with GUARD elements behind each -> (out, full buffers, sizes)
+    (alloc(nbytes, dtype, kind) -> (view, raw): the caller's allocator, which poisons with the byte P8; GUARD elements of its guard stand in `full`)"""
     sizes = [B, B, B * K, B + 1, runs_cap, runs_cap + 1, values_cap, 4, hra.extract_workspace_bytes(B) // 8]
     dts = [torch.int64, torch.int32, torch.int64, torch.int64, torch.int64, torch.int64, torch.uint8, torch.int64, torch.int64]
     poison = {torch.int64: P64, torch.int32: P32, torch.uint8: P8}
-    full = [torch.full((n + GUARD,), poison[dt], dtype=dt, device=DEV) for n, dt in zip(sizes, dts)]
+    if alloc is not None:
+        isz = {torch.int64: 8, torch.int32: 4, torch.uint8: 1}
+        full = [alloc(n * isz[dt], dt, kind)[1][:(n + GUARD) * isz[dt]].view(dt) for n, dt, kind in zip(sizes, dts, OUT_KINDS)]
+    else:
+        full = [torch.full((n + GUARD,), poison[dt], dtype=dt, device=DEV) for n, dt in zip(sizes, dts)]
     out = [f[:n] for f, n in zip(full, sizes)]
     out[2] = out[2].view(B, K)
     return tuple(out), full, sizes
 
 
-def run_device(cfg, bt, form, K, want, runs_cap=None, values_cap=None, require_accept=0):
-    """match + extract on the device into guarded outputs; checks the guards, status / counts against the oracle and the capacity rule against `want`"""
-    kind, args, kw, in_bytes = _inputs(bt, form)
+def run_device(cfg, bt, form, K, want, runs_cap=None, values_cap=None, require_accept=0, alloc=None, stream=None):
+    """match + extract on the device into guarded outputs; checks the guards, status / counts against the oracle and the capacity rule against `want`
+    (alloc: the caller's allocator for inputs and outputs; stream: the launches go there and it alone is waited for)"""
+    kind, args, kw, in_bytes = _inputs(bt, form, alloc)
+    if stream is not None:
+        kw = dict(kw, stream=stream)
     B = len(bt.lens)
     runs_cap = B * K if runs_cap is None else runs_cap
     values_cap = in_bytes if values_cap is None else values_cap
-    out, full, sizes = guarded_out(B, K, runs_cap, values_cap)
+    out, full, sizes = guarded_out(B, K, runs_cap, values_cap, alloc)
     fn = cfg.extract_batch_ragged if kind == "ragged" else cfg.extract_batch
     ex = fn(*args, max_spans=K, require_accept=require_accept, out=out, **kw)
-    torch.cuda.synchronize()
+    (torch.cuda if stream is None else stream).synchronize()
     for f, n, name in zip(full, sizes, "status counts spans run_offsets runs byte_offsets values totals workspace".split()):
         assert bool((f[n:] == {8: P64, 4: P32, 1: P8}[f.element_size()]).all()), (name, form)
     host = [f.cpu().numpy() for f in full]

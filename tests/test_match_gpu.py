@@ -32,14 +32,33 @@ def _expect(oracle, names, chars, lens, M):
     return ost, rle_masked(omsk, lens, ost)
 
 
-def _run(cfg, chars, lens, max_spans=16, pm=False):
-    d_chars = torch.from_numpy(chars).to(DEV)
-    d_lens = torch.from_numpy(lens.astype(np.int32)).to(DEV)
+def _placed(alloc, t, kind):
+    """t copied into the caller's allocation of that kind (alloc(nbytes, dtype, kind) -> (view, raw), tests/caller_conditions.py); no allocator: t itself"""
+    if alloc is None:
+        return t
+    v = alloc(t.numel() * t.element_size(), t.dtype, kind)[0].view(t.shape)
+    v.copy_(t)
+    return v
+
+
+def _match_out(alloc, B, max_spans):
+    """status, counts, spans out of the caller's allocator (None without one: match_batch makes its own)"""
+    if alloc is None:
+        return None
+    return (alloc(B * 8, torch.int64, "status")[0], alloc(B * 4, torch.int32, "counts")[0], alloc(B * max_spans * 8, torch.int64, "spans")[0].view(B, max_spans))
+
+
+def _run(cfg, chars, lens, max_spans=16, pm=False, alloc=None, stream=None):
+    d_chars = _placed(alloc, torch.from_numpy(chars).to(DEV), "chars")
+    d_lens = _placed(alloc, torch.from_numpy(lens.astype(np.int32)).to(DEV), "lens")
+    okw = {} if alloc is None else dict(out=_match_out(alloc, len(lens), max_spans))
+    if stream is not None:
+        okw["stream"] = stream
     if pm:
-        st, cnt, sp = cfg.match_batch(hra.chars_to_position_major(d_chars), d_lens, max_spans=max_spans, chars_pm_stride=chars.shape[1])
+        st, cnt, sp = cfg.match_batch(_placed(alloc, hra.chars_to_position_major(d_chars), "chars_pm"), d_lens, max_spans=max_spans, chars_pm_stride=chars.shape[1], **okw)
     else:
-        st, cnt, sp = cfg.match_batch(d_chars, d_lens, max_spans=max_spans)
-    torch.cuda.synchronize()
+        st, cnt, sp = cfg.match_batch(d_chars, d_lens, max_spans=max_spans, **okw)
+    (torch.cuda if stream is None else stream).synchronize()
     return st.cpu().numpy().view(np.uint64), cnt.cpu().numpy().view(np.uint32), sp.cpu().numpy().view(np.uint64)
 
 

@@ -13,7 +13,7 @@ import halo2_regex_amd as hra
 from halo2_regex_amd import synth
 from oracle_lib import OracleDefs
 from test_match_cpu import CFG_1, CFG_A, _defs, rle_masked
-from test_match_gpu import DEV, NO_HOST, SHAPES, VARIANTS, _cfg, _check, _expect, _run
+from test_match_gpu import DEV, NO_HOST, SHAPES, VARIANTS, _cfg, _check, _expect, _match_out, _placed, _run
 
 pytestmark = pytest.mark.gpu
 BAD_LENGTH = 3
@@ -61,9 +61,13 @@ def _padded(chars, lens, M):
     return out
 
 
-def _run_ragged(cfg, values, offsets, max_spans=16):
-    st, cnt, sp = cfg.match_batch_ragged(torch.from_numpy(values).to(DEV), torch.from_numpy(offsets).to(DEV), max_spans=max_spans)
-    torch.cuda.synchronize()
+def _run_ragged(cfg, values, offsets, max_spans=16, alloc=None, stream=None):
+    okw = {} if alloc is None else dict(out=_match_out(alloc, len(offsets) - 1, max_spans))
+    if stream is not None:
+        okw["stream"] = stream
+    st, cnt, sp = cfg.match_batch_ragged(_placed(alloc, torch.from_numpy(values).to(DEV), "values"), _placed(alloc, torch.from_numpy(offsets).to(DEV), "offsets"),
+                                         max_spans=max_spans, **okw)
+    (torch.cuda if stream is None else stream).synchronize()
     return st.cpu().numpy().view(np.uint64), cnt.cpu().numpy().view(np.uint32), sp.cpu().numpy().view(np.uint64)
 
 

@@ -14,6 +14,7 @@ from oracle_lib import OracleDefs
 from test_extract_cpu import GUARD, batch, column
 from test_extract_gpu import dev_cfg
 from test_match_cpu import CFG_A, CFG_H4, _defs
+from test_match_gpu import _placed
 from test_route_cpu import EIGHT, check_invariants, expect_route, lengths_of
 from test_route_cpu import test_device_forms_on_a_host_only_context as _host_only_context
 
@@ -46,9 +47,16 @@ def guards_intact(full, sizes):
     return all(bool((f[n:] == {8: P64, 4: P32, 1: P8}[f.element_size()]).all()) for f, n in zip(full, sizes))
 
 
-def route_device(cfg, status, kw, B, bounds, require_accept, stream=None):
-    """route into guarded outputs and a guarded workspace -> (order uint32, bucket_offsets uint64) on the host"""
+def route_device(cfg, status, kw, B, bounds, require_accept, stream=None, alloc=None):
+    """route into guarded outputs and a guarded workspace -> (order uint32, bucket_offsets uint64) on the host
+    (alloc(nbytes, dtype, kind) -> (view, raw): the caller's allocator for every argument, which checks its own guards; the stream alone is waited for then)"""
     sizes = [B, len(bounds) + 2, hra.route_workspace_bytes(B) // 8]
+    if alloc is not None:
+        out = tuple(alloc(n * sz, dt, kind)[0] for n, sz, dt, kind in zip(sizes, (4, 8, 8), (torch.int32, torch.int64, torch.int64), ("order", "bucket_offsets", "workspace")))
+        r = cfg.route(None if status is None else _placed(alloc, to_dev(status), "status_in"), bounds=bounds, require_accept=require_accept, out=out, stream=stream,
+                      **{k: _placed(alloc, to_dev(v), k) for k, v in kw.items()})
+        (torch.cuda if stream is None else stream).synchronize()
+        return r.order.cpu().numpy().view(np.uint32), r.bucket_offsets.cpu().numpy().view(np.uint64)
     out, full = guarded(sizes, [torch.int32, torch.int64, torch.int64])
     r = cfg.route(None if status is None else to_dev(status), bounds=bounds, require_accept=require_accept, out=out, stream=stream,
                   **{k: to_dev(v) for k, v in kw.items()})
@@ -96,9 +104,16 @@ def expect_gather(strings, sel, stride):
     return (hra.chars_to_position_major(sm) if len(sel) else np.zeros(0, np.uint8)), lens_out
 
 
-def gather_device(cfg, src, sel, stride, **kw):
+def gather_device(cfg, src, sel, stride, alloc=None, stream=None, **kw):
+    """(alloc: the caller's allocator for the selection and the outputs — src and the lengths are the caller's tensors —, which checks its own guards; stream: the
+    launch goes there and it alone is waited for)"""
     n_sel = len(sel)
     sizes = [n_sel * stride, n_sel]
+    if alloc is not None:
+        out = (alloc(sizes[0], torch.uint8, "chars_pm_out")[0], alloc(sizes[1] * 4, torch.int32, "lens_out")[0])
+        pm, lo = cfg.gather_to_position_major(src, _placed(alloc, to_dev(sel), "sel"), stride, out=out, **({} if stream is None else dict(stream=stream)), **kw)
+        (torch.cuda if stream is None else stream).synchronize()
+        return pm.cpu().numpy(), lo.cpu().numpy().view(np.uint32)
     out, full = guarded(sizes, [torch.uint8, torch.int32])
     pm, lo = cfg.gather_to_position_major(src, to_dev(sel), stride, out=out, **kw)
     torch.cuda.synchronize()

@@ -93,10 +93,19 @@ def selections(B, seed=1):
             "every_third": np.arange(0, B, 3, dtype=np.uint32), "empty": np.zeros(0, np.uint32), "past_the_batch": mixed[rng.permutation(len(mixed))]}
 
 
-def run_selected(cfg, src, sel, B, max_spans=16, **kw):
-    out, full = guarded(B, max_spans)
-    cfg.match_selected(src, to_dev(sel), max_spans=max_spans, out=out, **kw)
-    return read_back(out, full, B)
+def run_selected(cfg, src, sel, B, max_spans=16, alloc=None, stream=None, **kw):
+    """alloc(nbytes, dtype, kind) -> (view, raw): the caller's allocator (tests/caller_conditions.py) for the selection and the outputs, which it poisons like guarded()
+    (src and the lengths are the caller's tensors already); stream: the launch goes there and it alone is waited for"""
+    if alloc is None:
+        out, full = guarded(B, max_spans)
+        cfg.match_selected(src, to_dev(sel), max_spans=max_spans, out=out, **kw)
+        return read_back(out, full, B)
+    out = (alloc(B * 8, torch.int64, "status")[0], alloc(B * 4, torch.int32, "counts")[0], alloc(B * max_spans * 8, torch.int64, "spans")[0].view(B, max_spans))
+    d_sel = alloc(len(sel) * 4, torch.int32, "sel")[0]
+    d_sel.copy_(to_dev(sel))
+    cfg.match_selected(src, d_sel, max_spans=max_spans, out=out, **({} if stream is None else dict(stream=stream)), **kw)
+    (torch.cuda if stream is None else stream).synchronize()
+    return tuple(t.cpu().numpy().view(dt) for t, dt in zip(out, (np.uint64, np.uint32, np.uint64)))
 
 
 def edge_case(oracle, D, B=1000, M=208):

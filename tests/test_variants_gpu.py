@@ -169,24 +169,45 @@ def _stripe_sizes(hra, B, M, R):
     return npl.value, nm.value
 
 
-def launch_every_form(hra, row, case, cfg, o, ost, tag, fr=False, pitched=None):
+def launch_every_form(hra, row, case, cfg, o, ost, tag, fr=False, pitched=None, alloc=None, stream=None):
     """The row's entry point on one case, every output into poisoned, guarded buffers (string-major: pitched ones on odd seeds, the pitch gaps checked; position-major:
-    both input layouts, then record planes / row stripes); fr: fr_columns of the launch's rows as well.  Returns [(form, status, records (B, M, D), masked (B, M))]."""
+    both input layouts, then record planes / row stripes); fr: fr_columns of the launch's rows as well.  Returns [(form, status, records (B, M, D), masked (B, M))].
+    alloc(nbytes, dtype, kind) -> (view, raw): the caller's allocator for every buffer the library sees, the inputs included (raw: the bytes from the view's first on,
+    GUARD poisoned ones behind it; tests/caller_conditions.py); stream: the launches go there, and it alone is waited for."""
     import torch
     dev = torch.device("cuda", 0)
     B, M, D, stride = case.B, case.M, case.D, case.stride
     d_chars = torch.from_numpy(case.chars).to(dev)
     d_lens = torch.from_numpy(case.lens.astype(np.int32)).to(dev)
+    skw = {} if stream is None else dict(stream=stream)
+    sync = torch.cuda.synchronize if stream is None else stream.synchronize
+    if alloc is None:
+        def _guarded_(nbytes, dtype, kind):
+            return _guarded(torch, dev, nbytes, dtype)
+
+        def to_pm(c):
+            return hra.chars_to_position_major(c)
+    else:
+        _guarded_ = alloc
+
+        def to_pm(c):
+            v = alloc(c.numel(), torch.uint8, "chars_pm")[0]
+            v.copy_(hra.chars_to_position_major(c))
+            return v
+        c_v, l_v = alloc(B * stride, torch.uint8, "chars")[0].view(B, stride), alloc(B * 4, torch.int32, "lens")[0]
+        c_v.copy_(d_chars)
+        l_v.copy_(d_lens)
+        d_chars, d_lens = c_v, l_v
     runs = []      # (form, st, rec (B, M, D) numpy u32, msk (B, M) numpy u16)
     if row["entry"] == "sm":
         pitched = case.seed % 2 == 1 if pitched is None else pitched
         rp, mp = hra.recommended_pitches(M)[:2] if pitched else (M, M)
-        r_v, r_raw = _guarded(torch, dev, B * rp * D * 4, torch.int32)
-        m_v, m_raw = _guarded(torch, dev, B * mp * 2, torch.int16)
-        s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
+        r_v, r_raw = _guarded_(B * rp * D * 4, torch.int32, "records")
+        m_v, m_raw = _guarded_(B * mp * 2, torch.int16, "masked")
+        s_v, s_raw = _guarded_(B * 8, torch.int64, "status")
         out = (r_v.view(B, rp, D)[:, :M], m_v.view(B, mp)[:, :M], s_v)
-        cfg.witness_batch(d_chars, d_lens, out=out)
-        torch.cuda.synchronize()
+        cfg.witness_batch(d_chars, d_lens, out=out, **skw)
+        sync()
         for raw, n, what in ((r_raw, B * rp * D * 4, "records"), (m_raw, B * mp * 2, "masked"), (s_raw, B * 8, "status")):
             _guards_intact(raw, n, tag + " " + what)
         if pitched:      # rows M.. of every string's slot are never written
@@ -195,51 +216,51 @@ def launch_every_form(hra, row, case, cfg, o, ost, tag, fr=False, pitched=None):
         runs.append(("string-major" + (" pitched" if pitched else ""), out[2].cpu().numpy().view(np.uint64),
                      out[0].cpu().numpy().view(np.uint32), out[1].cpu().numpy().view(np.uint16)))
         if fr:
-            _check_fr(hra, torch, o, cfg, case, d_chars, d_lens, out, dict(position_major=False), ost, tag)
+            _check_fr(hra, torch, o, cfg, case, d_chars, d_lens, out, dict(position_major=False), ost, tag, alloc, stream)
     else:
         nr, nm = C.c_size_t(0), C.c_size_t(0)
         hra.lib.hrx_position_major_sizes(B, M, D, C.byref(nr), C.byref(nm))
         for pm_input in (False, True):
-            r_v, r_raw = _guarded(torch, dev, nr.value * 4, torch.int32)
-            m_v, m_raw = _guarded(torch, dev, nm.value * 2, torch.int16)
-            s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
+            r_v, r_raw = _guarded_(nr.value * 4, torch.int32, "records")
+            m_v, m_raw = _guarded_(nm.value * 2, torch.int16, "masked")
+            s_v, s_raw = _guarded_(B * 8, torch.int64, "status")
             if pm_input:
-                src, kw = hra.chars_to_position_major(d_chars), dict(chars_pm_stride=stride)
+                src, kw = to_pm(d_chars), dict(chars_pm_stride=stride)
             else:
                 src, kw = d_chars, {}
-            cfg.witness_batch_position_major(src, d_lens, out=(r_v, m_v, s_v), **kw)
-            torch.cuda.synchronize()
+            cfg.witness_batch_position_major(src, d_lens, out=(r_v, m_v, s_v), **kw, **skw)
+            sync()
             form = "position-major" + (" (position-major input)" if pm_input else "")
             for raw, n, what in ((r_raw, nr.value * 4, "records"), (m_raw, nm.value * 2, "masked"), (s_raw, B * 8, "status")):
                 _guards_intact(raw, n, "%s %s %s" % (tag, form, what))
             r1, m1 = hra.position_major_to_string_major(r_v, m_v, B, M, D)
             runs.append((form, s_v.cpu().numpy().view(np.uint64), r1.cpu().numpy().view(np.uint32), m1.cpu().numpy().view(np.uint16)))
             if fr and pm_input:
-                _check_fr(hra, torch, o, cfg, case, src, d_lens, (r_v, m_v, s_v), dict(position_major=True, **kw), ost, tag)
+                _check_fr(hra, torch, o, cfg, case, src, d_lens, (r_v, m_v, s_v), dict(position_major=True, **kw), ost, tag, alloc, stream)
         # record planes (D >= 2) or the two row stripes of one def.  Only the guards behind the buffers are checked: rows >= M of the last quad /
         # octet, and with it the second stripe's slot past the last quad, are unspecified by the layout (include/hrx.h) (the kernels may store whole quads)
         R = 2 if D == 1 else 1
         npl, nmp = _stripe_sizes(hra, B, M, R)
         planes, raws = [], []
         for _ in range(D * R):
-            p_v, p_raw = _guarded(torch, dev, npl * 4, torch.int32)
+            p_v, p_raw = _guarded_(npl * 4, torch.int32, "plane")
             planes.append(p_v)
             raws.append(p_raw)
-        m_v, m_raw = _guarded(torch, dev, nmp * 2, torch.int16)
-        s_v, s_raw = _guarded(torch, dev, B * 8, torch.int64)
+        m_v, m_raw = _guarded_(nmp * 2, torch.int16, "masked")
+        s_v, s_raw = _guarded_(B * 8, torch.int64, "status")
         pm_input = case.seed % 2 == 0
-        src, kw = (hra.chars_to_position_major(d_chars), dict(chars_pm_stride=stride)) if pm_input else (d_chars, {})
+        src, kw = (to_pm(d_chars), dict(chars_pm_stride=stride)) if pm_input else (d_chars, {})
         form = "row stripes" if D == 1 else "record planes"
         if row.get("planes") is False:      # a multi-pass config has no one-launch planes path: the library refuses, it writes nothing
             with pytest.raises(hra.HrxError, match="record planes"):
-                cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw)
-            torch.cuda.synchronize()
+                cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw, **skw)
+            sync()
             for k, raw in enumerate(raws + [m_raw, s_raw]):
                 assert (raw == POISON).all(), "%s %s %d: written by a refused call" % (tag, form, k)
             runs_planes = False
         else:
-            cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw)
-            torch.cuda.synchronize()
+            cfg.witness_batch_planes(src, d_lens, out=(planes, m_v, s_v), **kw, **skw)
+            sync()
             runs_planes = True
         for k, raw in enumerate(raws):
             _guards_intact(raw, npl * 4, "%s %s %d" % (tag, form, k))
@@ -249,7 +270,7 @@ def launch_every_form(hra, row, case, cfg, o, ost, tag, fr=False, pitched=None):
             r1, m1 = hra.planes_to_string_major(planes, m_v, B, M, D)
             runs.append((form, s_v.cpu().numpy().view(np.uint64), r1.cpu().numpy().view(np.uint32), m1.cpu().numpy().view(np.uint16)))
         if runs_planes and fr:
-            _check_fr(hra, torch, o, cfg, case, src, d_lens, (planes, m_v, s_v), dict(position_major=True, **kw), ost, tag + " " + form)
+            _check_fr(hra, torch, o, cfg, case, src, d_lens, (planes, m_v, s_v), dict(position_major=True, **kw), ost, tag + " " + form, alloc, stream)
     return runs
 
 
@@ -298,14 +319,24 @@ def test_variant_on_edge_case_definitions(hra, oracle, row):
 _LUTS = {}
 
 
-def _check_fr(hra, torch, o, cfg, case, src, d_lens, out, kw, ost, tag):
-    """fr_columns of the launch's rows against F::from of the oracle's integer columns (tests/test_fr.py's helper), status-0 strings"""
+def lib_fr_columns(hra, D):
+    return hra.lib.hrx_fr_num_columns(D)
+
+
+def _check_fr(hra, torch, o, cfg, case, src, d_lens, out, kw, ost, tag, alloc=None, stream=None):
+    """fr_columns of the launch's rows against F::from of the oracle's integer columns (tests/test_fr.py's helper), status-0 strings
+    (alloc, stream: as launch_every_form takes them; the cells come from the allocator then)"""
     from test_fr import _expected_cells, _mont
     if "m" not in _LUTS:
         _LUTS["m"] = np.array([[(_mont(v) >> (64 * i)) & (2**64 - 1) for i in range(4)] for v in range(65536)], np.uint64)
     ok = np.nonzero((ost & np.uint64(0xff)) == 0)[0]
+    if alloc is not None:
+        kw = dict(kw, cells=alloc(lib_fr_columns(hra, case.D) * case.B * case.M * 32, torch.int64, "cells")[0])
+    if stream is not None:
+        kw = dict(kw, stream=stream)
     cells = cfg.fr_columns(src, d_lens, out, **kw)
-    torch.cuda.synchronize()
+    (torch.cuda if stream is None else stream).synchronize()
+    cells = cells.view(-1, case.B, case.M, 4)
     got = cells.cpu().numpy().view(np.uint64)
     want = _expected_cells(o, case.chars, np.minimum(case.lens, case.M), case.M, case.D, _LUTS["m"])
     assert np.array_equal(got[:, ok], want[:, ok]), tag + ": fr_columns"
