@@ -350,6 +350,215 @@ void hrx_ctx_destroy(hrx_ctx *c) {
 
 }  // extern "C"
 
+namespace {
+
+// What the caller of launch_batch handed in, as the launches below need it
+struct BatchIo {
+    const uint8_t *chars;
+    size_t stride;
+    const uint32_t *lens;
+    size_t B, M;
+    hipStream_t st;
+    uint32_t *const *planes;    // the D record planes in buffers of their own (hrx_witness_batch_device_planes), or NULL
+    size_t n_planes;
+};
+// Where one launch writes, and what it is to a multi-pass config
+struct PassOut {
+    int layout;
+    uint32_t *records;
+    uint16_t *masked;
+    uint64_t *status;
+    size_t rec_pitch, msk_pitch;
+    uint32_t rec_D = 0;                                 // > 0: a pass writing its defs' planes of a config of rec_D defs ...
+    uint32_t *summary = nullptr;                        // ... and its tile summaries, or (the last pass of a merging route):
+    uint32_t merge_G = 0;                               // the earlier groups it merges,
+    const uint32_t *const *merge_summary = nullptr;     // their summaries
+    uint32_t *merge_ov = nullptr;
+};
+
+SetImages device_images(const hrx_ctx *c) { return {c->d_table, c->d_wide, c->d_half, c->d_pairtab, c->d_bytetab, nullptr}; }
+SetImages device_images(const hrx_ctx::GroupDev &g) { return {g.d_table, g.d_wide, g.d_half, g.d_pairtab, g.d_bytetab, nullptr}; }
+SetImages class_wide_images(const DevBuf &d_cw) { SetImages im; im.cw = (const uint8_t *)d_cw.p; return im; }
+
+// Context-owned device scratch (the group counter, the chunk, group and transpose buffers) is shared by the launches of the context: a launch on
+// another stream first waits, on the host, for the stream that used it last.  what: "<which scratch> is" / "are", for the message.
+int claim_scratch(hrx_ctx *ctx, hipStream_t st, const char *what) {
+    if (ctx->scratch_used && ctx->scratch_stream != st && hipStreamSynchronize(ctx->scratch_stream) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(HRX_ERR_STATE, std::string("the context's ") + what + " in use on another stream and that stream cannot be waited for here (stream capture?): one context serves one stream / graph at a time");
+    }
+    ctx->scratch_stream = st; ctx->scratch_used = true;
+    return HRX_OK;
+}
+
+// the scout's tables (hrx_defs.cpp build_scout_tables), built and uploaded once per context
+int scout_tables_ready(hrx_ctx *ctx) {
+    if (ctx->spec_tables_ready) return HRX_OK;
+    ctx->spec_tables = build_scout_tables(ctx->s);
+    ctx->spec_cimage_bytes = 0;
+    const std::vector<uint8_t> &img = ctx->spec_tables.cimage;
+    if (!img.empty() && !std::getenv("HRX_SPEC_NO_COMPACT")) {
+        HIP_TRY(ctx->spec_cimage.reserve(img.size()));
+        HIP_TRY(hipMemcpy(ctx->spec_cimage.p, img.data(), img.size(), hipMemcpyHostToDevice));
+        ctx->spec_cimage_bytes = (uint32_t)img.size();
+    }
+    ctx->spec_tables_ready = true;
+    return HRX_OK;
+}
+
+// ---- chunked launch (hrx_kernel_spec.hip): scout + compose find every chunk's start state, the walk runs over the chunks (a.vs_*), the stitch
+// launch behind it settles what crosses the chunk borders.  Context scratch, like the group buffers.  Launches scout and compose; sp serves the stitch.
+int setup_chunks(hrx_ctx *ctx, const BatchIo &io, const DefsSet &set, const LaunchInfo &li, WitnessArgs &a, SpecArgs &sp) {
+    // the chunked launch's state (quasi-absorbing states, pair-tag tables) belongs to the WHOLE config: a group of a multi-pass config is never chunked
+    // (the planner excludes a summary / merge pass; made explicit so that a planner change cannot walk into a NULL table)
+    if (&set != &ctx->s || !ctx->s.groups.empty() || ctx->d_pair.empty()) return fail(HRX_ERR_STATE, "chunked launch planned for a group of a multi-pass config");
+    if (int rc = claim_scratch(ctx, io.st, "chunk scratch is")) return rc;
+    if (int rc = scout_tables_ready(ctx)) return rc;
+    const uint32_t C = (uint32_t)li.spec_chunks, Dn = a.D, G = li.n_groups;
+    const size_t B = io.B, Bpad = (size_t)G * 64;
+    uint32_t smax = 4;
+    for (uint32_t d = 0; d < Dn; ++d) smax = std::max<uint32_t>(smax, (uint32_t)set.defs[d].allstr.largest_state_val + 1);
+    smax = (smax + 15u) & ~15u;
+    const uint32_t row_bytes = smax + 32u;
+    HIP_TRY(ctx->spec_cls.reserve((size_t)C * Dn * Bpad * row_bytes));   // one row per (chunk, def, string)
+    HIP_TRY(ctx->spec_init.reserve((size_t)C * B * Dn * 4));
+    HIP_TRY(ctx->spec_vstatus.reserve((size_t)C * B * 8));
+    HIP_TRY(ctx->spec_vinfo.reserve((size_t)C * B * 8));
+    HIP_TRY(ctx->spec_work.reserve(16 + (size_t)C * B * 8));
+    sp.chars = io.chars; sp.stride = io.stride; sp.lens = io.lens; sp.B = (uint32_t)B; sp.M = (uint32_t)io.M; sp.D = Dn; sp.in_pm = (a.layout & HRX_LAYOUT_INPUT_POSITION_MAJOR) ? 1u : 0u;
+    sp.C = C; sp.tiles_per_chunk = (uint32_t)li.spec_tiles; sp.n_groups = G;
+    sp.table_image = a.table_image; sp.table_bytes = a.table_bytes;
+    sp.smax = smax;
+    const ScoutTables &t = ctx->spec_tables;
+    for (uint32_t d = 0; d < Dn; ++d) {
+        sp.dc[d] = set.consts[d];
+        sp.n_states[d] = (uint32_t)set.defs[d].allstr.largest_state_val + 1;
+        sp.pair_tags[d] = ctx->d_pair[d];
+        if (d < kMaxDefsPerPass) { sp.c_lut[d] = t.c_lut[d]; sp.c_tab[d] = t.c_tab[d]; sp.c_rowb[d] = t.c_rowb[d]; sp.c_inv[d] = t.c_inv[d]; }
+    }
+    std::memcpy(sp.qabs, t.qabs, sizeof sp.qabs);
+    sp.cimage = ctx->spec_cimage_bytes ? (const uint8_t *)ctx->spec_cimage.p : nullptr; sp.cimage_bytes = ctx->spec_cimage_bytes;
+    sp.rows = (uint8_t *)ctx->spec_cls.p; sp.row_bytes = row_bytes;
+#ifdef HRX_ABLATION
+    if (const char *v = std::getenv("HRX_SPEC_DBG")) sp.dbg = (uint32_t)std::strtoul(v, nullptr, 0);
+#endif
+    sp.init = (uint32_t *)ctx->spec_init.p; sp.vinfo = (const uint2 *)ctx->spec_vinfo.p; sp.vstatus = (const uint64_t *)ctx->spec_vstatus.p;
+    sp.status = a.status; sp.records = a.records; sp.masked = a.masked;
+    if (io.planes)
+        for (uint32_t d = 0; d < Dn && d < kMaxDefsPerPass; ++d) sp.rec_planes[d] = io.planes[d];
+    sp.work_count = (uint32_t *)ctx->spec_work.p; sp.work = (uint2 *)((unsigned char *)ctx->spec_work.p + 16); sp.work_cap = (uint32_t)(C * B);
+    HIP_TRY(launch_spec_scout(sp, ctx->num_cus, io.st));
+    HIP_TRY(launch_spec_compose(sp, io.st));
+    a.vs_init = sp.init; a.vs_chunks = C; a.vs_tiles = (uint32_t)li.spec_tiles; a.vs_groups = G;
+    a.vs_status = (uint64_t *)ctx->spec_vstatus.p; a.vs_info = (uint2 *)ctx->spec_vinfo.p;
+    a.n_groups = G * C;
+    return HRX_OK;
+}
+
+// dynamic group assignment: the context's counter, zeroed on the launch's stream.  Launches that share the counter must not overlap: a launch on another
+// stream waits for the previous one.
+int setup_dynamic_groups(hrx_ctx *ctx, hipStream_t st, const LaunchInfo &li, WitnessArgs &a) {
+    if (int rc = claim_scratch(ctx, st, "launch scratch is")) return rc;
+    const uint32_t slots = (uint32_t)li.grid * (uint32_t)(li.waves_per_wg / ((a.layout & 1u) && !li.half ? 3 : 2));
+    // (a kernel, not hipMemsetAsync: captured into a HIP graph, memset nodes were seen executing out of order with the kernel nodes
+    // around them — replays whose first and last launch found the counter exhausted and skipped their dynamic groups,
+    // tools/dyn_graph_debug.py)
+    HIP_TRY(launch_zero_u32(ctx->d_group_counter, st));
+    a.group_counter = ctx->d_group_counter;
+    a.group_base = 0;
+    a.group_first_dyn = slots;
+    return HRX_OK;
+}
+
+// one planned launch of the route: over ps.set (the config, or a group of it) with that set's device images
+int launch_pass(hrx_ctx *ctx, const BatchIo &io, const BatchRoute::Pass &ps, const SetImages &im, const PassOut &o) {
+    const LaunchInfo &li = ps.li;
+    WitnessArgs a = witness_args_of(*ps.set, im);
+    a.chars = io.chars; a.stride = io.stride; a.lens = io.lens; a.B = (uint32_t)io.B; a.M = (uint32_t)io.M;
+    a.layout = (uint32_t)o.layout;
+    a.records = o.records; a.masked = o.masked; a.status = o.status;
+    a.rec_pitch = (uint32_t)o.rec_pitch; a.msk_pitch = (uint32_t)o.msk_pitch;
+    a.rec_D = o.rec_D; a.rec_d0 = o.rec_D ? ps.first_def : 0u; a.summary = o.summary;
+    a.merge_G = o.merge_G; a.merge_ov = o.merge_ov;
+    for (uint32_t g = 0; g < o.merge_G && g < kMaxMergeGroups; ++g) a.merge_summary[g] = o.merge_summary[g];
+    a.debug = ps.debug;
+    a.tune = ctx->tune;
+    for (uint32_t d = 0; io.planes && d < io.n_planes && d < kMaxDefsPerLaunch; ++d) a.rec_planes[d] = (unsigned char *)io.planes[d];
+    a.rec_stripes = ps.rec_stripes;
+    apply_plan(a, li);
+    SpecArgs sp{};
+    if (li.spec_tiles)
+        if (int rc = setup_chunks(ctx, io, *ps.set, li, a, sp)) return rc;
+    if (li.dyn)
+        if (int rc = setup_dynamic_groups(ctx, io.st, li, a)) return rc;
+    a.nt_mix = plan_nt_mix(a, li);
+#if defined(HRX_STAMPS) || defined(HRX_ABLATION) || defined(HRX_NT_ENV)
+    if (const char *nm = std::getenv("HRX_NT_MIX")) a.nt_mix = (uint32_t)std::strtoul(nm, nullptr, 0);
+    if (const char *nf = std::getenv("HRX_NT_FLAGS")) a.nt_mix |= (uint32_t)std::strtoul(nf, nullptr, 0);   // (kNtMix* bits, hrx_kernel.hpp)
+#endif
+#if defined(HRX_STAMPS) || defined(HRX_ABLATION)
+    if (const char *pe = std::getenv("HRX_PACE")) a.pace_even = (uint32_t)std::strtoul(pe, nullptr, 0);
+#endif
+#ifdef HRX_STAMPS
+    if (li.kernel == Kernel::Pm || li.kernel == Kernel::Pmd) {
+        const size_t bytes = (size_t)li.grid * 8 * 16 * 8;   // 16 u64 per walker pair (8 walker + 8 finisher stamps), up to 8 pairs per workgroup
+        if (ctx->stamps.cap < bytes) { HIP_TRY(ctx->stamps.reserve(bytes)); }
+        HIP_TRY(hipMemsetAsync(ctx->stamps.p, 0, bytes, io.st));
+        a.stamps = (unsigned long long *)ctx->stamps.p;
+    }
+#endif
+    HIP_TRY(launch_witness(a, li, io.st));
+    if (li.spec_tiles) HIP_TRY(launch_spec_stitch(sp, ctx->num_cus, io.st));
+    return HRX_OK;
+}
+
+// ---- more than one pass (BatchRoute::Case::ClassWideGroups, GroupsOfThree): every group's launch with its own status array — and, by the route, its
+// tile summary (the passes write the caller's record planes themselves) or private records — then what needs ALL defs of a row: the last pass itself
+// plus witness_merge_status_kernel (merge_last), or the combine launch (hrx_kernel_mp.hip).  The group buffers belong to the context.
+int run_passes(hrx_ctx *ctx, const BatchIo &io, const BatchRoute &r, uint32_t *records, uint16_t *masked, uint64_t *status, size_t rec_pitch, size_t msk_pitch) {
+    const bool cw = r.kind == BatchRoute::Case::ClassWideGroups, summaries = cw || r.summary_mode;
+    const size_t B = io.B, M = io.M, G = r.passes.size(), q4 = (M + 3) / 4, q8 = (M + 7) / 8, ntiles = (M + 63) / 64;
+    const uint32_t D = (uint32_t)ctx->s.defs.size();
+    if (!summaries) HIP_TRY(ctx->mp_masked.reserve(q8 * 8 * B * 2));
+    if (r.merge_last) HIP_TRY(ctx->mp_ov.reserve(B * 4));
+    CombineArgs ca{};
+    for (size_t g = 0; g < G; ++g) {
+        const BatchRoute::Pass &ps = r.passes[g];
+        DevBuf &gstatus = cw ? ctx->cw_groups[g].status : ctx->groups[g].status, &gsummary = cw ? ctx->cw_groups[g].summary : ctx->groups[g].summary;
+        HIP_TRY(gstatus.reserve(B * 8));
+        PassOut o{r.layout, records, masked, (uint64_t *)gstatus.p, M, M};
+        if (summaries && r.merge_last && g + 1 == G) {
+            o.rec_D = D; o.merge_G = (uint32_t)(G - 1); o.merge_summary = ca.gsummary; o.merge_ov = (uint32_t *)ctx->mp_ov.p;
+        } else if (summaries) {
+            HIP_TRY(gsummary.reserve(ntiles * 5 * B * 16));
+            o.rec_D = D; o.summary = (uint32_t *)gsummary.p;
+            ca.gsummary[g] = o.summary;
+        } else {
+            HIP_TRY(ctx->groups[g].records.reserve(q4 * 4 * ps.set->defs.size() * B * 4));
+            o.layout = ps.layout;
+            o.records = (uint32_t *)ctx->groups[g].records.p; o.masked = (uint16_t *)ctx->mp_masked.p;
+            ca.grec[g] = o.records;
+        }
+        if (int rc = launch_pass(ctx, io, ps, cw ? class_wide_images(ctx->cw_groups[g].d_cw) : device_images(ctx->groups[g]), o)) return rc;
+        ca.gstatus[g] = (const uint64_t *)gstatus.p;
+        ca.gD[g] = (uint8_t)ps.set->defs.size();
+        ca.gfirst[g] = (uint8_t)ps.first_def;
+    }
+    ca.chars = io.chars; ca.stride = io.stride; ca.lens = io.lens; ca.B = (uint32_t)B; ca.M = (uint32_t)M;
+    ca.D = D; ca.G = (uint32_t)G; ca.layout = (uint32_t)r.layout;
+    ca.rec_pitch = (uint32_t)rec_pitch; ca.msk_pitch = (uint32_t)msk_pitch;
+    ca.records = records; ca.masked = masked; ca.status = status;
+    if (r.merge_last) {
+        ca.merge_ov = (const uint32_t *)ctx->mp_ov.p;
+        HIP_TRY(launch_merge_status(ca, io.st));
+    } else {
+        HIP_TRY(launch_combine(ca, io.st));
+    }
+    return HRX_OK;
+}
+
+}  // namespace
+
 int launch_batch(hrx_ctx *ctx, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
                  uint32_t *records, uint16_t *masked, uint64_t *status, hipStream_t st, size_t rec_pitch,
                  size_t msk_pitch, int layout, uint32_t *const *planes, size_t n_planes) {
@@ -372,388 +581,39 @@ int launch_batch(hrx_ctx *ctx, const uint8_t *chars, size_t stride, const uint32
     if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_POSITION_MAJOR &&
         layout != (HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR))
         return fail(HRX_ERR_ARG, "unknown layout");
-    // one launch over `set` (a config of up to kMaxDefsPerPass defs, or one group of a larger one) with that set's device images
-    const uint16_t *const *d_pair_tags = ctx->s.groups.empty() && !ctx->d_pair.empty() ? ctx->d_pair.data() : nullptr;
-    auto launch_set = [&](const DefsSet &set, const uint32_t *d_table, const uint64_t *d_wide, const uint16_t *d_half, const uint8_t *d_pairtab,
-                          const uint8_t *d_bytetab, int lay, uint32_t *rec, uint16_t *msk, uint64_t *stat, size_t rp, size_t mp,
-                          uint32_t rec_D = 0, uint32_t rec_d0 = 0, uint32_t *summary = nullptr,
-                          uint32_t merge_G = 0, const uint32_t *const *merge_summary = nullptr, uint32_t *merge_ov = nullptr) -> int {
-        WitnessArgs a{};
-        a.rec_D = rec_D; a.rec_d0 = rec_d0; a.summary = summary;
-        a.merge_G = merge_G; a.merge_ov = merge_ov;
-        for (uint32_t g = 0; g < merge_G && g < kMaxMergeGroups; ++g) a.merge_summary[g] = merge_summary[g];
-        const bool pass = summary != nullptr || merge_G != 0;    // a pass of a multi-pass config
-        a.rec_pitch = (uint32_t)rp; a.msk_pitch = (uint32_t)mp;
-        a.layout = (uint32_t)lay;
-        a.chars = chars; a.stride = stride; a.lens = lens; a.B = (uint32_t)B; a.M = (uint32_t)M;
-        a.records = rec; a.masked = msk; a.status = stat;
-        a.table_image = d_table; a.table_bytes = (uint32_t)(set.table_image.size() * 4);
-        a.wide_image = d_wide;
-        a.half_image = d_half; a.half_bytes = (uint32_t)(set.half_image.size() * 2);
-        a.pair_image = d_pairtab; a.pair_bytes = set.pair.bytes; a.pair_classes = set.pair.n_classes;
-        a.pair_blk_bytes = set.pair.blk_bytes; a.pair_lut_off = set.pair.lut_off;
-        a.byte_image = d_bytetab; a.byte_bytes = set.byte.bytes; a.byte_ptab_off = set.byte.ptab_off; a.byte_mul_a4 = set.byte.mul_a * 4; a.byte_mul_b4 = set.byte.mul_b * 4; a.byte_slot_mask4 = (set.byte.slots - 1u) * 4u;
-        a.byte_dead = set.byte.dead;
-        a.byte_rows_bytes = set.byte.n_rows * 256u; a.byte16_bytes = set.byte.bytes16; a.byte16_ptab_off = set.byte.ptab16_off;
-        a.byte_one_id = (set.defs.size() == 1 && set.defs[0].substrs.size() == 1 && set.consts[0].substr_id_offset >= 1 && set.consts[0].substr_id_offset <= 63) ? set.consts[0].substr_id_offset : 0u;
-        a.D = (uint32_t)set.defs.size();
-        a.debug = ctx->debug;
-        a.tune = ctx->tune;
 #ifdef HRX_ABLATION
-        a.debug = debug_flags_from_env();   // tools/ab_flags.py switches ablations between launches of one process
+    const uint32_t debug = debug_flags_from_env();   // tools/ab_flags.py switches ablations between launches of one process
+#else
+    const uint32_t debug = ctx->debug;
 #endif
-        if (planes) {
-            for (uint32_t d = 0; d < n_planes && d < kMaxDefsPerLaunch; ++d) a.rec_planes[d] = (unsigned char *)planes[d];
-            if (n_planes == 2 * (size_t)a.D) {      // one def in two row stripes: the loader / walker / finisher kernel writes them (not the pair-step kernel, and not in chunks:
-                a.rec_stripes = 2;                  // a chunk's first tile is not a stripe boundary in general, and the chunked launch's repair reads whole planes)
-                a.debug |= kDbgNoPair | kDbgNoSpec;
-            }
-        }
-        // a summary-writing pass is the loader / walker / finisher kernel: no pair-step or def-parallel variant, no HALF table
-        if (pass) a.debug |= kDbgNoPair | kDbgNoDefParallel;
-        for (uint32_t d = 0; d < a.D && d < kMaxDefsPerLaunch; ++d) a.dc[d] = set.consts[d];
-        LaunchInfo li;
-        if (!plan_witness_launch(a, ctx->num_cus, li)) return fail(HRX_ERR_BOUNDS, "tables + staging do not fit the 160 KiB LDS");
-        if (pass && li.half) {   // (a group of one big DFA: walk its 4-byte table out of L2 instead)
-            a.debug |= kDbgForceGlobalTable;
-            if (!plan_witness_launch(a, ctx->num_cus, li)) return fail(HRX_ERR_BOUNDS, "tables + staging do not fit the 160 KiB LDS");
-        }
-        if (pass && li.split != 2) return fail(HRX_ERR_STATE, "multi-pass: the planner did not pick the position-major loader/walker kernel");
-        SpecArgs sp{};
-        if (li.spec_tiles) {
-            // the chunked launch's state (quasi-absorbing states, pair-tag tables) belongs to the WHOLE config: a group of a multi-pass config is never chunked
-            // (today because a summary / merge pass is excluded by the planner; made explicit so that a planner change cannot walk into a NULL table)
-            if (&set != &ctx->s || !d_pair_tags) return fail(HRX_ERR_STATE, "chunked launch planned for a group of a multi-pass config");
-            // ---- chunked launch (hrx_kernel_spec.hip): scout + compose find every chunk's start state, the walk below runs over the
-            // chunks, the stitch launch behind it settles what crosses the chunk borders.  Context scratch, like the group buffers.
-            if (ctx->scratch_used && ctx->scratch_stream != st && hipStreamSynchronize(ctx->scratch_stream) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(HRX_ERR_STATE, "the context's chunk scratch is in use on another stream and that stream cannot be waited for here (stream capture?): one context serves one stream / graph at a time");
-            }
-            ctx->scratch_stream = st; ctx->scratch_used = true;
-            const uint32_t C = (uint32_t)li.spec_chunks, Dn = a.D, G = a.n_groups;
-            const size_t Bpad = (size_t)G * 64;
-            uint32_t smax = 4;
-            for (uint32_t d = 0; d < Dn; ++d) smax = std::max<uint32_t>(smax, (uint32_t)set.defs[d].allstr.largest_state_val + 1);
-            smax = (smax + 15u) & ~15u;
-            const uint32_t row_bytes = smax + 32u;
-            HIP_TRY(ctx->spec_cls.reserve((size_t)C * Dn * Bpad * row_bytes));   // one row per (chunk, def, string)
-            HIP_TRY(ctx->spec_init.reserve((size_t)C * B * Dn * 4));
-            HIP_TRY(ctx->spec_vstatus.reserve((size_t)C * B * 8));
-            HIP_TRY(ctx->spec_vinfo.reserve((size_t)C * B * 8));
-            HIP_TRY(ctx->spec_work.reserve(16 + (size_t)C * B * 8));
-            sp.chars = chars; sp.stride = stride; sp.lens = lens; sp.B = (uint32_t)B; sp.M = (uint32_t)M; sp.D = Dn; sp.in_pm = (lay & HRX_LAYOUT_INPUT_POSITION_MAJOR) ? 1u : 0u;
-            sp.C = C; sp.tiles_per_chunk = (uint32_t)li.spec_tiles; sp.n_groups = G;
-            sp.table_image = d_table; sp.table_bytes = a.table_bytes;
-            sp.smax = smax;
-            for (uint32_t d = 0; d < Dn; ++d) {
-                sp.dc[d] = set.consts[d];
-                sp.n_states[d] = (uint32_t)set.defs[d].allstr.largest_state_val + 1;
-                sp.pair_tags[d] = d_pair_tags ? d_pair_tags[d] : nullptr;
-            }
-            if (!ctx->spec_qabs_ready) {     // quasi-absorbing states (hrx_kernel_spec.hip), once per context: from the defs' dense tables
-                std::memset(ctx->spec_qabs, 0, sizeof ctx->spec_qabs);
-                for (uint32_t d = 0; d < Dn; ++d) {
-                    const uint32_t S = sp.n_states[d], *T = set.table_image.data() + (size_t)set.consts[d].row_base * 256;
-                    bool undefined_everywhere[256];
-                    for (uint32_t c = 0; c < 256; ++c) {
-                        undefined_everywhere[c] = true;
-                        for (uint32_t t = 0; t < S && undefined_everywhere[c]; ++t) undefined_everywhere[c] = T[(size_t)t * 256 + c] >= set.consts[d].dead_entry;
-                    }
-                    for (uint32_t t = 0; t < S && t < 256; ++t) {
-                        bool q = true;
-                        for (uint32_t c = 0; c < 256 && q; ++c) {
-                            const uint32_t e = T[(size_t)t * 256 + c];
-                            q = e >= set.consts[d].dead_entry ? undefined_everywhere[c] : (e >> kNextShift) - set.consts[d].row_base == t;
-                        }
-                        if (q) ctx->spec_qabs[d][t >> 5] |= 1u << (t & 31);
-                    }
-                }
-                // ---- the scout's compact tables: per def, bytes with the same column in every row (real states, dummy row, dead row) are one CLASS
-                std::vector<uint8_t> img;
-                bool compact = true;
-                for (uint32_t d = 0; d < Dn && compact; ++d) {
-                    const uint32_t S = sp.n_states[d], R = S + 2u, base = set.consts[d].row_base;
-                    const uint32_t *T = set.table_image.data() + (size_t)base * 256;
-                    auto rel = [&](uint32_t r, uint32_t c) { const uint32_t e = T[(size_t)r * 256 + c]; const uint32_t x = (e >> kNextShift) - base; return e >= set.consts[d].dead_entry || x > S + 1u ? S + 1u : x; };
-                    std::map<std::vector<uint16_t>, uint32_t> cls_of;
-                    std::vector<std::vector<uint16_t>> cols;
-                    uint8_t lut[256];
-                    for (uint32_t c = 0; c < 256 && compact; ++c) {
-                        std::vector<uint16_t> col(R);
-                        for (uint32_t r = 0; r < R; ++r) col[r] = (uint16_t)rel(r, c);
-                        auto it = cls_of.find(col);
-                        if (it == cls_of.end()) {
-                            if (cols.size() >= 127) { compact = false; break; }
-                            it = cls_of.emplace(col, (uint32_t)cols.size()).first;
-                            cols.push_back(col);
-                        }
-                        lut[c] = (uint8_t)(it->second * 2u);
-                    }
-                    if (!compact) break;
-                    const uint32_t Cn = (uint32_t)cols.size(), rowb = Cn * 2u;
-                    const uint32_t lut_off = (uint32_t)img.size();
-                    img.insert(img.end(), lut, lut + 256);
-                    const uint32_t tab_off = (uint32_t)img.size();
-                    if ((size_t)tab_off + (size_t)R * rowb > 0xfff0u) { compact = false; break; }      // row addresses are u16
-                    img.resize((size_t)tab_off + (((size_t)R * rowb + 15) & ~(size_t)15), 0);
-                    for (uint32_t r = 0; r < R; ++r)
-                        for (uint32_t k = 0; k < Cn; ++k) {
-                            const uint16_t addr = (uint16_t)(tab_off + (uint32_t)cols[k][r] * rowb);
-                            std::memcpy(&img[(size_t)tab_off + (size_t)r * rowb + 2u * k], &addr, 2);
-                        }
-                    ctx->spec_c_lut[d] = lut_off; ctx->spec_c_tab[d] = tab_off; ctx->spec_c_rowb[d] = rowb; ctx->spec_c_inv[d] = (65536u + rowb - 1u) / rowb;
-                }
-                ctx->spec_cimage_bytes = 0;
-                if (compact && !img.empty() && !std::getenv("HRX_SPEC_NO_COMPACT")) {
-                    HIP_TRY(ctx->spec_cimage.reserve(img.size()));
-                    HIP_TRY(hipMemcpy(ctx->spec_cimage.p, img.data(), img.size(), hipMemcpyHostToDevice));       // (once per context, like the allocations above)
-                    ctx->spec_cimage_bytes = (uint32_t)img.size();
-                }
-                ctx->spec_qabs_ready = true;
-            }
-            std::memcpy(sp.qabs, ctx->spec_qabs, sizeof sp.qabs);
-            sp.cimage = ctx->spec_cimage_bytes ? (const uint8_t *)ctx->spec_cimage.p : nullptr; sp.cimage_bytes = ctx->spec_cimage_bytes;
-            for (uint32_t d = 0; d < Dn && d < kMaxDefsPerPass; ++d) { sp.c_lut[d] = ctx->spec_c_lut[d]; sp.c_tab[d] = ctx->spec_c_tab[d]; sp.c_rowb[d] = ctx->spec_c_rowb[d]; sp.c_inv[d] = ctx->spec_c_inv[d]; }
-            sp.rows = (uint8_t *)ctx->spec_cls.p; sp.row_bytes = row_bytes;
-#ifdef HRX_ABLATION
-            if (const char *v = std::getenv("HRX_SPEC_DBG")) sp.dbg = (uint32_t)std::strtoul(v, nullptr, 0);
-#endif
-            sp.init = (uint32_t *)ctx->spec_init.p; sp.vinfo = (const uint2 *)ctx->spec_vinfo.p; sp.vstatus = (const uint64_t *)ctx->spec_vstatus.p;
-            sp.status = stat; sp.records = rec; sp.masked = msk;
-            if (planes)
-                for (uint32_t d = 0; d < Dn && d < kMaxDefsPerPass; ++d) sp.rec_planes[d] = planes[d];
-            sp.work_count = (uint32_t *)ctx->spec_work.p; sp.work = (uint2 *)((unsigned char *)ctx->spec_work.p + 16); sp.work_cap = (uint32_t)(C * B);
-            HIP_TRY(launch_spec_scout(sp, ctx->num_cus, st));
-            HIP_TRY(launch_spec_compose(sp, st));
-            a.vs_init = sp.init; a.vs_chunks = C; a.vs_tiles = (uint32_t)li.spec_tiles; a.vs_groups = G;
-            a.vs_status = (uint64_t *)ctx->spec_vstatus.p; a.vs_info = (uint2 *)ctx->spec_vinfo.p;
-            a.n_groups = G * C;
-        }
-        if (li.dyn) {   // launches that share the counter must not overlap: a launch on another stream waits for the previous one
-            if (ctx->scratch_used && ctx->scratch_stream != st && hipStreamSynchronize(ctx->scratch_stream) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(HRX_ERR_STATE, "the context's launch scratch is in use on another stream and that stream cannot be waited for here (stream capture?): one context serves one stream / graph at a time");
-            }
-            ctx->scratch_stream = st; ctx->scratch_used = true;
-            const uint32_t slots = (uint32_t)li.grid * (uint32_t)(li.waves_per_wg / ((a.layout & 1u) && !li.half ? 3 : 2));
-            // (a kernel, not hipMemsetAsync: captured into a HIP graph, memset nodes were seen executing out of order with the kernel nodes
-            // around them — replays whose first and last launch found the counter exhausted and skipped their dynamic groups,
-            // tools/dyn_graph_debug.py)
-            HIP_TRY(launch_zero_u32(ctx->d_group_counter, st));
-            a.group_counter = ctx->d_group_counter;
-            a.group_base = 0;
-            a.group_first_dyn = slots;
-        }
-        a.nt_mix = plan_nt_mix(a, li);
-#if defined(HRX_STAMPS) || defined(HRX_ABLATION) || defined(HRX_NT_ENV)
-        if (const char *nm = std::getenv("HRX_NT_MIX")) a.nt_mix = (uint32_t)std::strtoul(nm, nullptr, 0);
-        if (const char *nf = std::getenv("HRX_NT_FLAGS")) a.nt_mix |= (uint32_t)std::strtoul(nf, nullptr, 0);   // (kNtMix* bits, hrx_kernel.hpp)
-#endif
-#if defined(HRX_STAMPS) || defined(HRX_ABLATION)
-        if (const char *pe = std::getenv("HRX_PACE")) a.pace_even = (uint32_t)std::strtoul(pe, nullptr, 0);
-#endif
-#ifdef HRX_STAMPS
-        if (li.split == 2 || li.split == 5) {
-            const size_t bytes = (size_t)li.grid * 8 * 16 * 8;   // 16 u64 per walker pair (8 walker + 8 finisher stamps), up to 8 pairs per workgroup
-            if (ctx->stamps.cap < bytes) { HIP_TRY(ctx->stamps.reserve(bytes)); }
-            HIP_TRY(hipMemsetAsync(ctx->stamps.p, 0, bytes, st));
-            a.stamps = (unsigned long long *)ctx->stamps.p;
-        }
-#endif
-        HIP_TRY(launch_witness(a, li, st));
-        if (li.spec_tiles) {
-            HIP_TRY(launch_spec_stitch(sp, ctx->num_cus, st));
-        }
-        return HRX_OK;
-    };
-    if (planes && !ctx->s.groups.empty() && !(ctx->d_cw.p && !ctx->mp_combine))
-        return fail(HRX_ERR_ARG, "record planes: configs that run as one launch (up to three defs, or four to eight defs of at most 32 byte classes each)");
-    if (ctx->s.groups.empty()) {
-        // string-major outputs of a DFA whose 4-byte table does not fit LDS (cfg 5): the string-major kernels would walk it out of global
-        // memory (0.21 of peak); the BYTE / HALF table kernels are position-major — run them into context scratch and turn the rows around
-        // (one def with a BYTE image has a string-major kernel of its own: the walker/storer kernel on that table)
-        const bool byte_split = !ctx->s.byte.image.empty() && !(ctx->debug & (kDbgNoByte | kDbgForceHalf));
-        if (layout == HRX_LAYOUT_STRING_MAJOR && M % 8 == 0 && !byte_split &&
-            (!ctx->s.byte.image.empty() || !ctx->s.half_image.empty()) && ctx->s.table_image.size() * 4 + wave_stage_bytes((int)ctx->s.defs.size(), 16) > kLdsLimit) {
-            if (ctx->scratch_used && ctx->scratch_stream != st && hipStreamSynchronize(ctx->scratch_stream) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(HRX_ERR_STATE, "the context's transpose scratch is in use on another stream and that stream cannot be waited for here (stream capture?): one context serves one stream / graph at a time");
-            }
-            ctx->scratch_stream = st; ctx->scratch_used = true;
-            const size_t q4 = (M + 3) / 4, q8 = (M + 7) / 8, D = ctx->s.defs.size();
-            HIP_TRY(ctx->tp_records.reserve(q4 * 4 * D * B * 4));
-            HIP_TRY(ctx->tp_masked.reserve(q8 * 8 * B * 2));
-            const int rc = launch_set(ctx->s, ctx->d_table, ctx->d_wide, ctx->d_half, ctx->d_pairtab, ctx->d_bytetab, HRX_LAYOUT_POSITION_MAJOR,
-                                      (uint32_t *)ctx->tp_records.p, (uint16_t *)ctx->tp_masked.p, status, M, M);
-            if (rc != HRX_OK) return rc;
-            TransposeArgs ta{(const uint32_t *)ctx->tp_records.p, (const uint16_t *)ctx->tp_masked.p, (uint32_t)B, (uint32_t)M, (uint32_t)D, records, masked, (uint32_t)rec_pitch, (uint32_t)msk_pitch};
-            HIP_TRY(launch_transpose(ta, st));
-            return HRX_OK;
-        }
-        return launch_set(ctx->s, ctx->d_table, ctx->d_wide, ctx->d_half, ctx->d_pairtab, ctx->d_bytetab, layout, records, masked, status, rec_pitch, msk_pitch);
+    BatchRoute route;
+    std::string err;
+    if (int rc = plan_batch_route(ctx->s, debug, ctx->tune, ctx->mp_combine, layout, B, M, rec_pitch, ctx->num_cus, planes ? n_planes : 0, true, route, err)) return fail(rc, err);
+    const BatchIo io{chars, stride, lens, B, M, st, planes, n_planes};
+    const bool grouped = !ctx->s.groups.empty();
+    // the group buffers and the transposer's scratch belong to the context: a launch on another stream first waits for the previous call
+    if (grouped || route.transpose)
+        if (int rc = claim_scratch(ctx, st, grouped ? "group buffers are" : "transpose scratch is")) return rc;
+    uint32_t *rec = records;
+    uint16_t *msk = masked;
+    if (route.transpose) {      // the launches write position-major rows into context scratch, transpose_pm_to_sm_kernel turns them around (hrx_kernel_tp.hip)
+        HIP_TRY(ctx->tp_records.reserve((M + 3) / 4 * 4 * ctx->s.defs.size() * B * 4));
+        HIP_TRY(ctx->tp_masked.reserve((M + 7) / 8 * 8 * B * 2));
+        rec = (uint32_t *)ctx->tp_records.p; msk = (uint16_t *)ctx->tp_masked.p;
     }
-    // ---- more than kMaxDefsPerPass defs: one ordinary launch per group into its private position-major buffers, then the
-    // combine kernel (hrx_kernel_mp.hip) writes the caller's buffers.  The group buffers belong to the context: a launch
-    // on another stream first waits for the previous combine.
-    const size_t G = ctx->s.groups.size();
-    if (G > kMaxGroups) return fail(HRX_ERR_BOUNDS, "too many def groups");
-    if (ctx->scratch_used && ctx->scratch_stream != st && hipStreamSynchronize(ctx->scratch_stream) != hipSuccess) {
-        (void)hipGetLastError();
-        return fail(HRX_ERR_STATE, "the context's group buffers are in use on another stream and that stream cannot be waited for here (stream capture?): one context serves one stream / graph at a time");
+    const bool pm_rows = (route.layout & HRX_LAYOUT_POSITION_MAJOR) != 0;
+    const PassOut whole{route.layout, rec, msk, status, pm_rows ? M : rec_pitch, pm_rows ? M : msk_pitch};
+    int rc = HRX_OK;
+    switch (route.kind) {
+        case BatchRoute::Case::OneLaunch: rc = launch_pass(ctx, io, route.passes[0], device_images(ctx), whole); break;
+        case BatchRoute::Case::ClassWide:
+        case BatchRoute::Case::ClassWideSm: rc = launch_pass(ctx, io, route.passes[0], class_wide_images(ctx->d_cw), whole); break;
+        case BatchRoute::Case::ClassWideGroups:
+        case BatchRoute::Case::GroupsOfThree: rc = run_passes(ctx, io, route, rec, msk, status, rec_pitch, msk_pitch); break;
     }
-    ctx->scratch_stream = st; ctx->scratch_used = true;
-    const size_t q4 = (M + 3) / 4, q8 = (M + 7) / 8, ntiles = (M + 63) / 64;
-    // string-major outputs (rows in multiples of 8): the passes and the combine run position-major into context scratch and
-    // transpose_pm_to_sm_kernel turns the rows around (hrx_kernel_tp.hip: 3.7 -> ~1 ms at D = 5, 65536 x 1024 rows); other row counts keep the
-    // copy-mode combine (per-lane 4-byte stores)
-    // ---- four and five defs, string-major outputs, rows in multiples of 16: the def-parallel launch writes the caller's [B][pitch][D] records and [B][pitch] masked rows itself — its walkers'
-    // quads meet in LDS sub-tiles, a storer wave writes each string's 16 rows x D records as one run (hrx_kernel_pmd.hip SMO) — instead of position-major scratch + the transposer
-    if (layout == HRX_LAYOUT_STRING_MAJOR && ctx->d_cw.p && !ctx->mp_combine) {
-        WitnessArgs a{};
-        a.layout = (uint32_t)layout; a.chars = chars; a.stride = stride; a.lens = lens; a.B = (uint32_t)B; a.M = (uint32_t)M;
-        a.rec_pitch = (uint32_t)rec_pitch; a.msk_pitch = (uint32_t)msk_pitch;
-        a.records = records; a.masked = masked; a.status = status;
-        a.D = (uint32_t)ctx->s.defs.size();
-        a.debug = ctx->debug;
-        a.cw_image = (const uint8_t *)ctx->d_cw.p; a.cw_lut_off = ctx->s.cw_lut_off; a.table_bytes = (uint32_t)ctx->s.cw_image.size();
-        for (uint32_t d = 0; d < a.D && d < kMaxDefsPerLaunch; ++d) a.dc[d] = ctx->s.cw_consts[d];
-        LaunchInfo li{};
-        if (plan_pmd_cw_sm(a, ctx->num_cus, li)) {
-            a.nt_mix = plan_nt_mix(a, li);
-            HIP_TRY(launch_witness(a, li, st));
-            return HRX_OK;
-        }
-    }
-    const bool via_tp = !(layout & HRX_LAYOUT_POSITION_MAJOR) && M % 8 == 0;
-    uint32_t *const caller_records = records;
-    uint16_t *const caller_masked = masked;
-    if (via_tp) {
-        HIP_TRY(ctx->tp_records.reserve(q4 * 4 * ctx->s.defs.size() * B * 4));
-        HIP_TRY(ctx->tp_masked.reserve(q8 * 8 * B * 2));
-        records = (uint32_t *)ctx->tp_records.p; masked = (uint16_t *)ctx->tp_masked.p;
-        layout = HRX_LAYOUT_POSITION_MAJOR | (layout & HRX_LAYOUT_INPUT_POSITION_MAJOR);
-    }
-    // ---- 6 or 7 defs whose CLASS-WIDE tables exist (every def <= 32 byte classes; 4 and 5 when forced): ONE def-parallel launch walks all defs — one walker wave per def, the last one combining
-    // (hrx_kernel_pmd.hip CW) — instead of passes over groups of three with summaries in between: no second read of the input, no 80-byte tile summaries written and read back
-    if ((layout & HRX_LAYOUT_POSITION_MAJOR) && ctx->d_cw.p && !ctx->mp_combine) {
-        WitnessArgs a{};
-        a.layout = (uint32_t)layout; a.chars = chars; a.stride = stride; a.lens = lens; a.B = (uint32_t)B; a.M = (uint32_t)M;
-        a.rec_pitch = (uint32_t)M; a.msk_pitch = (uint32_t)M;
-        a.records = records; a.masked = masked; a.status = status;
-        a.D = (uint32_t)ctx->s.defs.size();
-        a.debug = ctx->debug;
-        a.cw_image = (const uint8_t *)ctx->d_cw.p; a.cw_lut_off = ctx->s.cw_lut_off; a.table_bytes = (uint32_t)ctx->s.cw_image.size();
-        for (uint32_t d = 0; d < a.D && d < kMaxDefsPerLaunch; ++d) a.dc[d] = ctx->s.cw_consts[d];
-        if (planes)
-            for (uint32_t d = 0; d < a.D && d < kMaxDefsPerLaunch; ++d) a.rec_planes[d] = (unsigned char *)planes[d];
-        LaunchInfo li{};
-        if (plan_pmd_cw(a, ctx->num_cus, li)) {
-            a.nt_mix = plan_nt_mix(a, li);
-            HIP_TRY(launch_witness(a, li, st));
-            if (via_tp) {
-                TransposeArgs ta{records, masked, (uint32_t)B, (uint32_t)M, (uint32_t)ctx->s.defs.size(), caller_records, caller_masked, (uint32_t)rec_pitch, (uint32_t)msk_pitch};
-                HIP_TRY(launch_transpose(ta, st));
-            }
-            return HRX_OK;
-        }
-    }
-    if (planes) return fail(HRX_ERR_BOUNDS, "record planes: the one-launch def-parallel path does not fit this config");
-    // ---- more than eight defs, every def of at most 32 byte classes: passes over CW GROUPS of 4 .. 8 defs (DefsSet::cw_groups), each ONE def-parallel launch that writes its defs' planes of the
-    // caller's records and a tile summary; the combine launch forms what needs all defs of a row.  D = 16: two passes instead of six, D = 32: four instead of eleven.
-    if ((layout & HRX_LAYOUT_POSITION_MAJOR) && !ctx->cw_groups.empty() && !(ctx->debug & kDbgNoDefParallel)) {
-        const size_t GC = ctx->cw_groups.size();
-        CombineArgs cc{};
-        bool planned = true;
-        std::vector<LaunchInfo> lis(GC);
-        std::vector<WitnessArgs> was(GC);
-        for (size_t g = 0; g < GC && planned; ++g) {
-            const DefsSet &gs = ctx->s.cw_groups[g];
-            WitnessArgs &a = was[g];
-            a = WitnessArgs{};
-            a.layout = (uint32_t)layout; a.chars = chars; a.stride = stride; a.lens = lens; a.B = (uint32_t)B; a.M = (uint32_t)M;
-            a.rec_pitch = (uint32_t)M; a.msk_pitch = (uint32_t)M;
-            a.records = records; a.masked = masked;
-            a.D = (uint32_t)gs.defs.size();
-            a.rec_D = (uint32_t)ctx->s.defs.size(); a.rec_d0 = ctx->s.cw_group_first[g];
-            a.debug = ctx->debug;
-            a.cw_image = (const uint8_t *)ctx->cw_groups[g].d_cw.p; a.cw_lut_off = gs.cw_lut_off; a.table_bytes = (uint32_t)gs.cw_image.size();
-            for (uint32_t d = 0; d < a.D && d < kMaxDefsPerLaunch; ++d) a.dc[d] = gs.cw_consts[d];
-            planned = plan_pmd_cw(a, ctx->num_cus, lis[g]);
-        }
-        if (planned) {
-            for (size_t g = 0; g < GC; ++g) {
-                hrx_ctx::CwGroupDev &gd = ctx->cw_groups[g];
-                HIP_TRY(gd.status.reserve(B * 8));
-                HIP_TRY(gd.summary.reserve(ntiles * 5 * B * 16));
-                was[g].status = (uint64_t *)gd.status.p;
-                was[g].summary = (uint32_t *)gd.summary.p;
-                was[g].nt_mix = plan_nt_mix(was[g], lis[g]);
-                HIP_TRY(launch_witness(was[g], lis[g], st));
-                cc.gsummary[g] = (const uint32_t *)gd.summary.p;
-                cc.gstatus[g] = (const uint64_t *)gd.status.p;
-                cc.gD[g] = (uint8_t)ctx->s.cw_groups[g].defs.size();
-                cc.gfirst[g] = (uint8_t)ctx->s.cw_group_first[g];
-            }
-            cc.chars = chars; cc.stride = stride; cc.lens = lens; cc.B = (uint32_t)B; cc.M = (uint32_t)M;
-            cc.D = (uint32_t)ctx->s.defs.size(); cc.G = (uint32_t)GC; cc.layout = (uint32_t)layout;
-            cc.rec_pitch = (uint32_t)rec_pitch; cc.msk_pitch = (uint32_t)msk_pitch;
-            cc.records = records; cc.masked = masked; cc.status = status;
-            HIP_TRY(launch_combine(cc, st));
-            if (via_tp) {
-                TransposeArgs ta{records, masked, (uint32_t)B, (uint32_t)M, (uint32_t)ctx->s.defs.size(), caller_records, caller_masked, (uint32_t)rec_pitch, (uint32_t)msk_pitch};
-                HIP_TRY(launch_transpose(ta, st));
-            }
-            return HRX_OK;
-        }
-    }
-    const bool summary_mode = (layout & HRX_LAYOUT_POSITION_MAJOR) != 0;   // position-major outputs: the passes write the caller's record planes themselves
-    if (!summary_mode) HIP_TRY(ctx->mp_masked.reserve(q8 * 8 * B * 2));
-    // position-major outputs, up to kMaxMergeGroups + 1 groups: the LAST pass reads the earlier groups' summaries itself and writes the final
-    // masked rows; a one-thread-per-string launch merges the status words.  (HRX_MP_COMBINE=1: the separate combine launch, as with more groups.)
-    const bool merge_last = summary_mode && G - 1 <= kMaxMergeGroups && !ctx->mp_combine;
-    if (merge_last) HIP_TRY(ctx->mp_ov.reserve(B * 4));
-    CombineArgs ca{};
-    for (size_t g = 0; g < G; ++g) {
-        const DefsSet &gs = ctx->s.groups[g];
-        hrx_ctx::GroupDev &gd = ctx->groups[g];
-        HIP_TRY(gd.status.reserve(B * 8));
-        int rc;
-        if (summary_mode && merge_last && g + 1 == G) {
-            const uint32_t *ms[kMaxMergeGroups] = {nullptr, nullptr, nullptr};
-            for (size_t e = 0; e + 1 < G; ++e) ms[e] = ca.gsummary[e];
-            rc = launch_set(gs, gd.d_table, gd.d_wide, gd.d_half, gd.d_pairtab, gd.d_bytetab, layout, records, masked, (uint64_t *)gd.status.p, M, M,
-                            (uint32_t)ctx->s.defs.size(), ctx->s.group_first[g], nullptr, (uint32_t)(G - 1), ms, (uint32_t *)ctx->mp_ov.p);
-        } else if (summary_mode) {
-            HIP_TRY(gd.summary.reserve(ntiles * 5 * B * 16));
-            rc = launch_set(gs, gd.d_table, gd.d_wide, gd.d_half, gd.d_pairtab, gd.d_bytetab, layout, records, masked, (uint64_t *)gd.status.p, M, M,
-                            (uint32_t)ctx->s.defs.size(), ctx->s.group_first[g], (uint32_t *)gd.summary.p);
-            ca.gsummary[g] = (const uint32_t *)gd.summary.p;
-        } else {
-            HIP_TRY(gd.records.reserve(q4 * 4 * gs.defs.size() * B * 4));
-            rc = launch_set(gs, gd.d_table, gd.d_wide, gd.d_half, gd.d_pairtab, gd.d_bytetab, HRX_LAYOUT_POSITION_MAJOR | (layout & HRX_LAYOUT_INPUT_POSITION_MAJOR),
-                            (uint32_t *)gd.records.p, (uint16_t *)ctx->mp_masked.p, (uint64_t *)gd.status.p, M, M);
-            ca.grec[g] = (const uint32_t *)gd.records.p;
-        }
-        if (rc != HRX_OK) return rc;
-        ca.gstatus[g] = (const uint64_t *)gd.status.p;
-        ca.gD[g] = (uint8_t)gs.defs.size();
-        ca.gfirst[g] = (uint8_t)ctx->s.group_first[g];
-    }
-    ca.chars = chars; ca.stride = stride; ca.lens = lens; ca.B = (uint32_t)B; ca.M = (uint32_t)M;
-    ca.D = (uint32_t)ctx->s.defs.size(); ca.G = (uint32_t)G; ca.layout = (uint32_t)layout;
-    ca.rec_pitch = (uint32_t)rec_pitch; ca.msk_pitch = (uint32_t)msk_pitch;
-    ca.records = records; ca.masked = masked; ca.status = status;
-    if (merge_last) {
-        ca.merge_ov = (const uint32_t *)ctx->mp_ov.p;
-        HIP_TRY(launch_merge_status(ca, st));
-    } else {
-        HIP_TRY(launch_combine(ca, st));
-    }
-    if (via_tp) {
-        TransposeArgs ta{records, masked, (uint32_t)B, (uint32_t)M, (uint32_t)ctx->s.defs.size(), caller_records, caller_masked, (uint32_t)rec_pitch, (uint32_t)msk_pitch};
-        HIP_TRY(launch_transpose(ta, st));
-    }
+    if (rc != HRX_OK || !route.transpose) return rc;
+    TransposeArgs ta{rec, msk, (uint32_t)B, (uint32_t)M, (uint32_t)ctx->s.defs.size(), records, masked, (uint32_t)rec_pitch, (uint32_t)msk_pitch};
+    HIP_TRY(launch_transpose(ta, st));
     return HRX_OK;
 }
 

@@ -20,7 +20,7 @@
 #include "../../include/hrx.h"
 #include "hrx_defs.hpp"
 #include "hrx_error.hpp"
-#include "hrx_kernel.hpp"
+#include "hrx_plan.hpp"
 
 #define HRX_INTERNAL __attribute__((visibility("hidden")))
 
@@ -120,10 +120,12 @@ struct hrx_ctx {
     bool mp_combine = false;   // HRX_MP_COMBINE=1: always the separate combine launch
     DevBuf tp_records, tp_masked;   // string-major callers served by the position-major path + transpose_pm_to_sm_kernel (hrx_kernel_tp.hip)
     DevBuf spec_cls, spec_ends, spec_fail, spec_init, spec_vstatus, spec_vinfo, spec_work;
-    bool spec_qabs_ready = false;
-    DevBuf spec_cimage;            // the scout's compact tables (class LUTs + class-indexed u16 tables), built with spec_qabs
-    uint32_t spec_cimage_bytes = 0, spec_c_lut[hrx::kMaxDefsPerPass] = {}, spec_c_tab[hrx::kMaxDefsPerPass] = {}, spec_c_rowb[hrx::kMaxDefsPerPass] = {}, spec_c_inv[hrx::kMaxDefsPerPass] = {};
-    uint32_t spec_qabs[hrx::kMaxDefsPerPass][8];   // chunked launches (hrx_kernel_spec.hip)
+    // chunked launches (hrx_kernel_spec.hip): the scout's tables (hrx_defs.cpp build_scout_tables), built at the first chunked launch, and the device copy of
+    // their compact image (spec_cimage_bytes == 0: none, or HRX_SPEC_NO_COMPACT — the scout walks the narrow table)
+    bool spec_tables_ready = false;
+    hrx::ScoutTables spec_tables;
+    DevBuf spec_cimage;
+    uint32_t spec_cimage_bytes = 0;
     // dynamic group assignment (hrx_kernel_pm.hip): a device counter, zeroed on the launch's stream right before the launch
     // (a memset node when the launches are captured into a HIP graph: replay-safe)
     uint32_t *d_group_counter = nullptr;

@@ -491,4 +491,70 @@ size_t table_endpoint_rows(const DefsSet &s, size_t d, uint64_t *rows, size_t ca
     return k;
 }
 
+// The chunked launch's scout (hrx_kernel_spec.hip), from the defs' dense tables.
+// Quasi-absorbing states: bit s of def d is set where every byte keeps real state s where it is, except bytes that NO real state of the def has a
+// transition for (those send it to the dead row, like everybody else).
+static void scout_qabs(const DefsSet &s, uint32_t d, uint32_t (&bits)[8]) {
+    const uint32_t S = (uint32_t)s.defs[d].allstr.largest_state_val + 1, *T = s.table_image.data() + (size_t)s.consts[d].row_base * 256;
+    bool undefined_everywhere[256];
+    for (uint32_t c = 0; c < 256; ++c) {
+        undefined_everywhere[c] = true;
+        for (uint32_t t = 0; t < S && undefined_everywhere[c]; ++t) undefined_everywhere[c] = T[(size_t)t * 256 + c] >= s.consts[d].dead_entry;
+    }
+    for (uint32_t t = 0; t < S && t < 256; ++t) {
+        bool q = true;
+        for (uint32_t c = 0; c < 256 && q; ++c) {
+            const uint32_t e = T[(size_t)t * 256 + c];
+            q = e >= s.consts[d].dead_entry ? undefined_everywhere[c] : (e >> kNextShift) - s.consts[d].row_base == t;
+        }
+        if (q) bits[t >> 5] |= 1u << (t & 31);
+    }
+}
+
+// The compact tables of def d, appended to img: bytes with the same column in every row (real states, dummy row, dead row) are one CLASS.
+// false: more than 127 classes, or the table passes the u16 row addresses
+static bool scout_compact_def(const DefsSet &s, uint32_t d, std::vector<uint8_t> &img, ScoutTables &out) {
+    const uint32_t S = (uint32_t)s.defs[d].allstr.largest_state_val + 1, R = S + 2u, base = s.consts[d].row_base;
+    const uint32_t *T = s.table_image.data() + (size_t)base * 256;
+    auto rel = [&](uint32_t r, uint32_t c) { const uint32_t e = T[(size_t)r * 256 + c]; const uint32_t x = (e >> kNextShift) - base; return e >= s.consts[d].dead_entry || x > S + 1u ? S + 1u : x; };
+    std::map<std::vector<uint16_t>, uint32_t> cls_of;
+    std::vector<std::vector<uint16_t>> cols;
+    uint8_t lut[256];
+    for (uint32_t c = 0; c < 256; ++c) {
+        std::vector<uint16_t> col(R);
+        for (uint32_t r = 0; r < R; ++r) col[r] = (uint16_t)rel(r, c);
+        auto it = cls_of.find(col);
+        if (it == cls_of.end()) {
+            if (cols.size() >= 127) return false;
+            it = cls_of.emplace(col, (uint32_t)cols.size()).first;
+            cols.push_back(col);
+        }
+        lut[c] = (uint8_t)(it->second * 2u);
+    }
+    const uint32_t Cn = (uint32_t)cols.size(), rowb = Cn * 2u;
+    const uint32_t lut_off = (uint32_t)img.size();
+    img.insert(img.end(), lut, lut + 256);
+    const uint32_t tab_off = (uint32_t)img.size();
+    if ((size_t)tab_off + (size_t)R * rowb > 0xfff0u) return false;      // row addresses are u16
+    img.resize((size_t)tab_off + (((size_t)R * rowb + 15) & ~(size_t)15), 0);
+    for (uint32_t r = 0; r < R; ++r)
+        for (uint32_t k = 0; k < Cn; ++k) {
+            const uint16_t addr = (uint16_t)(tab_off + (uint32_t)cols[k][r] * rowb);
+            std::memcpy(&img[(size_t)tab_off + (size_t)r * rowb + 2u * k], &addr, 2);
+        }
+    out.c_lut[d] = lut_off; out.c_tab[d] = tab_off; out.c_rowb[d] = rowb; out.c_inv[d] = (65536u + rowb - 1u) / rowb;
+    return true;
+}
+
+ScoutTables build_scout_tables(const DefsSet &s) {
+    ScoutTables out;
+    const uint32_t Dn = (uint32_t)std::min(s.defs.size(), kMaxDefsPerPass);
+    for (uint32_t d = 0; d < Dn; ++d) scout_qabs(s, d, out.qabs[d]);
+    std::vector<uint8_t> img;
+    for (uint32_t d = 0; d < Dn; ++d)
+        if (!scout_compact_def(s, d, img, out)) return out;
+    out.cimage = std::move(img);
+    return out;
+}
+
 }  // namespace hrx

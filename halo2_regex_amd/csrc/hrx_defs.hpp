@@ -140,6 +140,16 @@ int finalize_defs(DefsSet &s, std::string &err);
 size_t table_transition_rows(const DefsSet &s, size_t d, uint64_t *rows4, size_t cap_rows);
 size_t table_endpoint_rows(const DefsSet &s, size_t d, uint64_t *rows3, size_t cap_rows);
 
+// The tables of the chunked launch's scout (hrx_kernel_spec.hip, SpecArgs), built once per context from a config of up to kMaxDefsPerPass defs:
+// the quasi-absorbing-state bits, and the COMPACT image — per def a 256-byte class LUT (byte -> 2 x its column class) and the transition table over
+// classes, u16 entries holding the image byte address of the next state's row, rows [0, S + 2) (real states, dummy row, dead row; undefined -> S + 1).
+struct ScoutTables {
+    uint32_t qabs[kMaxDefsPerPass][8] = {};
+    std::vector<uint8_t> cimage;           // empty: some def has more than 127 classes, or the image passes the u16 row addresses — the scout walks the narrow table
+    uint32_t c_lut[kMaxDefsPerPass] = {}, c_tab[kMaxDefsPerPass] = {}, c_rowb[kMaxDefsPerPass] = {}, c_inv[kMaxDefsPerPass] = {};   // offsets of LUT and table, bytes per row, ceil(2^16 / rowb)
+};
+ScoutTables build_scout_tables(const DefsSet &s);
+
 // hrx_compile.cpp: regex -> minimal DFA in the reference's numbering; either output may be null
 struct CompiledDfa {               // Vec<serde_json::Value> of get_dfa_json_value, edges in map (byte) order of the key text
     struct Edge { std::string key; int to; std::vector<uint16_t> syms; };

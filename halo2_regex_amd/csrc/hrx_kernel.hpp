@@ -1,4 +1,5 @@
-// hrx_kernel.hpp — host-visible launch interface of the HIP kernels (hrx_kernel.hip: planner, dispatch, auxiliary kernels; hrx_kernel_pm.hip / hrx_kernel_sm.hip: the witness kernels).
+// hrx_kernel.hpp — host-visible launch interface of the HIP kernels (hrx_kernel.hip: dispatch, auxiliary kernels; hrx_kernel_pm.hip / hrx_kernel_sm.hip: the witness kernels;
+// the planner that fills LaunchInfo: hrx_plan.hpp).
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -38,8 +39,8 @@ struct WitnessArgs {
     uint32_t cw_lut_off;          // LDS offset of def 0's class LUT
     const uint8_t *pair_image;    // device copy of DefsSet::pair.image (the exact LDS image: blocks + class LUT), or NULL
     uint32_t pair_bytes, pair_classes, pair_blk_bytes, pair_lut_off;
-    uint32_t n_groups;            // ceil(B / gs), set by plan_witness_launch
-    uint32_t gs;                  // strings per wave (64, 32 or 16), set by plan_witness_launch
+    uint32_t n_groups;            // ceil(B / gs): the planner's LaunchInfo::n_groups (apply_plan)
+    uint32_t gs;                  // strings per wave (64, 32 or 16): LaunchInfo::gs (apply_plan)
     uint32_t D;
     uint32_t debug;               // the context's kDbg* bits below (forced kernel / table choices for the tests; ablations only with -DHRX_ABLATION)
     uint32_t tune;                // the context's kTune* bits (hrx_ctx_set_option, include/hrx.h): choices between variants that compute the same rows
@@ -74,8 +75,8 @@ struct WitnessArgs {
     uint32_t vs_chunks, vs_tiles, vs_groups;   // chunks per string, tiles per chunk, REAL groups (n_groups = vs_groups * vs_chunks)
     uint64_t *vs_status;          // [chunk][B]: every chunk's status word
     uint2 *vs_info;               // [chunk][B]: pend | fwd << 1 | sm << 2 | dec << 3, pend_start (hrx_lane.h TileMasks)
-    uint32_t sm_no_touch;         // walker/storer kernel: 1 = the storer does not warm L2 for the walker (set by plan_witness_launch; hrx_kernel_sm.hip)
-    uint32_t sm_bufs;             // def-parallel kernel, string-major outputs: LDS sub-tile buffers per group, 2 or 3 (set by plan_pmd_cw_sm; hrx_kernel_pmd.hip SMO)
+    uint32_t sm_no_touch;         // walker/storer kernel: 1 = the storer does not warm L2 for the walker (LaunchInfo::sm_no_touch, apply_plan; hrx_kernel_sm.hip)
+    uint32_t sm_bufs;             // def-parallel kernel, string-major outputs: LDS sub-tile buffers per group, 2 or 3 (LaunchInfo::sm_bufs, apply_plan; hrx_kernel_pmd.hip SMO)
     uint32_t nt_mix;              // position-major kernels: which stores are write-back instead of streaming (kNtMix*, hrx_kernel_pm.hip)
     uint32_t pace_even;           // profiling only (HRX_PACE, stamps / ablation builds): x 64 idle cycles per tile for the walkers of even workgroups; 0 in the product
     DefConsts dc[kMaxDefsPerLaunch];
@@ -146,11 +147,15 @@ uint32_t debug_flags_from_env();
 constexpr uint64_t kDbgMatchViaRows = 1ull << 32;
 bool match_via_rows_from_env();
 
+enum class Kernel {
+    OneWave,   // one-wave-does-all kernel (witness_kernel)
+    Split,     // walker/storer kernel (witness_split_kernel)
+    Pm,        // loader/walker kernel for the position-major layout (witness_pm_kernel)
+    Pmd,       // def-parallel loader/walker kernel for D >= 2 batches that leave walker slots empty, or a whole config on the CLASS-WIDE tables (witness_pmd_kernel)
+    Pp,        // pair-step loader/walker kernel, position-major, D = 1 (witness_pp_kernel: two bytes per dependent lookup)
+};
 struct LaunchInfo {
-    int split;         // 6: pair-step loader/walker kernel, position-major, D = 1 (witness_pp_kernel: two bytes per dependent lookup),
-                       // 5: def-parallel loader/walker kernel for D >= 2 batches that leave walker slots empty (witness_pmd_kernel),
-                       // 2: loader/walker kernel for the position-major layout (witness_pm_kernel),
-                       // 1: walker/storer kernel (witness_split_kernel), 0: one-wave-does-all kernel (witness_kernel)
+    Kernel kernel;
     int waves_per_wg;  // split: 2 * pairs
     int nslots;        // split: ring slots per walker/storer pair
     int gtab;          // 1: fused table read from global memory (too large for LDS)
@@ -163,28 +168,29 @@ struct LaunchInfo {
     int spec_chunks;   // chunks per string
     int pmd_fin;       // def-parallel kernel on the WIDE table (two and three defs): 1 = a combiner wave of its own per group (hrx_kernel_pmd.hip FIN)
     size_t lds_bytes;
+    // what the kernels read out of WitnessArgs of the planner's choices (apply_plan copies them there)
+    uint32_t gs;           // strings per wave: 64; the one-wave kernel: 64, 32 or 16
+    uint32_t n_groups;     // ceil(B / gs); a chunked launch: the REAL groups (its walk runs over n_groups x spec_chunks)
+    uint32_t sm_no_touch;  // walker/storer kernel: 1 = the storer does not warm L2 for the walker
+    uint32_t sm_bufs;      // def-parallel kernel, string-major outputs: LDS sub-tile buffers per group, 2 or 3
 };
 
 // LDS bytes one wave stages per 64-string x 64-row tile
 constexpr size_t wave_stage_bytes(int D, unsigned gs) { return ((size_t)gs + 1) * ((256 * (size_t)D + 16) + 80 + 8); }
 constexpr size_t kLdsLimit = 160 * 1024;
 
-// Picks the launch geometry for `a` on a device with `num_cus` CUs; returns false if nothing fits.
-bool plan_witness_launch(WitnessArgs &a, int num_cus, LaunchInfo &out);
-bool plan_pmd_cw(WitnessArgs &a, int num_cus, LaunchInfo &out);
-bool plan_pmd_cw_sm(WitnessArgs &a, int num_cus, LaunchInfo &out);   // ... with string-major outputs straight out of the launch (four and five defs, rows in multiples of 16)   // a whole config of 4 .. 7 defs in one def-parallel launch on the CLASS-WIDE tables (a.cw_image set)
 hipError_t launch_witness(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream);
 hipError_t launch_zero_u32(uint32_t *p, hipStream_t stream);   // *p = 0 as a kernel node (hrx_kernel.hip)
-// the two kernel translation units behind launch_witness: li.split == 2 -> hrx_kernel_pm.hip, else hrx_kernel_sm.hip
+// the kernel translation units behind launch_witness: Kernel::Pm -> hrx_kernel_pm.hip, OneWave and Split -> hrx_kernel_sm.hip,
 hipError_t launch_witness_pm(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream);
 hipError_t launch_witness_sm(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream);
-hipError_t launch_witness_pmd(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream);   // hrx_kernel_pmd.hip (split == 5)
-hipError_t launch_witness_pp(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream);    // hrx_kernel_pp.hip (split == 6)
+hipError_t launch_witness_pmd(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream);   // Pmd -> hrx_kernel_pmd.hip
+hipError_t launch_witness_pp(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream);    // Pp -> hrx_kernel_pp.hip
 // position-major loader/walker kernel (hrx_kernel_pm.hip): LDS bytes per walker/loader pair.  FIN = the loader also finishes
 // the tiles (reveal masks + masked rows) from a 6-KiB summary the walker hands over; not for the HALF table (a 256-state table
 // leaves no LDS for it) nor for string-major outputs.
 // nt_mix: low byte k: the records of every k-th tile (t % k == k - 1) are stored write-back, 0 = all streaming; bit 8: the masked
-// rows write-back.  plan_nt_mix (hrx_kernel.hip) picks k so that ~128 MiB of a launch's records stay write-back.  Whatever it says, the
+// rows write-back.  plan_nt_mix (hrx_plan.cpp) picks k so that ~128 MiB of a launch's records stay write-back.  Whatever it says, the
 // masked rows of a tile into which an OPEN optimistic span reaches are written back: they may be zeroed later, and a repair that finds
 // its line in L2 costs the memory nothing (hrx_kernel_pm.hip octets_out).  Tools only (the libhrx_ntenv.so build reads HRX_NT_MIX /
 // HRX_NT_FLAGS at every launch, tools/ab_policy.py): bit 9 = not even those, bits 12-15 km = the masked rows of every km-th tile as well.
@@ -196,7 +202,6 @@ hipError_t launch_traffic_pass_sm(const uint8_t *chars, size_t stride, size_t B,
                                   size_t msk_pitch, uint32_t nt_mix, uint32_t *sink, int num_cus, hipStream_t stream);
 hipError_t launch_traffic_pass(const uint8_t *chars, size_t stride, size_t B, size_t M, uint32_t D, uint32_t *records, uint16_t *masked,
                                uint32_t nt_mix, uint32_t *sink, int num_cus, hipStream_t stream, uint32_t *const *planes = nullptr, uint32_t stripes = 1);
-uint32_t plan_nt_mix(const WitnessArgs &a, const LaunchInfo &li);
 constexpr size_t kPmSummaryBytes = 6144;
 template <bool HALF, bool SM> constexpr bool kPmFinisher = !HALF && !SM;
 constexpr int pm_max_threads(bool half, bool sm) { return (!half && !sm) ? 768 : 512; }
@@ -313,9 +318,6 @@ struct MatchPlan {
     int grid, threads;
     size_t lds_bytes;
 };
-// fused for D <= 3 on the narrow table in LDS where it fits, else the HALF table, else the narrow table out of L2 (the forced BYTE / HALF / global-table
-// bits pick among these); via rows for more defs, where the witness planner walks in chunks (few long strings), or when forced (kDbgMatchViaRows)
-bool plan_match_launch(WitnessArgs &a, int num_cus, bool via_rows, MatchPlan &out);
 hipError_t launch_match_lane(const MatchArgs &a, const MatchPlan &p, hipStream_t stream);
 hipError_t launch_spans_from_masked(const MatchArgs &a, hipStream_t stream);
 // position-major input of strings [b0, b0 + n) (all in one block of kPmBlock) -> string-major [n][stride] (the "via rows" slices inside a block)

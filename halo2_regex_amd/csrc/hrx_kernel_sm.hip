@@ -899,7 +899,7 @@ static hipError_t launch_t(const WitnessArgs &a, const LaunchInfo &li, hipStream
 }
 
 hipError_t launch_witness_sm(const WitnessArgs &a, const LaunchInfo &li, hipStream_t stream) {
-    if (li.split) return li.byte ? launch_split<1, 32, true>(a, li, stream) : a.D == 1 ? launch_split<1, 32>(a, li, stream) : launch_split<2, 16>(a, li, stream);
+    if (li.kernel == Kernel::Split) return li.byte ? launch_split<1, 32, true>(a, li, stream) : a.D == 1 ? launch_split<1, 32>(a, li, stream) : launch_split<2, 16>(a, li, stream);
     const bool al = (a.M % 8u) == 0;
     if (li.gtab) {
         switch (a.D) {

@@ -39,23 +39,16 @@ static int check_ragged_args(const uint8_t *values, const uint64_t *offsets, siz
 }
 
 // the planner's view of a context's config for the match entry points (describe and launch agree by construction)
-static void match_args_of(const DefsSet &s, uint32_t dbg, int layout, size_t B, size_t M, WitnessArgs &a) {
-    a = WitnessArgs{};
+static WitnessArgs match_args_of(const DefsSet &s, uint32_t dbg, int layout, size_t B, size_t M) {
+    WitnessArgs a = witness_args_of(s, host_images(s));
     a.layout = (uint32_t)layout; a.B = (uint32_t)B; a.M = (uint32_t)M;
-    a.table_image = s.table_image.empty() ? nullptr : s.table_image.data(); a.table_bytes = (uint32_t)(s.table_image.size() * 4);
-    a.wide_image = s.wide_image.empty() ? nullptr : s.wide_image.data();
-    a.half_image = s.half_image.empty() ? nullptr : s.half_image.data(); a.half_bytes = (uint32_t)(s.half_image.size() * 2);
-    a.pair_image = s.pair.image.empty() ? nullptr : s.pair.image.data(); a.pair_bytes = s.pair.bytes; a.pair_classes = s.pair.n_classes;
-    a.pair_blk_bytes = s.pair.blk_bytes; a.pair_lut_off = s.pair.lut_off;
-    a.byte_image = s.byte.image.empty() ? nullptr : s.byte.image.data(); a.byte_bytes = s.byte.bytes; a.byte_dead = s.byte.dead; a.byte16_bytes = s.byte.bytes16;
-    a.D = s.groups.empty() ? (uint32_t)s.defs.size() : 0u;     // (a multi-pass config always goes via rows)
+    if (!s.groups.empty()) a.D = 0u;     // (a multi-pass config always goes via rows)
     a.debug = dbg;
+    return a;
 }
 
 static bool match_plan(const DefsSet &s, uint32_t dbg, bool via_rows, int layout, size_t B, size_t M, int num_cus, MatchPlan &p) {
-    WitnessArgs a;
-    match_args_of(s, dbg, layout, B, M, a);
-    return plan_match_launch(a, num_cus, via_rows, p);
+    return plan_match_launch(match_args_of(s, dbg, layout, B, M), num_cus, via_rows, p);
 }
 
 // the fused kernels' arguments but for the input (the entry's own: stride, lens, in_pm / offsets, base)

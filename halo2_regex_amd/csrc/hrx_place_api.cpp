@@ -344,7 +344,7 @@ int hrx_traffic_pass_device(hrx_ctx *ctx, const uint8_t *chars, size_t stride, s
     WitnessArgs a{};
     a.layout = HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR; a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)ctx->s.defs.size();
     LaunchInfo li{};
-    li.split = 2;
+    li.kernel = Kernel::Pm;
     const uint32_t nt_mix = plan_nt_mix(a, li);
     HIP_TRY(launch_traffic_pass(chars, stride, B, M, a.D, records, masked, nt_mix, ctx->d_group_counter + 8, ctx->num_cus, (hipStream_t)stream));
     return HRX_OK;
@@ -373,7 +373,7 @@ int hrx_traffic_pass_device_layout(hrx_ctx *ctx, int layout, const uint8_t *char
     a.layout = HRX_LAYOUT_STRING_MAJOR; a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)D;
     a.rec_pitch = (uint32_t)rec_pitch; a.msk_pitch = (uint32_t)msk_pitch;      // (plan_nt_mix sizes the records by the pitch: without it the pass streamed every store where the launch writes some back — ADVICE r5)
     LaunchInfo li{};
-    li.split = 1;
+    li.kernel = Kernel::Split;
     const uint32_t nt_mix = plan_nt_mix(a, li);
     HIP_TRY(launch_traffic_pass_sm(chars, stride, B, M, (uint32_t)D, records, rec_pitch, masked, msk_pitch, nt_mix, ctx->d_group_counter + 8, ctx->num_cus, (hipStream_t)stream));
     return HRX_OK;
@@ -396,7 +396,7 @@ int hrx_traffic_pass_device_planes(hrx_ctx *ctx, const uint8_t *chars, size_t st
     WitnessArgs a{};
     a.layout = HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR; a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)Dn;
     LaunchInfo li{};
-    li.split = 2;
+    li.kernel = Kernel::Pm;
     const uint32_t nt_mix = plan_nt_mix(a, li);
     HIP_TRY(launch_traffic_pass(chars, stride, B, M, a.D, record_planes[0], masked, nt_mix, ctx->d_group_counter + 8, ctx->num_cus, (hipStream_t)stream, record_planes, (uint32_t)(n_planes / Dn)));
     return HRX_OK;

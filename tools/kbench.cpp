@@ -75,9 +75,10 @@ int main(int argc, char **argv) {
     a.D = 1; a.debug = debug; a.dc[0] = s.consts[0];
     LaunchInfo li;
     if (!plan_witness_launch(a, prop.multiProcessorCount, li)) return 5;
+    apply_plan(a, li);
     const size_t ntiles = (M + 63) / 64, nw = (size_t)li.grid * li.waves_per_wg;
     if (want_stamps) { CK(hipMalloc(&d_stamps, nw * ntiles * 128)); CK(hipMemset(d_stamps, 0, nw * ntiles * 128)); }
-    printf("grid %d x %d waves, gs %u, split %d, lds %zu, clock %d kHz\n", li.grid, li.waves_per_wg, a.gs, li.split, li.lds_bytes, prop.clockRate);
+    printf("grid %d x %d waves, gs %u, kernel %d, lds %zu, clock %d kHz\n", li.grid, li.waves_per_wg, a.gs, (int)li.kernel, li.lds_bytes, prop.clockRate);
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
     for (int i = 0; i < 5; ++i) CK(launch_witness(a, li, 0));
     CK(hipDeviceSynchronize());
@@ -87,7 +88,7 @@ int main(int argc, char **argv) {
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     const double us = ms * 1e3 / steps;
     printf("debug=0x%x  %.2f us/launch  %.3e rows/s  %.1f%% of 8 TB/s\n", debug, us, (double)B * n / (us * 1e-6), 7.0 * B * n / (us * 1e-6) / 8e12 * 100);
-    if (want_stamps && li.split == 2) {   // position-major kernel built with -DHRX_STAMPS: per walker [input wait, walk, tile end, whole group] ticks
+    if (want_stamps && li.kernel == Kernel::Pm) {   // position-major kernel built with -DHRX_STAMPS: per walker [input wait, walk, tile end, whole group] ticks
         CK(hipMemset(d_stamps, 0, nw * ntiles * 128));
         a.stamps = d_stamps;
         const int reps = 20;
@@ -129,12 +130,13 @@ int main(int argc, char **argv) {
     } else if (want_stamps) {
         a.stamps = d_stamps;
         CK(launch_witness(a, li, 0)); CK(hipDeviceSynchronize());
-        const int per = li.split ? 8 : 4;
-        const size_t units = li.split ? (size_t)li.grid * (li.waves_per_wg / 2) : nw;
-        const size_t nt = li.split ? (M + 31) / 32 : ntiles;
+        const bool ring = li.kernel != Kernel::OneWave;
+        const int per = ring ? 8 : 4;
+        const size_t units = ring ? (size_t)li.grid * (li.waves_per_wg / 2) : nw;
+        const size_t nt = ring ? (M + 31) / 32 : ntiles;
         std::vector<unsigned long long> st(units * nt * per);
         CK(hipMemcpy(st.data(), d_stamps, st.size() * 8, hipMemcpyDeviceToHost));
-        if (!li.split) {
+        if (!ring) {
             for (size_t w : {(size_t)0, nw / 2}) {
                 printf("wave %zu: per tile [walk, epilogue, store-issue, gap-to-next]\n", w);
                 for (size_t tt = 0; tt < nt; ++tt) {

@@ -132,7 +132,7 @@ __global__ __launch_bounds__(512) void pairp_k(const uint4 *__restrict__ in, uin
 }
 
 // pair_k with the shipped kernel's store policy: streaming stores, except that the record quads of every other 64-row tile are
-// stored write-back (plan_nt_mix, hrx_kernel.hip: ~128 MiB of a launch's records stay in the cache hierarchy)
+// stored write-back (plan_nt_mix, hrx_plan.cpp: ~128 MiB of a launch's records stay in the cache hierarchy)
 __global__ __launch_bounds__(512) void pairmix_k(const uint4 *__restrict__ in, uint4 *__restrict__ rec, uint4 *__restrict__ msk, unsigned *sink) {
     const size_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const size_t g = (size_t)blockIdx.x * 4 + (wave & 3), b = g * 64 + lane;
