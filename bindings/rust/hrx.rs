@@ -211,6 +211,7 @@ pub const HRX_OPT_HOST_ROUTE: c_int = 2;      // HRX_HOST_ROUTE_AUTO (the fastes
 pub const HRX_OPT_HOST_THREADS: c_int = 3;
 pub const HRX_OPT_HOST_PIPELINE: c_int = 4;
 pub const HRX_OPT_PLACE_DRY_LAUNCH: c_int = 5;
+pub const HRX_OPT_MATCH_FUSED_WIDE: c_int = 6;
 #[repr(C)] #[derive(Default, Clone, Copy)]
 pub struct hrx_host_route_report {
     pub route: c_int, pub device_strings: usize, pub host_strings: usize, pub device_ms: f64, pub host_ms: f64, pub call_ms: f64,

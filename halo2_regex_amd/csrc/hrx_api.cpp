@@ -208,6 +208,7 @@ int hrx_ctx_clone(const hrx_ctx *ctx, int device, hrx_ctx **out) {
     if (rc != HRX_OK) return rc;
     c->host_threshold = ctx->host_threshold;      // the per-context switches travel with the clone
     c->tune = ctx->tune;
+    c->match_fused_wide = ctx->match_fused_wide;
     c->place_dry = ctx->place_dry; c->host_route = ctx->host_route; c->host_threads = ctx->host_threads; c->host_pipeline = ctx->host_pipeline; c->host_chunk_mib = ctx->host_chunk_mib; c->host_trace = ctx->host_trace;
     c->place_enabled = ctx->place_enabled; c->place_max_bytes = ctx->place_max_bytes; c->place_max_ms = ctx->place_max_ms;
     *out = c;
@@ -699,6 +700,10 @@ int hrx_ctx_set_option(hrx_ctx *ctx, int option, long value) {
             if (value < 0 || value > 1) return fail(HRX_ERR_ARG, "HRX_OPT_PLACE_DRY_LAUNCH: 0 or 1");
             ctx->place_dry = value != 0;
             return HRX_OK;
+        case HRX_OPT_MATCH_FUSED_WIDE:
+            if (value < 0 || value > 1) return fail(HRX_ERR_ARG, "HRX_OPT_MATCH_FUSED_WIDE: 0 or 1");
+            ctx->match_fused_wide = value != 0;
+            return HRX_OK;
         default: return fail(HRX_ERR_ARG, "hrx_ctx_set_option: unknown option");
     }
 }
@@ -711,6 +716,7 @@ long hrx_ctx_get_option(const hrx_ctx *ctx, int option) {
         case HRX_OPT_HOST_THREADS: return ctx->host_threads;
         case HRX_OPT_HOST_PIPELINE: return ctx->host_pipeline;
         case HRX_OPT_PLACE_DRY_LAUNCH: return ctx->place_dry ? 1 : 0;
+        case HRX_OPT_MATCH_FUSED_WIDE: return ctx->match_fused_wide ? 1 : 0;
         default: return -1;
     }
 }

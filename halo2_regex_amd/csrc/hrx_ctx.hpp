@@ -146,12 +146,14 @@ struct hrx_ctx {
     // hrx_match_batch_* (hrx_match_api.cpp): HRX_DEBUG_FLAGS bit 32 (kDbgMatchViaRows), the "via rows" scratch (witness slices, a slice's string-major input) and its last stream,
     // the host entry's staged counts / spans
     bool match_via_rows = false;
+    // HRX_OPT_MATCH_FUSED_WIDE: four to eight defs take the fused walk on the CLASS-WIDE image where plan_match_wide allows it (hrx_plan.hpp)
+    bool match_fused_wide = false;
     DevBuf match_rec, match_msk, match_chars, match_counts, match_spans;
     DevBuf match_lens;               // ragged "via rows": the slice's lens (hrx_match_batch_device_ragged)
     DevBuf match_status;             // selected "via rows": the slice's status words by slot (hrx_match_selected_device)
     hipStream_t match_stream = nullptr;
     bool match_used = false;
-    DevBuf d_cw;                    // CLASS-WIDE image of a config of 4 .. 7 defs (DefsSet::cw_image): the single-launch def-parallel path
+    DevBuf d_cw;                    // CLASS-WIDE image of a config of 4 .. 8 defs (DefsSet::cw_image): the single-launch def-parallel path and the fused-wide match
 #ifdef HRX_STAMPS
     DevBuf stamps;                  // tools-only build: 8 u64 per walker pair of the position-major kernel (hrx_kernel_pm.hip)
 #endif

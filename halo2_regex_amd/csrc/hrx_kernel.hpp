@@ -314,6 +314,7 @@ struct MatchArgs {
 };
 struct MatchPlan {
     int fused;          // 1: match_lane_kernel<D, gtab, half>; 0: via rows
+    int wide;           // > 0: the fused walk for four to eight defs instead, match_wide_kernel<D, wide, Src, SEL> on the CLASS-WIDE image (plan_match_wide)
     int gtab, half;
     int grid, threads;
     size_t lds_bytes;
@@ -365,6 +366,12 @@ struct SpanScatter {
     uint64_t *spans;                // [B_src][max_spans], NULL when max_spans == 0
 };
 hipError_t launch_spans_from_masked_selected(const MatchArgs &a, const SpanScatter &o, hipStream_t stream);
+// FUSED-WIDE match (HRX_OPT_MATCH_FUSED_WIDE; hrx_kernel_match_wide.hip, lane core and arguments: hrx_match_wide.h): four to eight defs, one lane per
+// string on the CLASS-WIDE image in LDS, p.wide defs side by side.  One kernel template serves the string-major, ragged (base: subtracted from every offset) and
+// selected entries: sel == NULL walks strings 0 .. a.B - 1 of the source, else sel[0 .. n_sel)
+struct MatchWideArgs;
+hipError_t launch_match_wide(const MatchWideArgs &a, const SelectedSrc &s, uint64_t base, const uint32_t *sel, size_t n_sel, const MatchPlan &p, int num_cus,
+                             hipStream_t stream);
 
 // EXTRACT (include/hrx.h hrx_extract_spans_device; hrx_kernel_extract.hip): the runs of a match call -> run_offsets / runs / byte_offsets / values / totals.
 // Count, scan, apply, gather: four launches, nothing but the caller's workspace in between (extract_workspace_bytes: 3 words per kExtractThreads strings + 4)

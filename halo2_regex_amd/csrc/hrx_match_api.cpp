@@ -10,6 +10,7 @@
 #include "hrx_ctx.hpp"
 #include "hrx_host_walk.hpp"
 #include "hrx_lane.h"
+#include "hrx_match_wide.h"
 
 using namespace hrx;
 
@@ -47,8 +48,16 @@ static WitnessArgs match_args_of(const DefsSet &s, uint32_t dbg, int layout, siz
     return a;
 }
 
-static bool match_plan(const DefsSet &s, uint32_t dbg, bool via_rows, int layout, size_t B, size_t M, int num_cus, MatchPlan &p) {
-    return plan_match_launch(match_args_of(s, dbg, layout, B, M), num_cus, via_rows, p);
+// what a context's switches say about the match route: kDbgMatchViaRows, HRX_OPT_MATCH_FUSED_WIDE (none: the context-free describe)
+struct MatchSwitches {
+    bool via_rows, fused_wide;
+};
+static MatchSwitches switches_of(const hrx_ctx *ctx) { return MatchSwitches{ctx->match_via_rows, ctx->match_fused_wide}; }
+
+// the one decision: the fused-wide walk where the option and plan_match_wide allow it, else plan_match_launch
+static bool match_plan(const DefsSet &s, uint32_t dbg, const MatchSwitches &sw, int layout, size_t B, size_t M, int num_cus, MatchPlan &p) {
+    if (plan_match_wide(s, dbg, sw.via_rows, sw.fused_wide, layout, B, M, num_cus, p)) return true;
+    return plan_match_launch(match_args_of(s, dbg, layout, B, M), num_cus, sw.via_rows, p);
 }
 
 // the fused kernels' arguments but for the input (the entry's own: stride, lens, in_pm / offsets, base)
@@ -60,6 +69,16 @@ static MatchArgs fused_args(const hrx_ctx *ctx, const MatchPlan &p, const uint8_
     m.status = status; m.span_counts = span_counts; m.spans = spans;
     for (uint32_t d = 0; d < m.D; ++d) m.dc[d] = ctx->s.consts[d];
     return m;
+}
+
+// the fused-wide kernel's arguments (p.wide; hrx_match_wide.h)
+static MatchWideArgs wide_args(const hrx_ctx *ctx, const MatchPlan &p, size_t B, size_t M, uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans) {
+    MatchWideArgs w{};
+    w.cw_image = (const uint8_t *)ctx->d_cw.p; w.image_bytes = (uint32_t)p.lds_bytes; w.cw_lut_off = ctx->s.cw_lut_off;
+    w.B = (uint32_t)B; w.M = (uint32_t)M; w.D = (uint32_t)ctx->s.defs.size(); w.max_spans = (uint32_t)max_spans;
+    w.status = status; w.span_counts = span_counts; w.spans = spans;
+    for (uint32_t d = 0; d < w.D; ++d) w.dc[d] = ctx->s.cw_consts[d];
+    return w;
 }
 
 // ---- "via rows".  Strings per slice: the witness rows of a slice, and `extra` staged bytes per string, fit the scratch; slices of more than one
@@ -163,7 +182,11 @@ static int match_device_locked(hrx_ctx *ctx, int layout, const uint8_t *chars, s
         return fail(HRX_ERR_ARG, "chars must be 16-byte aligned with stride % 16 == 0 and stride >= 16");
     if (B == 0) return HRX_OK;
     MatchPlan p;
-    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, layout, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (!match_plan(ctx->s, ctx->debug, switches_of(ctx), layout, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.wide) {
+        HIP_TRY(launch_match_wide(wide_args(ctx, p, B, M, status, span_counts, spans, max_spans), SelectedSrc{chars, nullptr, lens, stride}, 0, nullptr, 0, p, ctx->num_cus, st));
+        return HRX_OK;
+    }
     if (p.fused) {
         MatchArgs m = fused_args(ctx, p, chars, B, M, status, span_counts, spans, max_spans);
         m.stride = stride; m.lens = lens; m.in_pm = layout == HRX_LAYOUT_INPUT_POSITION_MAJOR ? 1u : 0u;
@@ -187,7 +210,11 @@ static int match_ragged_device_locked(hrx_ctx *ctx, const uint8_t *values, const
                                       uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
     if (B == 0) return HRX_OK;
     MatchPlan p;
-    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, HRX_LAYOUT_STRING_MAJOR, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (!match_plan(ctx->s, ctx->debug, switches_of(ctx), HRX_LAYOUT_STRING_MAJOR, B, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.wide) {
+        HIP_TRY(launch_match_wide(wide_args(ctx, p, B, M, status, span_counts, spans, max_spans), SelectedSrc{values, offsets, nullptr, 0}, base, nullptr, 0, p, ctx->num_cus, st));
+        return HRX_OK;
+    }
     if (p.fused) {
         RaggedMatchArgs r{};
         r.m = fused_args(ctx, p, values, B, M, status, span_counts, spans, max_spans);
@@ -228,7 +255,11 @@ static int match_selected_device_locked(hrx_ctx *ctx, const SelectedSrc &src, si
                                         uint32_t *span_counts, uint64_t *spans, size_t max_spans, hipStream_t st) {
     if (B == 0 || n_sel == 0) return HRX_OK;
     MatchPlan p;
-    if (!match_plan(ctx->s, ctx->debug, ctx->match_via_rows, HRX_LAYOUT_STRING_MAJOR, n_sel, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (!match_plan(ctx->s, ctx->debug, switches_of(ctx), HRX_LAYOUT_STRING_MAJOR, n_sel, M, ctx->num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.wide) {
+        HIP_TRY(launch_match_wide(wide_args(ctx, p, B, M, status, span_counts, spans, max_spans), src, 0, sel, n_sel, p, ctx->num_cus, st));
+        return HRX_OK;
+    }
     if (p.fused) {
         const MatchArgs m = fused_args(ctx, p, src.src, B, M, status, span_counts, spans, max_spans);
         HIP_TRY(launch_match_selected(m, src, sel, n_sel, p, ctx->num_cus, st));
@@ -479,7 +510,7 @@ int hrx_ragged_to_position_major_device(hrx_ctx *ctx, const uint8_t *values, con
     return HRX_OK;
 }
 
-static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_rows, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
+static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, const MatchSwitches &sw, int layout, size_t B, size_t M, int num_cus, char *out, size_t cap) {
     // HRX_LAYOUT_INPUT_SELECTED | a source layout: the launch of hrx_match_selected_device with n_sel = B
     const bool selected = (layout & HRX_LAYOUT_INPUT_SELECTED) != 0;
     const char *src_name = nullptr;
@@ -493,7 +524,12 @@ static int describe_match(const DefsSet &s, uint32_t dbg, bool mpc_on, bool via_
     if (!ragged && layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_INPUT_POSITION_MAJOR)
         return fail(HRX_ERR_ARG, "layout must be HRX_LAYOUT_STRING_MAJOR, HRX_LAYOUT_INPUT_POSITION_MAJOR or HRX_LAYOUT_INPUT_RAGGED");
     MatchPlan p;
-    if (!match_plan(s, dbg, via_rows, ragged ? HRX_LAYOUT_STRING_MAJOR : layout, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (!match_plan(s, dbg, sw, ragged ? HRX_LAYOUT_STRING_MAJOR : layout, B, M, num_cus, p)) return fail(HRX_ERR_BOUNDS, "no match launch fits");
+    if (p.wide) {
+        std::snprintf(out, cap, "hrx::match_wide_kernel<%zu, %d, %s, %s> grid=persistent threads=%d lds=%zu", s.defs.size(), p.wide,
+                      selected ? src_name : ragged ? "hrx::RaggedSrc" : "hrx::PaddedSrc", selected ? "true" : "false", p.threads, p.lds_bytes);
+        return HRX_OK;
+    }
     if (p.fused) {
         const char *g = p.gtab ? "true" : "false", *h = p.half ? "true" : "false";
         if (selected)
@@ -522,13 +558,13 @@ int hrx_describe_match(const hrx_defs *defs, int layout, size_t B, size_t M, int
     if (num_cus < 1) return fail(HRX_ERR_ARG, "num_cus must be >= 1");
     if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
     const char *mpc = std::getenv("HRX_MP_COMBINE");      // (what hrx_ctx_create would read now)
-    return describe_match(defs->s, debug_flags_from_env(), mpc && std::atoi(mpc) != 0, match_via_rows_from_env(), layout, B ? B : 1, M, num_cus, out, cap);
+    return describe_match(defs->s, debug_flags_from_env(), mpc && std::atoi(mpc) != 0, MatchSwitches{match_via_rows_from_env(), false}, layout, B ? B : 1, M, num_cus, out, cap);
 }
 
 int hrx_ctx_describe_match(const hrx_ctx *ctx, int layout, size_t B, size_t M, char *out, size_t cap) {
     if (!ctx || !out || !cap) return fail(HRX_ERR_ARG, "NULL argument");
     if (M == 0 || M > (1u << 24)) return fail(HRX_ERR_ARG, "max_chars_size must be in 1..2^24");
-    return describe_match(ctx->s, ctx->debug, ctx->mp_combine, ctx->match_via_rows, layout, B ? B : 1, M, ctx->num_cus > 0 ? ctx->num_cus : 256, out, cap);
+    return describe_match(ctx->s, ctx->debug, ctx->mp_combine, switches_of(ctx), layout, B ? B : 1, M, ctx->num_cus > 0 ? ctx->num_cus : 256, out, cap);
 }
 
 }  // extern "C"

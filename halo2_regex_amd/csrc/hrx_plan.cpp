@@ -421,6 +421,27 @@ bool plan_match_launch(const WitnessArgs &a, int num_cus, bool via_rows, MatchPl
     return true;
 }
 
+// MATCH, four to eight defs (hrx_kernel_match_wide.hip): the rule of hrx_plan.hpp.  The "chunked" test is plan_match_launch's, asked of the route that the
+// via-rows call of this shape would launch (today no route of four and more defs chunks: its launches are the def-parallel kernel or passes)
+bool plan_match_wide(const DefsSet &s, uint32_t debug, bool via_rows, bool option, int layout, size_t B, size_t M, int num_cus, MatchPlan &out) {
+    const size_t D = s.defs.size(), lds = (s.cw_image.size() + 15) & ~(size_t)15;
+    if (!option || via_rows || D < 4 || D > kMaxDefsPerLaunch || s.cw_image.empty() || lds > kLdsLimit || layout != HRX_LAYOUT_STRING_MAJOR) return false;
+    BatchRoute route;
+    std::string err;
+    if (plan_batch_route(s, debug, 0u, false, HRX_LAYOUT_POSITION_MAJOR, B, M, 0, num_cus, 0, false, route, err) != HRX_OK) return false;
+    for (const BatchRoute::Pass &ps : route.passes)
+        if (ps.li.spec_tiles) return false;
+    out = MatchPlan{};
+    out.fused = 1;
+    // defs a sweep walks side by side: four (the fastest of 1, 2 and 4 at one wave per SIMD, where the walk is chain-latency bound, at four and at eight defs);
+    // one by one at four defs for batches of more than a wave per SIMD (occupancy 2: 1.72 against 2.22 ms at 262144 x 1024).  DESIGN.md §16
+    out.wide = D == 4 && B > (size_t)num_cus * kMatchThreads ? 1 : 4;
+    out.lds_bytes = lds;
+    out.threads = (int)kMatchThreads;
+    out.grid = (int)((B + kMatchThreads - 1) / kMatchThreads);       // (persistent lanes: the launch caps it at what the device holds at once)
+    return true;
+}
+
 // ---------------------------------------------------------------------------------------------
 // a launch's table fields, and the route of a witness call
 // ---------------------------------------------------------------------------------------------

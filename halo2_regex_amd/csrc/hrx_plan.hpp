@@ -21,6 +21,11 @@ uint32_t plan_nt_mix(const WitnessArgs &a, const LaunchInfo &li);
 // fused for D <= 3 on the narrow table in LDS where it fits, else the HALF table, else the narrow table out of L2 (the forced BYTE / HALF / global-table
 // bits pick among these); via rows for more defs, where the witness planner walks in chunks (few long strings), or when forced (kDbgMatchViaRows)
 bool plan_match_launch(const WitnessArgs &a, int num_cus, bool via_rows, MatchPlan &out);
+// HRX_OPT_MATCH_FUSED_WIDE: does the fused walk on the CLASS-WIDE image (hrx_kernel_match_wide.hip) serve this config and shape?  True (out.wide = the defs a sweep
+// walks side by side) iff the option is on, the set has 4 .. kMaxDefsPerLaunch defs and a CLASS-WIDE image that fits LDS,
+// via_rows (kDbgMatchViaRows) is not set, no launch of the via-rows witness route of this shape is chunked and the input is not position-major.  False: `out`
+// untouched, plan_match_launch decides as before.  layout: HRX_LAYOUT_STRING_MAJOR (ragged and selected calls too) or HRX_LAYOUT_INPUT_POSITION_MAJOR
+bool plan_match_wide(const DefsSet &s, uint32_t debug, bool via_rows, bool option, int layout, size_t B, size_t M, int num_cus, MatchPlan &out);
 
 // ---- the table fields of a launch's arguments: the ONE place a WitnessArgs is filled from a DefsSet.  The launch passes the set's device images,
 // the planning-only callers the host images (host_images): the planner only looks at which images exist and how large they are.

@@ -151,8 +151,16 @@ size_t hrx_ctx_host_threshold(const hrx_ctx *ctx);
  *                              sets 1 / 2 as the context's default
  *   HRX_OPT_PLACE_DRY_LAUNCH   hrx_alloc_output_planes / _for_batch: 1 (default) the best candidate sets by the pairings' score are each launched into and the fastest is kept, 0 the best
  *                              by score is kept unlaunched (a profiler's kernel list then holds the caller's launches only)
+ *   HRX_OPT_MATCH_FUSED_WIDE   the match entry points (MATCH, RAGGED, SELECTED below) on configs of four to eight RegexDefs: 0 (default) "via rows", 1 the fused walk — one lane
+ *                              per string on the config's class-wide tables in LDS, no witness row written, no scratch, no slices — for string-major, ragged and selected input
+ *                              where every def has at most 32 byte classes, the defs have at most 1023 table rows together and the tables fit LDS; every other config and
+ *                              shape (position-major input, more than eight defs, HRX_DEBUG_FLAGS bit 32) stays via rows.  hrx_ctx_describe_match names what a shape takes.
+ *                              Results are identical either way.  Recommended (measured at most 0.9 of the via-rows time, tools/match_wide_bench.py on 65536 x 1024 and 4 x 65536 x 1024) for
+ *                              whole batches — string-major or ragged — whose strings mostly fill M (0.42 .. 0.60) or are mostly short with a few long (0.80 .. 0.89), and at four
+ *                              defs for batches of several waves per SIMD (262144 strings: 0.70 .. 0.75).  NOT for a selection of a batch (the cascade: 0.92 .. 6.5 — a launch of
+ *                              few strings lasts as long as its longest string's walk) nor for uniformly mixed lengths at 65536 strings (0.94 .. 1.13).
  * Applies to later calls; hrx_ctx_clone copies the options.  hrx_ctx_get_option: the value, -1 for an unknown option. */
-enum { HRX_OPT_PMD_COMBINER_WAVE = 1, HRX_OPT_HOST_ROUTE = 2, HRX_OPT_HOST_THREADS = 3, HRX_OPT_HOST_PIPELINE = 4, HRX_OPT_PLACE_DRY_LAUNCH = 5 };
+enum { HRX_OPT_PMD_COMBINER_WAVE = 1, HRX_OPT_HOST_ROUTE = 2, HRX_OPT_HOST_THREADS = 3, HRX_OPT_HOST_PIPELINE = 4, HRX_OPT_PLACE_DRY_LAUNCH = 5, HRX_OPT_MATCH_FUSED_WIDE = 6 };
 enum { HRX_HOST_ROUTE_AUTO = 0, HRX_HOST_ROUTE_DEVICE = 1, HRX_HOST_ROUTE_HOST = 2 };
 /* What the context's last hrx_witness_batch_host call did. */
 typedef struct hrx_host_route_report {
@@ -408,7 +416,8 @@ int hrx_witness_batch_host(hrx_ctx *ctx, const uint8_t *chars, size_t stride, co
  * The device entry is asynchronous on `stream`.  Def sets the fused match kernel walks (hrx_ctx_describe_match names it) need no
  * scratch, and the call is then legal inside a stream capture; every other def set goes "via rows": the witness launch into
  * context-owned scratch (at most 1 GiB, allocated at first use: inside a capture before that, HRX_ERR_STATE; HRX_ERR_BOUNDS if one string's
- * witness rows alone would not fit) and a scan of its masked rows.
+ * witness rows alone would not fit) and a scan of its masked rows.  With HRX_OPT_MATCH_FUSED_WIDE = 1 the def sets of four to eight defs that the option
+ * covers have a fused kernel too: no scratch, and the call can be captured on a fresh context.
  * hrx_match_batch_host: HOST buffers, synchronous; on a host-only context the native host walk, otherwise staged through the device. */
 int hrx_match_batch_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M,
                            uint64_t *status, uint32_t *span_counts, uint64_t *spans, size_t max_spans, void *stream);
@@ -433,7 +442,8 @@ int hrx_ctx_describe_match(const hrx_ctx *ctx, int layout, size_t B, size_t M, c
  *   up to round_up(offsets[B], 16) (in general: up to the aligned chunk end of every string's last byte), and it never reads a chunk that
  *   holds no byte of some string of the batch.  Every other argument rule, the asynchronous behaviour and the stream-capture rules are those
  *   of hrx_match_batch_device: where the fused kernel runs (hrx_ctx_describe_match with HRX_LAYOUT_INPUT_RAGGED names it) no scratch is
- *   needed and the launch can be captured; "via rows" uses the context scratch with the same first-use and capture rules.
+ *   needed and the launch can be captured (HRX_OPT_MATCH_FUSED_WIDE = 1: that holds for the four- to eight-def sets the option covers as well); "via rows" uses the
+ *   context scratch with the same first-use and capture rules.
  *   Host entry: host buffers (no alignment rule for values), synchronous.  On a host-only context the native host walk; on a device
  *   context chunks of whole strings whose bytes span about 64 MiB go through the device, each one contiguous byte range plus its offsets
  *   in, status / counts / spans out.
@@ -571,7 +581,7 @@ int hrx_gather_to_position_major_device(hrx_ctx *ctx, int layout, const uint8_t 
  *   ORDER      the strings are walked in sel order: persistent lane g of G takes sel[g], sel[g + G], ...  Order affects time only.
  * The device entry is asynchronous on `stream`; stream-capture and scratch rules are those of hrx_match_batch_device_ragged: def sets with a fused
  * kernel need no scratch and the launch can be captured; "via rows" def sets use the context scratch with the same first-use rule (inside a capture
- * before that: HRX_ERR_STATE).  No atomics: the call is deterministic.  HRX_ERR_HIP on a host-only context (after the argument rules).
+ * before that: HRX_ERR_STATE); HRX_OPT_MATCH_FUSED_WIDE = 1 gives the four- to eight-def sets it covers a fused kernel here too.  No atomics: the call is deterministic.  HRX_ERR_HIP on a host-only context (after the argument rules).
  * Host entry: host buffers, synchronous.  On a host-only context the native host walk over the selection; on a device context chunks of the selection
  * whose strings' bytes sum to about 64 MiB are packed back to back, matched on the device and copied out to index sel[k]: only the selected strings'
  * bytes cross the link.
