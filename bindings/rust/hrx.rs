@@ -28,6 +28,17 @@ pub const HRX_PLACE_CAPPED_TIME: c_int = 4;
 pub const HRX_PLACE_CAPPED_ALLOC: c_int = 8;
 
 pub const HRX_DEVICE_NONE: c_int = -1;
+pub const HRX_VERIFY_FIRST_STATE: u64 = 1;
+pub const HRX_VERIFY_ENABLE: u64 = 2;
+pub const HRX_VERIFY_TRANSITION: u64 = 4;
+pub const HRX_VERIFY_START_LOOKUP: u64 = 8;
+pub const HRX_VERIFY_END_LOOKUP: u64 = 16;
+pub const HRX_VERIFY_ACCEPT: u64 = 32;
+pub const HRX_VERIFY_FLAGS: u64 = 64;
+pub const HRX_VERIFY_PADDING: u64 = 128;
+pub const HRX_VERIFY_MASK: u64 = 256;
+pub const HRX_VERIFY_CIRCUIT_BITS: u64 = 63;   // what MockProver::verify() itself sees
+pub const HRX_VERIFY_ROW_SHIFT: u32 = 32;      // bits 32..56 of a verdict: the lowest failing row
 pub const HRX_MAX_DEFS: usize = 32;   // RegexDefs per config (more than three are walked in passes)
 
 #[link(name = "hrx")]
@@ -198,6 +209,16 @@ extern "C" {
                                     msk_pitch: usize, b: usize, m: usize, d: usize, b_begin: usize, b_count: usize, columns: *mut u64) -> c_int;
     pub fn hrx_fr_columns_device_planes(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32, record_planes: *const *const u32, n_planes: usize,
                                         masked: *const u16, b: usize, m: usize, b_begin: usize, b_count: usize, cells: *mut u64, flags: c_int, stream: *mut c_void) -> c_int;
+    /// VERIFY: one u64 verdict per string (bits 0..8 the failed checks, HRX_VERIFY_*; bits 32..56 the lowest failing row; all ones: n_b > M) for the rows of a
+    /// finished batch, on the device where they lie (one launch after the context's first verify call) or in host memory
+    pub fn hrx_verify_rows_device(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                  records: *const u32, rec_pitch: usize, masked: *const u16, msk_pitch: usize, b: usize, m: usize,
+                                  verdict: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn hrx_verify_rows_device_planes(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32, record_planes: *const *const u32,
+                                         n_planes: usize, masked: *const u16, b: usize, m: usize, verdict: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn hrx_verify_rows_host(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                records: *const u32, rec_pitch: usize, masked: *const u16, msk_pitch: usize, b: usize, m: usize,
+                                verdict: *mut u64) -> c_int;
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

@@ -140,6 +140,9 @@ def _load():
         "hrx_fr_columns_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, sz, sz, vp, i, vp]),
         "hrx_fr_columns_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, vp, sz, sz, sz, sz, vp, i, vp]),
         "hrx_fr_from_u64": (None, [C.c_uint64, i, _u64p]),
+        "hrx_verify_rows_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, vp, vp]),
+        "hrx_verify_rows_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, vp, sz, sz, vp, vp]),
+        "hrx_verify_rows_host": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, vp]),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -1250,6 +1253,70 @@ class RegexVerifyConfig:
                                          FR_CANONICAL if canonical else 0, s.cuda_stream))
         return cells
 
+    def verify_rows(self, chars, lens, records, masked, layout=LAYOUT_STRING_MAJOR, planes=None, rec_pitch=0, msk_pitch=0, out=None, chars_pm_stride=None,
+                    stream=None):
+        """hrx_verify_rows_device / _planes: do the witness rows of a finished batch satisfy the circuit?  (B,) int64 CUDA tensor of verdict words (include/hrx.h VERIFY:
+        0 = every gate, lookup and assignment rule holds; bits 0..8 VERIFY_*, bits 32..56 the lowest failing row — verdict_row / explain_verdict; -1: lens[b] > M).
+        chars, lens and `layout` are those of the witness_batch* call that wrote the rows (chars_pm_stride: the flat position-major input and its per-string capacity);
+        records / masked its outputs — string-major views, pitched or not (rec_pitch / msk_pitch in rows, 0: taken from a (B, M, D) / (B, M) view's strides), or the
+        flat position-major buffers; planes: the list of record planes (or the two row stripes of one def) instead of records.  One launch, asynchronous on `stream`
+        (default: torch's current stream); the context's first call also builds and uploads the check tables (not inside a graph capture)."""
+        assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and chars.dtype == torch.uint8
+        B, M, D = lens.numel(), self.max_chars_size, self.num_defs
+        if chars_pm_stride is not None:
+            stride = int(chars_pm_stride)
+            assert layout & LAYOUT_INPUT_POSITION_MAJOR and chars.is_contiguous()
+        else:
+            assert not layout & LAYOUT_INPUT_POSITION_MAJOR and chars.stride(1) == 1
+            stride = chars.stride(0)
+        if out is None:
+            out = torch.empty((B,), dtype=torch.int64, device=lens.device)
+        elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != B:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous int64 tensor of %d elements" % B)
+        s = torch.cuda.current_stream(lens.device) if stream is None else stream
+        if planes is not None:
+            arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+            _check(lib.hrx_verify_rows_device_planes(self._need_device(chars, lens, masked, out, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(), arr, len(planes),
+                                                     masked.data_ptr(), B, M, out.data_ptr(), s.cuda_stream))
+            return out
+        if not layout & LAYOUT_POSITION_MAJOR:
+            if not rec_pitch and records.dim() == 3:
+                rec_pitch = records.stride(0) // D
+            if not msk_pitch and masked.dim() == 2:
+                msk_pitch = masked.stride(0)
+        _check(lib.hrx_verify_rows_device(self._need_device(chars, lens, records, masked, out), int(layout), chars.data_ptr(), stride, lens.data_ptr(), records.data_ptr(),
+                                          int(rec_pitch), masked.data_ptr(), int(msk_pitch), B, M, out.data_ptr(), s.cuda_stream))
+        return out
+
+    def verify_rows_host(self, chars, lens, records, masked, layout=LAYOUT_STRING_MAJOR, rec_pitch=0, msk_pitch=0, out=None, chars_pm_stride=None):
+        """hrx_verify_rows_host: verify_rows over numpy arrays in host memory, on a host-only or a device context — the same rules (csrc/hrx_verify.hpp) over host
+        threads; (B,) uint64.  String-major records (B, M, D) / masked (B, M) / chars (B, stride), pitched views included, or the flat position-major buffers."""
+        lens = np.ascontiguousarray(lens, np.uint32)
+        B, M, D = len(lens), self.max_chars_size, self.num_defs
+        ch = np.asarray(chars)
+        rec, msk = np.asarray(records), np.asarray(masked)
+        if layout & LAYOUT_POSITION_MAJOR:
+            rec, msk = np.ascontiguousarray(rec), np.ascontiguousarray(msk)
+        else:
+            if not rec_pitch and rec.ndim == 3:
+                assert rec.strides[2] == 4 and rec.strides[1] == 4 * D
+                rec_pitch = rec.strides[0] // (4 * D)
+            if not msk_pitch and msk.ndim == 2:
+                assert msk.strides[1] == 2
+                msk_pitch = msk.strides[0] // 2
+        if chars_pm_stride is not None:
+            stride, ch = int(chars_pm_stride), np.ascontiguousarray(ch)
+        else:
+            assert ch.ndim == 2 and ch.strides[1] == 1
+            stride = ch.strides[0]
+        if out is None:
+            out = np.empty(B, np.uint64)
+        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != B:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of %d elements" % B)
+        _check(lib.hrx_verify_rows_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch), msk.ctypes.data,
+                                        int(msk_pitch), B, M, out.ctypes.data))
+        return out
+
     def witness_batch(self, chars, lens, out=None, stream=None):
         """Device-resident batch: chars (B, stride) uint8 CUDA tensor (stride % 16 == 0), lens (B,) int32 CUDA tensor.
         Asynchronous on `stream` (default: torch's current stream).  Returns (records, masked, status) tensors whose
@@ -1267,6 +1334,32 @@ class RegexVerifyConfig:
                                                     self.max_chars_size, rec.data_ptr(), rec.stride(0) // D,
                                                     msk.data_ptr(), msk.stride(0), st.data_ptr(), s.cuda_stream))
         return rec, msk, st
+
+
+# VERIFY (include/hrx.h): the check bits of a verdict word, the values tests/mock_prover.py gives them
+VERIFY_FIRST_STATE, VERIFY_ENABLE, VERIFY_TRANSITION, VERIFY_START_LOOKUP, VERIFY_END_LOOKUP, VERIFY_ACCEPT = 1, 2, 4, 8, 16, 32
+VERIFY_FLAGS, VERIFY_PADDING, VERIFY_MASK = 64, 128, 256
+VERIFY_CIRCUIT_BITS = 63               # what MockProver::verify() itself sees
+VERIFY_ROW_SHIFT = 32
+VERIFY_NAMES = {VERIFY_FIRST_STATE: "first-state gate", VERIFY_ENABLE: "enable gate", VERIFY_TRANSITION: "transition lookup",
+                VERIFY_START_LOOKUP: "start lookup", VERIFY_END_LOOKUP: "end lookup", VERIFY_ACCEPT: "accept chain",
+                VERIFY_FLAGS: "flag completeness", VERIFY_PADDING: "padding", VERIFY_MASK: "masked rows"}
+
+
+def verdict_row(v):
+    """the lowest row at which a reported check of verdict word v fails (0 when none does; None: the string is longer than max_chars_size and has no rows)"""
+    v = int(v) & 0xffffffffffffffff
+    return None if v == 0xffffffffffffffff else (v >> VERIFY_ROW_SHIFT) & 0x1ffffff
+
+
+def explain_verdict(v):
+    """a verdict word in words: "ok", or the failed checks and the lowest failing row"""
+    v = int(v) & 0xffffffffffffffff
+    if v == 0:
+        return "ok"
+    if v == 0xffffffffffffffff:
+        return "longer than max_chars_size"
+    return " + ".join(name for bit, name in VERIFY_NAMES.items() if v & bit) + " at row %d" % verdict_row(v)
 
 
 FR_CANONICAL = 1                       # HRX_FR_CANONICAL

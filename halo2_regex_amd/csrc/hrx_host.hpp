@@ -177,6 +177,23 @@ class RegexVerifyConfig {
         check(hrx_extract_spans_device(ctx_, layout, src, stride, offsets, B, status, span_counts, spans, max_spans, require_accept, &out, workspace, workspace_bytes, stream));
     }
 
+    // VERIFY (include/hrx.h): one verdict word per string for rows in host memory (string-major with pitches in rows, 0 = M; or position-major), and the device
+    // forms as they are (device pointers, asynchronous on `stream`)
+    std::vector<uint64_t> verify_rows_host(int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
+                                           const uint16_t *masked, size_t msk_pitch, size_t B) const {
+        std::vector<uint64_t> verdict(B);
+        check(hrx_verify_rows_host(ctx_, layout, chars, stride, lens, records, rec_pitch, masked, msk_pitch, B, max_chars_size_, verdict.data()));
+        return verdict;
+    }
+    void verify_rows_device(int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch, const uint16_t *masked,
+                            size_t msk_pitch, size_t B, uint64_t *verdict, void *stream) const {
+        check(hrx_verify_rows_device(ctx_, layout, chars, stride, lens, records, rec_pitch, masked, msk_pitch, B, max_chars_size_, verdict, stream));
+    }
+    void verify_rows_device_planes(int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *const *record_planes, size_t n_planes,
+                                   const uint16_t *masked, size_t B, uint64_t *verdict, void *stream) const {
+        check(hrx_verify_rows_device_planes(ctx_, layout, chars, stride, lens, record_planes, n_planes, masked, B, max_chars_size_, verdict, stream));
+    }
+
    private:
     static std::vector<std::vector<uint64_t>> split(const std::vector<uint64_t> &f, size_t D, size_t len) {
         std::vector<std::vector<uint64_t>> o(D);

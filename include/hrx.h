@@ -621,6 +621,51 @@ int hrx_fr_columns_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars,
 void hrx_fr_from_u64(uint64_t v, int flags, uint64_t *limbs);
 
 /* ------------------------------------------------------------------ */
+/* VERIFY — do these witness rows satisfy the circuit?  (what MockProver::verify() says of a witness, src/lib.rs:1086 ...) */
+/* ------------------------------------------------------------------ */
+/* Every gate and lookup of RegexVerifyConfig::configure (src/lib.rs:126-305) and the accept chain (lib.rs:427-457), evaluated over plain integers on the
+ * compact rows of a finished batch — rows kept between runs, produced on another device or under a context option, read back after a fault — plus three
+ * checks beyond what verify() sees, which pin the rest of the assignment.  One u64 verdict per string, 0 = every check holds:
+ *   bits 0..8   the checks that fail
+ *     HRX_VERIFY_FIRST_STATE   gate "The state must start from the first state value"   lib.rs:173-191
+ *     HRX_VERIFY_ENABLE        gate "The transition of enable flags"                    lib.rs:193-205  (enable is [r < n_b]: cannot fail; kept gate for gate)
+ *     HRX_VERIFY_TRANSITION    lookup "characters and their state"                      lib.rs:207-233
+ *     HRX_VERIFY_START_LOOKUP  lookup "start_state of substring"                        lib.rs:235-259
+ *     HRX_VERIFY_END_LOOKUP    lookup "end_state of substring"                          lib.rs:261-284
+ *     HRX_VERIFY_ACCEPT        accept chain: the state where enable drops is the accepted one   lib.rs:427-457
+ *     (these six are HRX_VERIFY_CIRCUIT_BITS: what verify() itself sees; with n_b == M the transition and end lookups of row M - 1 read a cell
+ *      match_substrs never assigns and are left out)
+ *     HRX_VERIFY_FLAGS         start_enable / end_enable are exactly derive_is_start_end's (lib.rs:847-888) gated by enable (lib.rs:482-519)
+ *     HRX_VERIFY_PADDING       rows from n_b on hold no tag and no flag, rows after n_b the dummy state (lib.rs:387-418); no flag bit above the two
+ *     HRX_VERIFY_MASK          masked rows = the reveal gates (lib.rs:593-764) evaluated on the records' own sums; not reported for a string in which
+ *                              two defs flag one row (out of contract)
+ *   bits 32..56 the lowest row at which any reported check fails (0 when none does).  A check belongs to the row r whose record, masked cell or
+ *               Rotation::next pair (r, r + 1) it reads; the accept chain to the row where enable drops; the first-state gate to row 0
+ *   everything else 0.  n_b > M: all ones (the string has no rows).
+ * The fixed tables are the rows RegexTableConfig::load assigns (hrx_table_transition_rows / hrx_table_endpoint_rows), never a walk's table: the
+ * checker shares nothing with the kernels whose rows it judges.  They are built — and for the device forms uploaded — at the context's FIRST verify
+ * call: inside a stream capture before that the device forms return HRX_ERR_STATE; afterwards a call is one kernel launch, asynchronous on `stream`,
+ * and capturable.
+ * `layout`, chars / stride / lens, records / masked (rec_pitch / msk_pitch string-major only, in rows; 0 = M) and the record planes are those of the
+ * hrx_witness_batch_device* call that wrote the rows, at that section's alignments (and stride % 16 == 0); M <= 2^24; planes only with a
+ * position-major layout, one per def (at most eight) or the two row stripes of one def.  verdict: [B] u64, 8-byte aligned.  A refused call writes
+ * nothing.  The launch reads 1 + 4 D + 2 bytes per row once and writes 8 bytes per string. */
+enum { HRX_VERIFY_FIRST_STATE = 1, HRX_VERIFY_ENABLE = 2, HRX_VERIFY_TRANSITION = 4, HRX_VERIFY_START_LOOKUP = 8, HRX_VERIFY_END_LOOKUP = 16,
+       HRX_VERIFY_ACCEPT = 32, HRX_VERIFY_FLAGS = 64, HRX_VERIFY_PADDING = 128, HRX_VERIFY_MASK = 256,
+       HRX_VERIFY_CIRCUIT_BITS = 63, HRX_VERIFY_ROW_SHIFT = 32 };
+int hrx_verify_rows_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                           const uint32_t *records, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch,
+                           size_t B, size_t M, uint64_t *verdict, void *stream);
+int hrx_verify_rows_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                  const uint32_t *const *record_planes, size_t n_planes, const uint16_t *masked,
+                                  size_t B, size_t M, uint64_t *verdict, void *stream);
+/* The same rules over rows in HOST memory (as hrx_witness_columns_host takes them: string-major with pitches, or position-major as copied from the
+ * device), on a host-only or a device context, over HRX_OPT_HOST_THREADS threads by ranges of strings.  The definition of the verdict word. */
+int hrx_verify_rows_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                         const uint32_t *records, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch,
+                         size_t B, size_t M, uint64_t *verdict);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */
 /* ------------------------------------------------------------------ */
 /* One circuit: EXACTLY the Vecs the three derive_* calls at the top of match_substrs return (src/lib.rs:316-318), out of the string's compact records, so that the body
