@@ -2,7 +2,8 @@
 // built with -fsanitize=address,undefined by tests/test_verify_cpu.py.  Every array is a heap block of exactly its size, so one element too far is a sanitizer
 // error.  The rows are hand-made: three small DFAs over {a, b} whose table rows are written out below, a walk of them in the words of src/lib.rs (states,
 // substr ids, start / end flags, padding), and the masked rows from the two "last event wins" scans of lib.rs:593-764 as arrays, forward and backward — not
-// from the one-pass rule under test.  Checked: clean rows give 0 (or exactly the accept chain at row n), every tampered cell its check and its row, the
+// from the one-pass rule under test.  Checked: clean rows give 0 (or exactly the accept chain at row n), every tampered cell its check and its row, values
+// outside every table (in one to five defs, with the image a heap block of exactly its size) the check that pins them and no read outside the image, the
 // string-major, pitched and position-major images of the same rows the same words, and the kernel's tile loop (verify_lane, every instantiation the
 // kernel uses) the same words as the row-by-row loop.
 #include <cstdio>
@@ -295,6 +296,44 @@ static void tampered_rows() {
     EXPECT(bits_of(v) == kVfyTransition && row_of(v) == 62);
 }
 
+// values outside every table — the state 0xffff, the tag 0xff, flag bit 31, each alone, with a start and an end flag beside it, and all of them at once — in every def
+// of one to five defs, at rows on both sides of the borders of every tile size, of n and of M.  The image is a heap block of exactly its size (word_of), so a lookup
+// that verify_def_look did not clamp is a sanitizer error; the tile loop of every instantiation the kernel uses must give the row-by-row loop's word, and the word the
+// check that pins the cell: the pair (r - 1, r) or the first-state gate for a state at r <= n, the padding rule behind n and for the flag bit, the transition lookup
+// for a tag below n.
+static void out_of_range_rows(const std::vector<Def> &defs) {
+    const std::vector<uint32_t> img = image_of(defs);
+    const uint32_t D = (uint32_t)defs.size();
+    for (uint32_t M : {33u, 64u, 65u}) {
+        const Rows clean = make_rows(defs, abba(5, 16, 9), M);
+        const uint32_t n = clean.n;
+        const uint64_t v0 = word_of(img, clean);
+        EXPECT(v0 == (clean.accepted_all ? 0 : (uint64_t)kVfyAccept | (uint64_t)n << 32));
+        for (uint32_t d = 0; d < D; ++d)
+            for (uint32_t r : {0u, 1u, 5u, 7u, 8u, 15u, 16u, 17u, 20u, n - 1, n, 31u, 32u, M - 2, M - 1})
+                for (int kind = 0; kind < 6; ++kind) {
+                    Rows R = clean;
+                    uint32_t &x = R.rec[(size_t)r * D + d];
+                    uint32_t bit = 0;
+                    if (kind == 0 || kind == 3) { x = (x & 0xffff0000u) | 0xffffu; bit = r == 0 ? kVfyFirstState : r <= n ? kVfyTransition : kVfyPadding; }
+                    if (kind == 1 || kind == 4) { x |= 0xffu << 16; bit = r < n ? kVfyTransition : kVfyPadding; }
+                    if (kind == 2) { x |= 1u << 31; bit = kVfyPadding; }
+                    if (kind == 3 || kind == 4) x |= 3u << 24;          // the start and the end lookup run on the value that is out of range
+                    if (kind == 5) { x = 0xffffffffu; bit = kVfyPadding; }
+                    const uint64_t v = word_of(img, R);
+                    if (!(bits_of(v) & bit) || (v >> 57) != 0 || row_of(v) > r)
+                        std::printf("out of range: M %u D %u def %u row %u kind %d: %llx\n", M, D, d, r, kind, (unsigned long long)v);
+                    EXPECT((bits_of(v) & bit) && (v >> 57) == 0 && row_of(v) <= r);
+                }
+        for (uint32_t r : {0u, 7u, 8u, 31u, 32u, M - 1}) {             // a masked cell of all ones
+            Rows R = clean;
+            R.msk[r] = 0xffffu;
+            const uint64_t v = word_of(img, R);
+            EXPECT((bits_of(v) & kVfyMask) && row_of(v) <= r);
+        }
+    }
+}
+
 // the same rows as a string-major, a pitched and a position-major image through verify_rows_host (threads included), B strings of every length class
 static void images(const std::vector<Def> &defs, uint32_t M, size_t B) {
     const std::vector<uint32_t> image = image_of(defs);
@@ -355,6 +394,7 @@ int main() {
                            five = {kDef1, kDef3, kDef2, kDef3, kDef3};
     for (const auto *defs : {&one, &two, &three, &four, &five}) clean_rows(*defs);
     tampered_rows();
+    for (const auto *defs : {&one, &two, &three, &four, &five}) out_of_range_rows(*defs);
     for (uint32_t M : {1u, 7u, 64u, 65u}) {
         images(one, M, 11);
         images(two, M, 130);

@@ -189,7 +189,8 @@ def test_contract_of_the_host_form():
 
 def test_standalone_program_under_the_sanitizers(tmp_path):
     """tests/host_cpp/test_verify_host.cpp: csrc/hrx_verify.hpp + csrc/hrx_verify_host.cpp compiled into a program of their own with the address and
-    undefined-behaviour sanitizers — hand-made rows at M = 1, 7, 64, 65, n = 0 .. M, every image of them, the kernel's tile loop on the host"""
+    undefined-behaviour sanitizers — hand-made rows at M = 1, 7, 64, 65, n = 0 .. M, every image of them, the kernel's tile loop on the host; states, tags and
+    flags outside every table in one to five defs at M = 33, 64, 65, in every instantiation of the tile loop the kernel uses, the image a heap block of its exact size"""
     exe = str(tmp_path / "hrx_test_verify_host")
     subprocess.check_call(["g++", "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
                            os.path.join(ROOT, "tests", "host_cpp", "test_verify_host.cpp"), "-o", exe, "-pthread"])

@@ -136,6 +136,108 @@ class Rows:
         t, i = self._msk_cell(b, r)
         return int(t[i]) & 0xffff
 
+    # many cells at once (numpy index arrays in, flat indices into a buffer's whole storage out): the rows behind M of a pitched string's slot and of a
+    # position-major buffer's last quad / octet can be addressed too
+    def rec_buffers(self):
+        if self.planes is not None:
+            return list(self.planes)
+        return [self.rec.as_strided((self.B * self.rec.stride(0),), (1,))] if self.layout == hra.LAYOUT_STRING_MAJOR else [self.rec]
+
+    def msk_buffer(self):
+        return self.msk.as_strided((self.B * self.msk.stride(0),), (1,)) if self.layout == hra.LAYOUT_STRING_MAJOR else self.msk
+
+    def chr_buffer(self):
+        return self.src.view(-1)
+
+    def _block(self, b):
+        k = b // hra.PM_BLOCK
+        return k, b % hra.PM_BLOCK, np.minimum(hra.PM_BLOCK, self.B - k * hra.PM_BLOCK)
+
+    def rec_cells(self, b, r, d):
+        """(number of the buffer of rec_buffers(), index into it) of the records (b, r, d)"""
+        b, r, d = (np.asarray(a, np.int64) for a in (b, r, d))
+        M, D = self.M, self.D
+        if self.layout == hra.LAYOUT_STRING_MAJOR:
+            return np.zeros(len(b), np.int64), (b * (self.rec.stride(0) // D) + r) * D + d
+        (k, bl, nb), q4 = self._block(b), (M + 3) // 4
+        if self.planes is None:
+            return np.zeros(len(b), np.int64), k * hra.PM_BLOCK * q4 * D * 4 + ((r // 4 * D + d) * nb + bl) * 4 + r % 4
+        R = len(self.planes) // D
+        q, slots = r // 4, (q4 + R - 1) // R
+        return (q % R) * D + d, k * hra.PM_BLOCK * slots * 4 + ((q // R) * nb + bl) * 4 + r % 4
+
+    def msk_cells(self, b, r):
+        b, r = np.asarray(b, np.int64), np.asarray(r, np.int64)
+        if self.layout == hra.LAYOUT_STRING_MAJOR:
+            return b * self.msk.stride(0) + r
+        k, bl, nb = self._block(b)
+        return k * hra.PM_BLOCK * ((self.M + 7) // 8) * 8 + (r // 8 * nb + bl) * 8 + r % 8
+
+    def chr_cells(self, b, r):
+        """input byte r of string b in the buffer verify reads: chunk r / 16 of a block of nb strings where the input is position-major"""
+        b, r = np.asarray(b, np.int64), np.asarray(r, np.int64)
+        if not self.layout & hra.LAYOUT_INPUT_POSITION_MAJOR:
+            return b * self.stride + r
+        k, bl, nb = self._block(b)
+        return k * hra.PM_BLOCK * self.stride + ((r // 16) * nb + bl) * 16 + r % 16
+
+    def update(self, bufs, which, idx, keep, flip):
+        """buf[idx] = (buf[idx] & keep) ^ flip: per buffer one indexed read and one indexed write; every index is checked against the buffer's size here, on the host"""
+        which, idx, keep, flip = (np.asarray(a, np.int64) for a in (which, idx, keep, flip))
+        for j, t in enumerate(bufs):
+            sel = np.nonzero(which == j)[0]
+            if not len(sel):
+                continue
+            i = idx[sel]
+            assert 0 <= i.min() and i.max() < t.numel() and len(np.unique(i)) == len(i), self.form
+            u, s = {1: (np.uint8, np.uint8), 2: (np.uint16, np.int16), 4: (np.uint32, np.int32)}[t.element_size()]
+            ti = torch.from_numpy(i).to(DEV)
+            new = (t[ti].cpu().numpy().view(u) & keep[sel].astype(u)) ^ flip[sel].astype(u)
+            t[ti] = torch.from_numpy(new.view(s)).to(DEV)
+        torch.cuda.synchronize()
+
+    def apply(self, cat):
+        """every mutation of a verify_cases.Catalogue on the device copy, addressed as this form lays the cells out"""
+        b, r, d, keep, flip = cat.cells("rec")
+        which, idx = self.rec_cells(b, r, d)
+        self.update(self.rec_buffers(), which, idx, keep, flip)
+        b, r, d, keep, flip = cat.cells("msk")
+        self.update([self.msk_buffer()], np.zeros(len(b)), self.msk_cells(b, r), keep, flip)
+        b, r, d, keep, flip = cat.cells("chr")
+        self.update([self.chr_buffer()], np.zeros(len(b)), self.chr_cells(b, r), keep, flip)
+
+    def poison_unjudged(self, rec_value, msk_value, chr_value):
+        """the cells verify must never judge, all strings at once: the rows M .. of the last quad (records, every def) and of the last octet (masked rows) of a
+        position-major form, the rows M .. pitch - 1 of a pitched string's slot, the input bytes n .. stride - 1.  Returns how many cells of each kind there were."""
+        B, M, D = self.B, self.M, self.D
+        if self.layout == hra.LAYOUT_STRING_MAJOR:
+            rec_end, msk_end = self.rec.stride(0) // D, self.msk.stride(0)
+        else:
+            rec_end, msk_end = (M + 3) // 4 * 4, (M + 7) // 8 * 8
+        count = {}
+        b, r, d = (a.reshape(-1) for a in np.meshgrid(np.arange(B), np.arange(M, rec_end), np.arange(D), indexing="ij"))
+        count["rec"] = len(b)
+        which, idx = self.rec_cells(b, r, d)
+        self.update(self.rec_buffers(), which, idx, np.zeros(len(b)), np.full(len(b), rec_value))
+        b, r = (a.reshape(-1) for a in np.meshgrid(np.arange(B), np.arange(M, msk_end), indexing="ij"))
+        count["msk"] = len(b)
+        self.update([self.msk_buffer()], np.zeros(len(b)), self.msk_cells(b, r), np.zeros(len(b)), np.full(len(b), msk_value))
+        b, r = np.nonzero(np.arange(self.stride)[None, :] >= self.lens[:, None].astype(np.int64))
+        count["chr"] = len(b)
+        self.update([self.chr_buffer()], np.zeros(len(b)), self.chr_cells(b, r), np.zeros(len(b)), np.full(len(b), chr_value))
+        return count
+
+    def host_chars(self):
+        """the input as verify reads it now, copied out and turned string-major: (B, stride) uint8"""
+        c = self.src.cpu().numpy()
+        if not self.layout & hra.LAYOUT_INPUT_POSITION_MAJOR:
+            return c
+        out = np.empty((self.B, self.stride), np.uint8)
+        for k0 in range(0, self.B, hra.PM_BLOCK):
+            nb = min(hra.PM_BLOCK, self.B - k0)
+            out[k0:k0 + nb] = c[k0 * self.stride:(k0 + nb) * self.stride].reshape(self.stride // 16, nb, 16).transpose(1, 0, 2).reshape(nb, self.stride)
+        return out
+
 
 def torch_bits(cfg, rows, rec, msk):
     mp = IntegerMockProver.from_config(cfg)
