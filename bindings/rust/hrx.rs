@@ -219,6 +219,20 @@ extern "C" {
     pub fn hrx_verify_rows_host(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
                                 records: *const u32, rec_pitch: usize, masked: *const u16, msk_pitch: usize, b: usize, m: usize,
                                 verdict: *mut u64) -> c_int;
+    /// the same verdict words from chunks of `chunk_rows` rows (a multiple of 32; 0: hrx_ctx_verify_chunk_rows), so that few long strings fill the device:
+    /// two launches and a caller-supplied workspace of hrx_verify_chunked_workspace_bytes
+    pub fn hrx_verify_chunked_workspace_bytes(b: usize, m: usize, chunk_rows: usize) -> usize;
+    pub fn hrx_ctx_verify_chunk_rows(ctx: *mut hrx_ctx, b: usize, m: usize) -> usize;
+    pub fn hrx_verify_rows_chunked_device(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                          records: *const u32, rec_pitch: usize, masked: *const u16, msk_pitch: usize, b: usize, m: usize,
+                                          chunk_rows: usize, workspace: *mut c_void, workspace_bytes: usize, verdict: *mut u64, stream: *mut c_void) -> c_int;
+    pub fn hrx_verify_rows_chunked_device_planes(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                                 record_planes: *const *const u32, n_planes: usize, masked: *const u16, b: usize, m: usize,
+                                                 chunk_rows: usize, workspace: *mut c_void, workspace_bytes: usize, verdict: *mut u64,
+                                                 stream: *mut c_void) -> c_int;
+    pub fn hrx_verify_rows_chunked_host(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                        records: *const u32, rec_pitch: usize, masked: *const u16, msk_pitch: usize, b: usize, m: usize,
+                                        chunk_rows: usize, verdict: *mut u64) -> c_int;
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

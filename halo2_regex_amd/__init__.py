@@ -143,6 +143,11 @@ def _load():
         "hrx_verify_rows_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, vp, vp]),
         "hrx_verify_rows_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, vp, sz, sz, vp, vp]),
         "hrx_verify_rows_host": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, vp]),
+        "hrx_verify_chunked_workspace_bytes": (sz, [sz, sz, sz]),
+        "hrx_ctx_verify_chunk_rows": (sz, [vp, sz, sz]),
+        "hrx_verify_rows_chunked_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, sz, vp, sz, vp, vp]),
+        "hrx_verify_rows_chunked_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, vp, sz, sz, sz, vp, sz, vp, vp]),
+        "hrx_verify_rows_chunked_host": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, sz, vp]),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -1253,14 +1258,21 @@ class RegexVerifyConfig:
                                          FR_CANONICAL if canonical else 0, s.cuda_stream))
         return cells
 
+    def verify_chunk_rows(self, B, M=None):
+        """hrx_ctx_verify_chunk_rows: the chunk the context picks for B strings of M rows (default: max_chars_size); >= M: one chunk, the plain launch is the better call"""
+        return int(lib.hrx_ctx_verify_chunk_rows(self._need_ctx(), int(B), int(self.max_chars_size if M is None else M)))
+
     def verify_rows(self, chars, lens, records, masked, layout=LAYOUT_STRING_MAJOR, planes=None, rec_pitch=0, msk_pitch=0, out=None, chars_pm_stride=None,
-                    stream=None):
+                    stream=None, chunk_rows=None, workspace=None):
         """hrx_verify_rows_device / _planes: do the witness rows of a finished batch satisfy the circuit?  (B,) int64 CUDA tensor of verdict words (include/hrx.h VERIFY:
         0 = every gate, lookup and assignment rule holds; bits 0..8 VERIFY_*, bits 32..56 the lowest failing row — verdict_row / explain_verdict; -1: lens[b] > M).
         chars, lens and `layout` are those of the witness_batch* call that wrote the rows (chars_pm_stride: the flat position-major input and its per-string capacity);
         records / masked its outputs — string-major views, pitched or not (rec_pitch / msk_pitch in rows, 0: taken from a (B, M, D) / (B, M) view's strides), or the
         flat position-major buffers; planes: the list of record planes (or the two row stripes of one def) instead of records.  One launch, asynchronous on `stream`
-        (default: torch's current stream); the context's first call also builds and uploads the check tables (not inside a graph capture)."""
+        (default: torch's current stream); the context's first call also builds and uploads the check tables (not inside a graph capture).
+        chunk_rows: None — that one launch; 0 or a multiple of 32 — hrx_verify_rows_chunked_device / _planes: the same words from chunks of that many rows (0: the
+        context's pick, verify_chunk_rows), so that few long strings fill the device; two launches and a workspace of verify_chunked_workspace_bytes(B, M, chunk_rows)
+        bytes — `workspace`, any contiguous CUDA tensor of at least that size, or one allocated here."""
         assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and chars.dtype == torch.uint8
         B, M, D = lens.numel(), self.max_chars_size, self.num_defs
         if chars_pm_stride is not None:
@@ -1274,6 +1286,27 @@ class RegexVerifyConfig:
         elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != B:
             raise HrxError(HRX_ERR_ARG, "out: a contiguous int64 tensor of %d elements" % B)
         s = torch.cuda.current_stream(lens.device) if stream is None else stream
+        if chunk_rows is not None:
+            chunk_rows = int(chunk_rows)
+            need = verify_chunked_workspace_bytes(B, M, chunk_rows if chunk_rows else self.verify_chunk_rows(B))
+            if workspace is None:
+                workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=lens.device)
+            ws_bytes = workspace.numel() * workspace.element_size()
+            if planes is not None:
+                arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+                _check(lib.hrx_verify_rows_chunked_device_planes(self._need_device(chars, lens, masked, out, workspace, *planes), int(layout), chars.data_ptr(), stride,
+                                                                 lens.data_ptr(), arr, len(planes), masked.data_ptr(), B, M, chunk_rows, workspace.data_ptr(), ws_bytes,
+                                                                 out.data_ptr(), s.cuda_stream))
+                return out
+            if not layout & LAYOUT_POSITION_MAJOR:
+                if not rec_pitch and records.dim() == 3:
+                    rec_pitch = records.stride(0) // D
+                if not msk_pitch and masked.dim() == 2:
+                    msk_pitch = masked.stride(0)
+            _check(lib.hrx_verify_rows_chunked_device(self._need_device(chars, lens, records, masked, out, workspace), int(layout), chars.data_ptr(), stride, lens.data_ptr(),
+                                                      records.data_ptr(), int(rec_pitch), masked.data_ptr(), int(msk_pitch), B, M, chunk_rows, workspace.data_ptr(), ws_bytes,
+                                                      out.data_ptr(), s.cuda_stream))
+            return out
         if planes is not None:
             arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
             _check(lib.hrx_verify_rows_device_planes(self._need_device(chars, lens, masked, out, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(), arr, len(planes),
@@ -1288,9 +1321,10 @@ class RegexVerifyConfig:
                                           int(rec_pitch), masked.data_ptr(), int(msk_pitch), B, M, out.data_ptr(), s.cuda_stream))
         return out
 
-    def verify_rows_host(self, chars, lens, records, masked, layout=LAYOUT_STRING_MAJOR, rec_pitch=0, msk_pitch=0, out=None, chars_pm_stride=None):
+    def verify_rows_host(self, chars, lens, records, masked, layout=LAYOUT_STRING_MAJOR, rec_pitch=0, msk_pitch=0, out=None, chars_pm_stride=None, chunk_rows=None):
         """hrx_verify_rows_host: verify_rows over numpy arrays in host memory, on a host-only or a device context — the same rules (csrc/hrx_verify.hpp) over host
-        threads; (B,) uint64.  String-major records (B, M, D) / masked (B, M) / chars (B, stride), pitched views included, or the flat position-major buffers."""
+        threads; (B,) uint64.  String-major records (B, M, D) / masked (B, M) / chars (B, stride), pitched views included, or the flat position-major buffers.
+        chunk_rows: None — that call; 0 or a multiple of 32 — hrx_verify_rows_chunked_host, the same words from the chunk walk and fold over (string, chunk) pairs."""
         lens = np.ascontiguousarray(lens, np.uint32)
         B, M, D = len(lens), self.max_chars_size, self.num_defs
         ch = np.asarray(chars)
@@ -1313,6 +1347,10 @@ class RegexVerifyConfig:
             out = np.empty(B, np.uint64)
         elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != B:
             raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of %d elements" % B)
+        if chunk_rows is not None:
+            _check(lib.hrx_verify_rows_chunked_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch),
+                                                    msk.ctypes.data, int(msk_pitch), B, M, int(chunk_rows), out.ctypes.data))
+            return out
         _check(lib.hrx_verify_rows_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch), msk.ctypes.data,
                                         int(msk_pitch), B, M, out.ctypes.data))
         return out
@@ -1344,6 +1382,11 @@ VERIFY_ROW_SHIFT = 32
 VERIFY_NAMES = {VERIFY_FIRST_STATE: "first-state gate", VERIFY_ENABLE: "enable gate", VERIFY_TRANSITION: "transition lookup",
                 VERIFY_START_LOOKUP: "start lookup", VERIFY_END_LOOKUP: "end lookup", VERIFY_ACCEPT: "accept chain",
                 VERIFY_FLAGS: "flag completeness", VERIFY_PADDING: "padding", VERIFY_MASK: "masked rows"}
+
+
+def verify_chunked_workspace_bytes(B, M, chunk_rows):
+    """hrx_verify_chunked_workspace_bytes: the workspace of a chunked verify call; 0: chunk_rows is 0 or no multiple of 32"""
+    return int(lib.hrx_verify_chunked_workspace_bytes(int(B), int(M), int(chunk_rows)))
 
 
 def verdict_row(v):

@@ -455,5 +455,7 @@ hipError_t launch_fr_columns(const FrArgs &a, hipStream_t stream);
 // VERIFY (hrx_kernel_verify.hip): the rules of hrx_verify.hpp over the rows FrArgs describes; one verdict word per string
 struct VerifyArgs;     // hrx_verify.hpp
 hipError_t launch_verify_rows(const VerifyArgs &a, hipStream_t stream);
+struct VerifyChunkArgs;
+hipError_t launch_verify_chunked(const VerifyChunkArgs &ca, hipStream_t stream);      // the chunk launch, then the stitch launch
 
 }  // namespace hrx

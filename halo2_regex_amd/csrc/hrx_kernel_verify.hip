@@ -9,6 +9,10 @@
 //
 // Instantiations: DT = 1, 2, 3, 4 defs with the tile's records in registers (T = 32, 16, 16, 8), and DT = 0 — any number of defs, T = 8, the defs one after the other with
 // the record before the tile read again in place of a carried one — for everything else (five defs and more; planes of five to eight defs).
+//
+// The chunked form (hrx_verify_rows_chunked_device*, below verify_rows_kernel): verify_chunk_kernel — one wave per (64 strings, chunk of the rows), the same
+// tile loop over the chunk's tiles in the same instantiations, a summary of eight words per (string, chunk) into the caller's workspace — and
+// verify_stitch_kernel, one lane per string, which folds the summaries in row order into the same verdict word.  Few long strings fill the device that way.
 #include <hip/hip_runtime.h>
 
 #include "../../include/hrx.h"
@@ -175,7 +179,108 @@ void launch_verify_form(const VerifyArgs &a, hipStream_t stream) {
     }
 }
 
+// ---- the chunked form (hrx_verify_rows_chunked_device*): the same tile loop over one chunk of the rows, then a fold of the chunks' summaries.
+// verify_rows_kernel above shares the loaders with it and nothing else: its text stays as it was.
+
+// the loads behind verify_chunk_lane (hrx_verify.hpp): DeviceTiles' tiles; the row before and the row behind a chunk come as the quad that holds them in the
+// position-major forms (the last and the first record of a quad: one contiguous 1-KiB run per load instruction there too), as one element string-major
+template <int T, int REC>
+struct ChunkTiles {
+    const VerifyArgs &a;
+    const VerifySrc &s;
+    uint32_t n;
+    __device__ __forceinline__ void chars(const uint32_t base, uint32_t (&c)[T]) const { load_chars<T>(s, base, n, c); }
+    __device__ __forceinline__ void masked(const uint32_t base, uint32_t (&mk)[T]) const { load_masked<T, REC != kRecSm>(s, base, a.M, mk); }
+    __device__ __forceinline__ void records(const uint32_t d, const uint32_t base, uint32_t (&x)[T]) const { load_records<T, REC>(a, s, d, base, x); }
+    __device__ __forceinline__ uint32_t record(const uint32_t d, const uint32_t r) const {
+        if constexpr (REC == kRecSm) {
+            return load_record<REC>(a, s, d, r);
+        } else {
+            uint32_t x[4];
+            load_records<4, REC>(a, s, d, r & ~3u, x);
+            const uint32_t i = r & 3u;
+            return i == 0u ? x[0] : i == 1u ? x[1] : i == 2u ? x[2] : x[3];
+        }
+    }
+};
+
+// One wave per (64 consecutive strings, one chunk); workgroup w: strings (w % groups) * 64 .., chunk w / groups — the waves in flight together read the same
+// rows of neighbouring strings.  A summary goes out field by field, word f of (chunk k, string b) at (f K + k) B + b: eight contiguous 256-byte stores per wave.
+template <int DT, int T, int REC>
+__global__ __launch_bounds__(64) void verify_chunk_kernel(const VerifyChunkArgs ca) {
+    const VerifyArgs &a = ca.a;
+    const uint32_t groups = (a.B + 63u) / 64u;
+    const uint32_t k = blockIdx.x / groups, b = (blockIdx.x - k * groups) * 64u + threadIdx.x;
+    if (b >= a.B) return;
+    const uint32_t n = a.lens[b];
+    if (n > a.M) return;       // the string has no rows: verify_stitch_kernel reads no summary of it
+    const uint32_t r0 = k * ca.chunk_rows, r1 = min(a.M, r0 + ca.chunk_rows);
+    const VerifySrc s = verify_src(a, b);
+    const VerifyChunk v = verify_chunk_lane<DT, T>(a.image, a.D, n, a.M, r0, r1, ChunkTiles<T, REC>{a, s, n});
+    const size_t B = a.B, K = ca.K;
+    uint32_t *out = ca.summaries + (size_t)k * B + b;
+    out[0 * K * B] = v.flags;
+    out[1 * K * B] = v.row;
+    out[2 * K * B] = v.mask_row[0];
+    out[3 * K * B] = v.mask_row[1];
+    out[4 * K * B] = v.need1[0];
+    out[5 * K * B] = v.need1[1];
+    out[6 * K * B] = v.need0[0];
+    out[7 * K * B] = v.need0[1];
+}
+
+// One lane per string: its K summaries in row order into the verdict word (verify_fold_chunk), one store
+__global__ __launch_bounds__(64) void verify_stitch_kernel(const VerifyChunkArgs ca) {
+    const VerifyArgs &a = ca.a;
+    const uint32_t b = blockIdx.x * 64u + threadIdx.x;
+    if (b >= a.B) return;
+    if (a.lens[b] > a.M) {
+        a.verdict[b] = ~0ull;
+        return;
+    }
+    const size_t B = a.B, K = ca.K;
+    VerifyAcc acc;
+    verify_begin(acc);
+    for (uint32_t k = 0; k < ca.K; ++k) {
+        const uint32_t *in = ca.summaries + (size_t)k * B + b;
+        VerifyChunk v;
+        v.flags = in[0 * K * B];
+        v.row = in[1 * K * B];
+        v.mask_row[0] = in[2 * K * B];
+        v.mask_row[1] = in[3 * K * B];
+        v.need1[0] = in[4 * K * B];
+        v.need1[1] = in[5 * K * B];
+        v.need0[0] = in[6 * K * B];
+        v.need0[1] = in[7 * K * B];
+        verify_fold_chunk(acc, v);
+    }
+    a.verdict[b] = verify_finish(acc);
+}
+
+template <int REC>
+void launch_chunk_form(const VerifyChunkArgs &ca, hipStream_t stream) {
+    const dim3 grid((ca.a.B + 63u) / 64u * ca.K), block(64);
+    switch (ca.a.D) {
+        case 1: hipLaunchKernelGGL((verify_chunk_kernel<1, 32, REC>), grid, block, 0, stream, ca); break;
+        case 2: hipLaunchKernelGGL((verify_chunk_kernel<2, 16, REC>), grid, block, 0, stream, ca); break;
+        case 3: hipLaunchKernelGGL((verify_chunk_kernel<3, 16, REC>), grid, block, 0, stream, ca); break;
+        case 4: hipLaunchKernelGGL((verify_chunk_kernel<4, 8, REC>), grid, block, 0, stream, ca); break;
+        default: hipLaunchKernelGGL((verify_chunk_kernel<0, 8, REC>), grid, block, 0, stream, ca); break;
+    }
+}
+
 }  // namespace
+
+// the caller has checked chunk_rows, K and that ceil(B / 64) * K workgroups fit a grid
+hipError_t launch_verify_chunked(const VerifyChunkArgs &ca, hipStream_t stream) {
+    if (ca.a.B == 0 || ca.a.M == 0) return hipSuccess;
+    if (!(ca.a.layout & HRX_LAYOUT_POSITION_MAJOR)) launch_chunk_form<kRecSm>(ca, stream);
+    else if (ca.a.records) launch_chunk_form<kRecPm>(ca, stream);
+    else launch_chunk_form<kRecPlanes>(ca, stream);
+    if (const hipError_t e = hipGetLastError(); e != hipSuccess) return e;
+    hipLaunchKernelGGL(verify_stitch_kernel, dim3((ca.a.B + 63u) / 64u), dim3(64), 0, stream, ca);
+    return hipGetLastError();
+}
 
 hipError_t launch_verify_rows(const VerifyArgs &a, hipStream_t stream) {
     if (a.B == 0 || a.M == 0) return hipSuccess;

@@ -3,6 +3,8 @@
 // (hrx_describe_api.cpp) prints one, tests/test_plan_golden_cpu.py holds every choice against a recorded sweep.
 #include "hrx_plan.hpp"
 
+#include <algorithm>
+
 #include "../../include/hrx.h"
 #include "hrx_lane.h"
 
@@ -595,6 +597,19 @@ int plan_batch_route(const DefsSet &s, uint32_t debug, uint32_t tune, bool mp_co
     if (in.n_planes && strict_planes) { err = "record planes: the one-launch def-parallel path does not fit this config"; return HRX_ERR_BOUNDS; }
     in.n_planes = 0;
     return route_class_wide_groups(in, out) ? HRX_OK : route_groups_of_three(in, mp_combine, pm_layout, out, err);
+}
+
+// The chunk of the chunked verify (hrx_ctx_verify_chunk_rows): the fewest chunks K that give every SIMD of the device two waves — ceil(B / 64) K >= 8 CUs
+// (the one- to three-def kernels hold two waves per SIMD) — but never so many that a chunk falls below kVerifyChunkFloor rows (K <= M / floor):
+// a chunk pays for the two rows it reads beside its own, for one summary and for its share of the stitch launch.  The rows are cut evenly, in multiples of
+// 64.  The floor is measured, not derived (tools/verify_bench.py --floor-sweep, NOTES_MEASUREMENTS.md §20).  A result >= M: one chunk, the unchunked launch
+// is the better call.
+size_t plan_verify_chunk_rows(size_t B, size_t M, int num_cus) {
+    if (B == 0 || M == 0) return M;
+    const size_t groups = (B + 63) / 64, want = (size_t)8 * (size_t)(num_cus > 0 ? num_cus : 256);
+    size_t K = groups >= want ? 1 : (want + groups - 1) / groups;
+    K = std::min(K, std::max<size_t>(1, M / kVerifyChunkFloor));
+    return ((M + K - 1) / K + 63) / 64 * 64;
 }
 
 }  // namespace hrx

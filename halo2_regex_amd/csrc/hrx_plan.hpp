@@ -68,4 +68,8 @@ struct BatchRoute {
 int plan_batch_route(const DefsSet &s, uint32_t debug, uint32_t tune, bool mp_combine, int layout, size_t B, size_t M, size_t rec_pitch, int num_cus,
                      size_t n_planes, bool strict_planes, BatchRoute &out, std::string &err);
 
+// ---- the chunked verify's chunk (hrx_ctx_verify_chunk_rows): a multiple of 64 rows; >= M: one chunk
+constexpr size_t kVerifyChunkFloor = 256;
+size_t plan_verify_chunk_rows(size_t B, size_t M, int num_cus);
+
 }  // namespace hrx

@@ -1,6 +1,7 @@
 // hrx_verify.hpp — the rules of VERIFY (include/hrx.h: hrx_verify_rows_device* / hrx_verify_rows_host) that must exist once: which gate, lookup or assignment
 // rule of RegexVerifyConfig::configure (src/lib.rs:126-305), of the accept chain (lib.rs:427-457) and of the reveal gates (lib.rs:593-764) a witness row breaks.
-// No HIP dependency: the kernel (hrx_kernel_verify.hip), the host form (hrx_verify_host.cpp) and tests/host_cpp/test_verify_host.cpp all include it.
+// No HIP dependency: the kernels (hrx_kernel_verify.hip), the host forms (hrx_verify_host.cpp) and tests/host_cpp/test_verify_host.cpp /
+// test_verify_chunk_host.cpp all include it.  The chunked rule — a summary per chunk of a string's rows and a fold of the summaries — follows verify_lane.
 //
 // The checker shares nothing with the walk: its tables are built from the rows RegexTableConfig::load assigns (src/table.rs:61-198; table_transition_rows /
 // table_endpoint_rows of hrx_defs.cpp) and it is handed state[r], state[r + 1], char[r] and the tags of every row, so every lookup stands alone.
@@ -285,6 +286,235 @@ HRX_VFY_UNROLL
     return verify_finish(acc);
 }
 
+// ---- the same verdict out of CHUNKS of a string's rows (hrx_verify_rows_chunked_*): chunk k judges rows [r0, r1) = [k C, min(M, (k + 1) C)) on its own,
+// leaves a summary, and verify_fold_chunk folds the summaries of a string in row order into a VerifyAcc that verify_finish turns into verify_string's word.
+// Every def check is a function of rows r and r + 1 alone: bits, row and overlap fold by OR, min and OR.  The reveal mask carries state both ways:
+//   forward   start_mask at r0 is decided by an event before the chunk, which the chunk cannot see: it runs verify_mask_row's classification under both
+//             hypotheses h = 0, 1 (from prev_sid of row r0 - 1, nothing pending) and leaves mask_row[h], need1[h], need0[h] as they stand at r1, and what its
+//             LAST forward event did to start_mask (the same under both: an event overrides the hypothesis);
+//   backward  rows pending from before the chunk are resolved by its FIRST backward event, which the summary names.
+// A chunk reads rows r0 - 1 .. r1: the row before for prev_sid and the end_enable share of row r0's sums, the row behind for Rotation::next and the sums
+// that decide the backward event at row r1 - 1 (r1 == M: the cell nobody assigns, sums 0).  Rows are absolute, so every min is order-free.
+constexpr uint32_t kVfyChunkAlign = 32;             // chunk_rows is a multiple of this: whole tiles of every T, whole quads, octets and 16-byte input chunks
+constexpr uint32_t kVfyChunkFields = 8;             // u32 words of a summary; the workspace holds them field by field: word f of (chunk k, string b) at (f K + k) B + b
+constexpr uint32_t kVfyEvNone = 0, kVfyEvSet = 1, kVfyEvReset = 2;
+constexpr uint32_t kVfyChunkOverlap = 1u << 9, kVfyChunkFwdShift = 10, kVfyChunkBackShift = 12;
+
+struct VerifyChunk {
+    uint32_t flags;                     // the failed def checks (bits 0..8) | overlap << 9 | last forward event << 10 | first backward event << 12
+    uint32_t row;                       // the lowest row of the failed def checks
+    uint32_t mask_row[2], need1[2], need0[2];       // [h]: as VerifyAcc's, had start_mask been h at r0
+};
+static_assert(sizeof(VerifyChunk) == 4 * kVfyChunkFields, "a summary is kVfyChunkFields words");
+
+// what a chunk's walk carries from row to row: the reveal-mask state once per hypothesis (named halves, not an array: every field stays a register)
+struct VerifyMaskHalf {
+    uint32_t sm, need1, need0, mask_row;            // start_mask under this hypothesis; as VerifyAcc's
+};
+struct VerifyChunkAcc {
+    VerifyAcc d;                        // bits, row, overlap, prev_sid (the def checks write bits and row through verify_def_judge)
+    VerifyMaskHalf h0, h1;
+    uint32_t fwd, back;
+};
+HRX_XHD void verify_chunk_begin(VerifyChunkAcc &A) {
+    verify_begin(A.d);
+    A.h0 = VerifyMaskHalf{0u, kVfyNoRow, kVfyNoRow, kVfyNoRow};
+    A.h1 = VerifyMaskHalf{1u, kVfyNoRow, kVfyNoRow, kVfyNoRow};
+    A.fwd = A.back = kVfyEvNone;
+}
+// verify_mask_row's classification of row r (got: the masked cell, e: what it holds where the mask is 1) ...
+HRX_XHD void verify_half_row(VerifyMaskHalf &H, uint32_t r, uint32_t got, uint32_t e) {
+    if (H.sm && got == 0u) {
+        if (e != 0u) H.need0 = vfy_min(H.need0, r);
+    } else if (H.sm && got == e) {
+        H.need1 = vfy_min(H.need1, r);
+    } else if (got != 0u) {
+        H.mask_row = vfy_min(H.mask_row, r);
+    }
+}
+// ... and its backward event (set: end_mask = 1 back to the previous event; else reset)
+HRX_XHD void verify_half_event(VerifyMaskHalf &H, bool set) {
+    H.mask_row = vfy_min(H.mask_row, set ? H.need0 : H.need1);
+    H.need0 = H.need1 = kVfyNoRow;
+}
+// verify_mask_row under both hypotheses
+HRX_XHD void verify_chunk_mask_row(VerifyChunkAcc &A, uint32_t r, uint32_t c, uint32_t got, uint32_t s, uint32_t sn) {
+    const uint32_t sid = s & 0xffffu, st = (s >> 16) & 0xffu, en = s >> 24;
+    const uint32_t sidn = sn & 0xffffu, stn = (sn >> 16) & 0xffu, enn = sn >> 24;
+    if (st > 1u || en > 1u) A.d.overlap = 1u;
+    if (A.d.prev_sid != sid) {
+        if (st) { A.h0.sm = A.h1.sm = 1u; A.fwd = kVfyEvSet; }
+        else if (en) { A.h0.sm = A.h1.sm = 0u; A.fwd = kVfyEvReset; }
+    }
+    A.d.prev_sid = sid;
+    const uint32_t e = c | sid << 8;
+    verify_half_row(A.h0, r, got, e);
+    verify_half_row(A.h1, r, got, e);
+    if (sidn != sid && (enn || stn)) {
+        verify_half_event(A.h0, enn != 0u);
+        verify_half_event(A.h1, enn != 0u);
+        if (A.back == kVfyEvNone) A.back = enn ? kVfyEvSet : kVfyEvReset;
+    }
+}
+HRX_XHD VerifyChunk verify_chunk_finish(const VerifyChunkAcc &A) {
+    VerifyChunk k;
+    k.flags = A.d.bits | (A.d.overlap ? kVfyChunkOverlap : 0u) | A.fwd << kVfyChunkFwdShift | A.back << kVfyChunkBackShift;
+    k.row = A.d.row;
+    k.mask_row[0] = A.h0.mask_row; k.need1[0] = A.h0.need1; k.need0[0] = A.h0.need0;
+    k.mask_row[1] = A.h1.mask_row; k.need1[1] = A.h1.need1; k.need0[1] = A.h1.need0;
+    return k;
+}
+
+// the next chunk of a string into what the chunks before it left (verify_begin, then every chunk in row order, then verify_finish)
+HRX_XHD void verify_fold_chunk(VerifyAcc &a, const VerifyChunk &k) {
+    a.bits |= k.flags & 511u;
+    a.row = vfy_min(a.row, k.row);
+    a.overlap |= (k.flags >> 9) & 1u;
+    const uint32_t fwd = (k.flags >> kVfyChunkFwdShift) & 3u, back = (k.flags >> kVfyChunkBackShift) & 3u;
+    if (back != kVfyEvNone) {           // the rows pending from the chunks before: judged as verify_mask_row judges them at the event
+        a.mask_row = vfy_min(a.mask_row, back == kVfyEvSet ? a.need0 : a.need1);
+        a.need0 = a.need1 = kVfyNoRow;
+    }
+    const uint32_t h = a.start_mask & 1u;
+    a.mask_row = vfy_min(a.mask_row, h ? k.mask_row[1] : k.mask_row[0]);
+    a.need1 = vfy_min(a.need1, h ? k.need1[1] : k.need1[0]);
+    a.need0 = vfy_min(a.need0, h ? k.need0[1] : k.need0[0]);
+    if (fwd == kVfyEvSet) a.start_mask = 1u;
+    else if (fwd == kVfyEvReset) a.start_mask = 0u;
+}
+
+HRX_XHD uint32_t verify_chunk_count(uint32_t M, uint32_t chunk_rows) { return (M + chunk_rows - 1u) / chunk_rows; }
+// 0: not a chunk size (chunk_rows a positive multiple of kVfyChunkAlign, M in range)
+inline size_t verify_chunked_workspace_bytes(size_t B, size_t M, size_t chunk_rows) {
+    if (chunk_rows == 0 || chunk_rows % kVfyChunkAlign || M == 0 || M > kVfyMaxRows || B > 0xffffffffull - 64) return 0;
+    return (size_t)kVfyChunkFields * 4u * (M / chunk_rows + (M % chunk_rows != 0)) * B;
+}
+
+// rows [r0, r1) of one string of n <= M characters over verify_string's accessor: 0 <= r0 < r1 <= M
+template <class Src>
+inline VerifyChunk verify_chunk_string(const uint32_t *img, uint32_t D, uint32_t n, uint32_t M, uint32_t r0, uint32_t r1, const Src &src) {
+    const VerifyDef *defs = reinterpret_cast<const VerifyDef *>(img);
+    VerifyChunkAcc A;
+    verify_chunk_begin(A);
+    uint32_t s = 0;
+    for (uint32_t d = 0; d < D; ++d) {
+        s += verify_sums_of(src.rec(r0, d), r0 < n);
+        if (r0 > 0) {
+            const uint32_t xb = src.rec(r0 - 1u, d);
+            s += verify_end_sum(xb);
+            A.d.prev_sid += verify_sums_of(xb, r0 - 1u < n) & 0xffffu;
+        }
+    }
+    for (uint32_t r = r0; r < r1; ++r) {
+        const uint32_t c = r < n ? src.chr(r) : 0u;
+        uint32_t sn = 0;
+        for (uint32_t d = 0; d < D; ++d) {
+            const uint32_t x = src.rec(r, d);
+            uint32_t next_state = defs[d].dummy;
+            if (r + 1u < M) {
+                const uint32_t xn = src.rec(r + 1u, d);
+                next_state = xn & 0xffffu;
+                sn += verify_sums_of(xn, r + 1u < n) + verify_end_sum(x);
+            }
+            verify_def_row(img, defs[d], r, n, M, c, x, next_state, A.d);
+        }
+        verify_chunk_mask_row(A, r, c, src.msk(r), s, sn);
+        s = sn;
+    }
+    return verify_chunk_finish(A);
+}
+
+// The chunk as the kernel walks it: verify_lane's tile loop over the tiles of [r0, r1) — r0 a multiple of kVfyChunkAlign, r1 one or M — with the row before
+// the chunk and the row behind it read alone (src.record).  n <= M.
+template <int DT, int T, class Tiles>
+HRX_XHD VerifyChunk verify_chunk_lane(const uint32_t *img, const uint32_t Dn, const uint32_t n, const uint32_t M, const uint32_t r0, const uint32_t r1,
+                                      const Tiles &src) {
+    const uint32_t D = DT ? (uint32_t)DT : Dn;
+    const VerifyDef *defs = reinterpret_cast<const VerifyDef *>(img);
+    VerifyChunkAcc A;
+    verify_chunk_begin(A);
+    uint32_t c_prev = 0, mk_prev = 0, s_prev = 0;
+    uint32_t x_prev[DT ? DT : 1] = {};
+    if (r0 > 0) {                                   // the row before the chunk: its tags are prev_sid, its end flags land on row r0's sums
+        uint32_t sb = 0;
+        if constexpr (DT > 0) {
+HRX_VFY_UNROLL
+            for (int d = 0; d < DT; ++d) { x_prev[d] = src.record((uint32_t)d, r0 - 1u); sb += verify_sums_of(x_prev[d], r0 - 1u < n); }
+        } else {
+            for (uint32_t d = 0; d < D; ++d) sb += verify_sums_of(src.record(d, r0 - 1u), r0 - 1u < n);
+        }
+        A.d.prev_sid = sb & 0xffffu;
+    }
+    for (uint32_t base = r0; base < r1; base += T) {
+        uint32_t c[T], mk[T], x[DT ? DT : 1][T], sums[T];
+        src.chars(base, c);
+        src.masked(base, mk);
+        if constexpr (DT > 0) {
+HRX_VFY_UNROLL
+            for (int d = 0; d < DT; ++d) src.records((uint32_t)d, base, x[d]);
+        }
+HRX_VFY_UNROLL
+        for (int j = 0; j < T; ++j) sums[j] = 0;
+        auto def_tile = [&](const uint32_t d, const uint32_t(&xd)[T], uint32_t xp) {
+            const VerifyDef def = defs[d];
+            uint32_t e[T], sw[T], ew[T];
+HRX_VFY_UNROLL
+            for (int j = 0; j < T; ++j) {
+                const bool live = base + j < M && base + j > r0;
+                const VerifyLook k = verify_def_look(def, live ? (j ? c[j ? j - 1 : 0] : c_prev) : 0u, live ? (j ? xd[j ? j - 1 : 0] : xp) : def.dummy, live ? xd[j] & 0xffffu : 0u);
+                e[j] = img[k.tab]; sw[j] = img[k.start]; ew[j] = img[k.end];
+            }
+HRX_VFY_UNROLL
+            for (int j = 0; j < T; ++j) {
+                const uint32_t rj = base + j;          // the row xd[j] holds; row rj - 1 is judged where it is the chunk's
+                if (rj < M) {
+                    sums[j] += verify_sums_of(xd[j], rj < n);
+                    if (rj > 0) sums[j] += verify_end_sum(xp);
+                    if (rj > r0) verify_def_judge(def, rj - 1u, n, M, xp, xd[j] & 0xffffu, e[j], sw[j], ew[j], A.d);
+                    xp = xd[j];
+                }
+            }
+            return xp;
+        };
+        if constexpr (DT > 0) {
+HRX_VFY_UNROLL
+            for (int d = 0; d < DT; ++d) x_prev[d] = def_tile((uint32_t)d, x[d], x_prev[d]);
+        } else {
+            for (uint32_t d = 0; d < D; ++d) {
+                src.records(d, base, x[0]);
+                def_tile(d, x[0], base ? src.record(d, base - 1u) : 0u);
+            }
+        }
+HRX_VFY_UNROLL
+        for (int j = 0; j < T; ++j) {
+            const uint32_t rj = base + j;
+            if (rj < M) {
+                if (rj > r0) verify_chunk_mask_row(A, rj - 1u, c_prev, mk_prev, s_prev, sums[j]);
+                c_prev = c[j]; mk_prev = mk[j]; s_prev = sums[j];
+            }
+        }
+    }
+    // row r1 - 1 against row r1, or against the cell nobody assigns
+    uint32_t sn = 0;
+    auto last_row = [&](const uint32_t d, const uint32_t xp) {
+        uint32_t next_state = defs[d].dummy;
+        if (r1 < M) {
+            const uint32_t xn = src.record(d, r1);
+            next_state = xn & 0xffffu;
+            sn += verify_sums_of(xn, r1 < n) + verify_end_sum(xp);
+        }
+        verify_def_row(img, defs[d], r1 - 1u, n, M, c_prev, xp, next_state, A.d);
+    };
+    if constexpr (DT > 0) {
+HRX_VFY_UNROLL
+        for (int d = 0; d < DT; ++d) last_row((uint32_t)d, x_prev[d]);
+    } else {
+        for (uint32_t d = 0; d < D; ++d) last_row(d, src.record(d, r1 - 1u));
+    }
+    verify_chunk_mask_row(A, r1 - 1u, c_prev, mk_prev, s_prev, sn);
+    return verify_chunk_finish(A);
+}
+
 // The image of a config out of the rows RegexTableConfig::load assigns: per def transition rows (char, cur, next, substr_id) x n_tr and endpoint rows
 // (substr_id, start, end) x n_ep as table_transition_rows / table_endpoint_rows give them, first_state_val and accepted_state_val.  false: rows a dense
 // table cannot hold (the first row of either table is not the dummy row, a value out of range, two rows with one (char, cur) key that disagree).
@@ -351,6 +581,12 @@ struct VerifyArgs {
     uint64_t rec_pitch, msk_pitch;                  // string-major: rows between consecutive strings
     const uint32_t *image;                          // build_verify_image, on the device
     uint64_t *verdict;
+};
+// ... and the two launches of the chunked form: verify_chunk_kernel writes the summaries, verify_stitch_kernel folds them into a.verdict
+struct VerifyChunkArgs {
+    VerifyArgs a;
+    uint32_t chunk_rows, K;                         // K = verify_chunk_count(a.M, chunk_rows)
+    uint32_t *summaries;                            // [kVfyChunkFields][K][a.B] u32
 };
 
 }  // namespace hrx

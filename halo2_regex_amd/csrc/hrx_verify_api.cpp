@@ -2,12 +2,17 @@
 // the circuit?  The rules are hrx_verify.hpp's, the kernel is hrx_kernel_verify.hip, the host form hrx_verify_host.cpp.  The check tables are the context's:
 // built from the rows RegexTableConfig::load assigns (table_transition_rows / table_endpoint_rows — never from a walk table) at the context's first verify
 // call, under its lock, and for a device call uploaded then; after that a device call is one launch and nothing else.  DESIGN.md §17.
+// The chunked forms (hrx_verify_rows_chunked_device / _planes / _host, hrx_verify_chunked_workspace_bytes, hrx_ctx_verify_chunk_rows) take
+// the same arguments through the same checks, a chunk size (0: plan_verify_chunk_rows of hrx_plan.cpp) and a workspace for the chunks' summaries; a device
+// call is two launches and nothing else.
 #include "hrx_ctx.hpp"
 #include "hrx_kernel.hpp"
+#include "hrx_plan.hpp"
 #include "hrx_verify.hpp"
 
 namespace hrx {
 void verify_rows_host(const VerifyArgs &a, unsigned threads);      // hrx_verify_host.cpp
+void verify_rows_chunked_host(const VerifyArgs &a, uint32_t chunk_rows, uint32_t *summaries, unsigned threads);
 }
 using namespace hrx;
 static_assert(kVfyPmBlock == HRX_PM_BLOCK && kVfyMaxPlanes == kMaxDefsPerLaunch, "hrx_verify.hpp, include/hrx.h and hrx_kernel.hpp");
@@ -74,6 +79,26 @@ static int check_verify_args(const hrx_ctx *ctx, int layout, const uint8_t *char
     return HRX_OK;
 }
 
+// the context's check tables on its device (the caller holds ctx->mu and has set the device).  First use: build and upload — an allocation and a
+// blocking copy: not inside a stream capture
+static int verify_tab_ready(hrx_ctx *ctx, void *stream) {
+    if (ctx->verify_tab.p) return HRX_OK;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return fail(HRX_ERR_STATE, "verify: the context's check tables are built and uploaded at its first verify call, not inside a stream capture");
+    if (int rc = verify_image_ready(ctx)) return rc;
+    DevBuf tab;
+    HIP_TRY(tab.reserve(ctx->verify_image.size() * 4));
+    const hipError_t e = hipMemcpy(tab.p, ctx->verify_image.data(), ctx->verify_image.size() * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        tab.release();
+        return fail(HRX_ERR_HIP, std::string("verify: table upload: ") + hipGetErrorString(e));
+    }
+    ctx->verify_tab = tab;
+    return HRX_OK;
+}
+
 static int verify_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
                              const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M,
                              uint64_t *verdict, void *stream) {
@@ -85,23 +110,42 @@ static int verify_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, siz
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
-    if (!ctx->verify_tab.p) {     // first use: build and upload (an allocation and a blocking copy: not inside a stream capture)
-        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-        HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
-        if (cap != hipStreamCaptureStatusNone)
-            return fail(HRX_ERR_STATE, "verify: the context's check tables are built and uploaded at its first verify call, not inside a stream capture");
-        if (int rc = verify_image_ready(ctx)) return rc;
-        DevBuf tab;
-        HIP_TRY(tab.reserve(ctx->verify_image.size() * 4));
-        const hipError_t e = hipMemcpy(tab.p, ctx->verify_image.data(), ctx->verify_image.size() * 4, hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            tab.release();
-            return fail(HRX_ERR_HIP, std::string("verify: table upload: ") + hipGetErrorString(e));
-        }
-        ctx->verify_tab = tab;
-    }
+    if (int rc = verify_tab_ready(ctx, stream)) return rc;
     a.image = (const uint32_t *)ctx->verify_tab.p;
     HIP_TRY(launch_verify_rows(a, (hipStream_t)stream));
+    return HRX_OK;
+}
+
+// chunk_rows as the chunked entry points take it: 0 = the context's pick; otherwise a multiple of kVfyChunkAlign, cut to one chunk where it reaches M
+static int resolve_chunk_rows(const hrx_ctx *ctx, size_t B, size_t M, size_t chunk_rows, uint32_t &out) {
+    if (chunk_rows == 0) chunk_rows = plan_verify_chunk_rows(B, M, ctx->num_cus);
+    if (chunk_rows % kVfyChunkAlign) return fail(HRX_ERR_ARG, "chunk_rows must be 0 or a multiple of 32");
+    const size_t one = (M + kVfyChunkAlign - 1) / kVfyChunkAlign * kVfyChunkAlign;
+    out = (uint32_t)std::min(chunk_rows, one);
+    return HRX_OK;
+}
+
+static int verify_chunked_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
+                                     const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B,
+                                     size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes, uint64_t *verdict, void *stream) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (B == 0) return HRX_OK;
+    VerifyChunkArgs ca{};
+    if (int rc = check_verify_args(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, masked, msk_pitch, B, M, verdict, true, ca.a)) return rc;
+    if (int rc = resolve_chunk_rows(ctx, B, M, chunk_rows, ca.chunk_rows)) return rc;
+    ca.K = verify_chunk_count(ca.a.M, ca.chunk_rows);
+    if (!workspace || ((uintptr_t)workspace & 15)) return fail(HRX_ERR_ARG, "workspace must be 16-byte aligned and not NULL");
+    if (workspace_bytes < verify_chunked_workspace_bytes(B, M, ca.chunk_rows))
+        return fail(HRX_ERR_ARG, "workspace smaller than hrx_verify_chunked_workspace_bytes(B, M, chunk_rows)");
+    if ((B + 63) / 64 * (size_t)ca.K > 0x7fffffffull) return fail(HRX_ERR_ARG, "more (64 strings, chunk) pairs than a launch has workgroups: use larger chunks");
+    ca.summaries = (uint32_t *)workspace;
+    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    DeviceGuard guard;
+    HIP_TRY(guard.set(ctx->device));
+    if (int rc = verify_tab_ready(ctx, stream)) return rc;
+    ca.a.image = (const uint32_t *)ctx->verify_tab.p;
+    HIP_TRY(launch_verify_chunked(ca, (hipStream_t)stream));
     return HRX_OK;
 }
 
@@ -132,6 +176,53 @@ int hrx_verify_rows_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t 
     }
     a.image = ctx->verify_image.data();       // (never rebuilt once it is there)
     verify_rows_host(a, threads);
+    return HRX_OK;
+}
+
+size_t hrx_verify_chunked_workspace_bytes(size_t B, size_t M, size_t chunk_rows) { return verify_chunked_workspace_bytes(B, M, chunk_rows); }
+
+size_t hrx_ctx_verify_chunk_rows(hrx_ctx *ctx, size_t B, size_t M) {
+    if (!ctx) return 0;
+    return plan_verify_chunk_rows(B, M, ctx->num_cus);
+}
+
+int hrx_verify_rows_chunked_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
+                                   const uint16_t *masked, size_t msk_pitch, size_t B, size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes,
+                                   uint64_t *verdict, void *stream) {
+    return verify_chunked_device_any(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M, chunk_rows, workspace,
+                                     workspace_bytes, verdict, stream);
+}
+
+int hrx_verify_rows_chunked_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *const *record_planes,
+                                          size_t n_planes, const uint16_t *masked, size_t B, size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes,
+                                          uint64_t *verdict, void *stream) {
+    if (!record_planes) return fail(HRX_ERR_ARG, "NULL buffer");
+    return verify_chunked_device_any(ctx, layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, masked, 0, B, M, chunk_rows, workspace, workspace_bytes,
+                                     verdict, stream);
+}
+
+int hrx_verify_rows_chunked_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
+                                 const uint16_t *masked, size_t msk_pitch, size_t B, size_t M, size_t chunk_rows, uint64_t *verdict) {
+    if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    if (B == 0) return HRX_OK;
+    VerifyArgs a;
+    if (int rc = check_verify_args(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M, verdict, false, a)) return rc;
+    uint32_t C;
+    if (int rc = resolve_chunk_rows(ctx, B, M, chunk_rows, C)) return rc;
+    unsigned threads;
+    {
+        std::lock_guard<std::mutex> lk(ctx->mu);
+        if (int rc = verify_image_ready(ctx)) return rc;
+        threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
+    }
+    a.image = ctx->verify_image.data();
+    std::vector<uint32_t> summaries;      // (the device form's workspace; here the call's own)
+    try {
+        summaries.resize(verify_chunked_workspace_bytes(B, M, C) / 4);
+    } catch (const std::bad_alloc &) {
+        return fail(HRX_ERR_BOUNDS, "verify: no memory for the chunk summaries: use larger chunks");
+    }
+    verify_rows_chunked_host(a, C, summaries.data(), threads);
     return HRX_OK;
 }
 

@@ -664,6 +664,36 @@ int hrx_verify_rows_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars
 int hrx_verify_rows_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
                          const uint32_t *records, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch,
                          size_t B, size_t M, uint64_t *verdict);
+/* CHUNKED VERIFY — the same verdict words, bit for bit, with every string's rows cut into chunks of `chunk_rows` rows so that few long strings fill
+ * the device (one lane per string leaves 8192 x 32768 on an eighth of the SIMDs).  A first launch judges every (64 strings, chunk) pair on its own
+ * and leaves a summary of eight u32 words per (string, chunk) in the caller's workspace; a second launch folds each string's summaries in row order
+ * into the verdict word.  No atomics, no context scratch, nothing allocated, no synchronisation; deterministic; capturable under the first-call rule
+ * above.  chunk_rows: a multiple of 32, or 0 = hrx_ctx_verify_chunk_rows(ctx, B, M); a value of M or more is one chunk.
+ * hrx_verify_chunked_workspace_bytes: what a call with this chunk_rows needs (32 bytes x ceil(M / chunk_rows) x B; 0: chunk_rows is 0 or no
+ * multiple of 32, or the shape is out of range).  Context-free. */
+size_t hrx_verify_chunked_workspace_bytes(size_t B, size_t M, size_t chunk_rows);
+/* The context's pick for a shape: the fewest chunks that give every SIMD of its device two waves (256 CUs on a host-only context), but no more than
+ * M / 256 of them (no chunk below 256 rows; measured: DESIGN.md §17), the rows cut evenly in multiples of 64.  A value >= M means one chunk: hrx_verify_rows_device is the better call.  0: NULL ctx. */
+size_t hrx_ctx_verify_chunk_rows(hrx_ctx *ctx, size_t B, size_t M);
+/* Stands in for hrx_verify_rows_device: its arguments, with chunk_rows and the workspace (device memory, 16-byte aligned, at least
+ * hrx_verify_chunked_workspace_bytes(B, M, chunk_rows) bytes — for chunk_rows = 0 of the context's pick; its contents before the call do not matter
+ * and it is free again once the call's work on `stream` is done) before verdict.  Two launches, asynchronous on `stream`.  Refused with HRX_ERR_ARG,
+ * nothing written: whatever hrx_verify_rows_device refuses, chunk_rows no multiple of 32, a NULL or misaligned or too small workspace, more than
+ * 2^31 - 1 (64 strings, chunk) pairs.  A host-only context: HRX_ERR_HIP. */
+int hrx_verify_rows_chunked_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                   const uint32_t *records, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch,
+                                   size_t B, size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes,
+                                   uint64_t *verdict, void *stream);
+/* Stands in for hrx_verify_rows_device_planes in the same way. */
+int hrx_verify_rows_chunked_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                          const uint32_t *const *record_planes, size_t n_planes, const uint16_t *masked,
+                                          size_t B, size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes,
+                                          uint64_t *verdict, void *stream);
+/* Stands in for hrx_verify_rows_host: the same chunk walk and fold (csrc/hrx_verify.hpp) on HRX_OPT_HOST_THREADS threads over (string, chunk)
+ * pairs, so eight long strings use sixteen threads.  The summaries are the call's own allocation.  The definition of the chunked rule. */
+int hrx_verify_rows_chunked_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                 const uint32_t *records, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch,
+                                 size_t B, size_t M, size_t chunk_rows, uint64_t *verdict);
 
 /* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */

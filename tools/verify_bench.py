@@ -15,7 +15,17 @@ MI355X, 2026-10-19, one lease, us per launch, witness (its two figures) / traffi
   header defs 65536 x 2048   interleaved 311.6 314.6 / 300.8 / 2611.9 = 8.38   planes      281.7 285.3 / 286.5 / 2659.7 = 9.44
   regex1 8192 x 32768        interleaved 433.5 439.1 / 1226.6 / 15789.7 = 36.4
   torch checker, regex1 65536 x 1024: 26.4 ms, 16.75 GiB of temporaries
-The launch is bound by one wave per SIMD issuing 160 instructions a row, not by memory (DESIGN.md §17 has the counters)."""
+The launch is bound by one wave per SIMD issuing 160 instructions a row, not by memory (DESIGN.md §17 has the counters).
+
+--chunked: the chunked verify (hrx_verify_rows_chunked_device*) beside the unchunked launch, same procedure, every chunked verdict equal to the
+unchunked launch's before anything is timed, the unchunked launch and the witness launch each timed twice: regex1 at 8192 x 32768 interleaved and the three
+header defs at 32768 x 32768 in planes at the context's pick (--long-headers-B: another string count, 0 leaves the shape out), the two headline rows at
+K = 1, 2, 4 and the pick.  --floor-sweep: regex1 x 32768 rows, 8192 and 1024 strings, chunks of 128 .. 4096 rows (the floor of hrx_ctx_verify_chunk_rows).
+MI355X, 2026-10-20, us per call (two launches), chunked / unchunked / their ratio:
+  regex1 8192 x 32768, the pick 2048 (K = 16)        1823.4 / 15765.7 = 0.116 (8.65 times as fast; 4.11 of the witness launch)
+  header defs 32768 x 32768, the pick 8192 (K = 4)  15642.8 / 41112.6 = 0.380
+  regex1 65536 x 1024        K = 1 821.6   K = 2 482.7 (the pick)   K = 4 482.3   unchunked 542.9
+  header defs 65536 x 2048   K = 1 3228.1  K = 2 1958.2 (the pick)  K = 4 1939.1  unchunked 2597.5"""
 import argparse
 import os
 import statistics
@@ -72,7 +82,8 @@ def time_kinds(kinds, rounds=20, launches=10):
     return {k: statistics.median(v) for k, v in times.items()}
 
 
-def run_shape(label, names, B, M, make, planes, rounds):
+def run_shape(label, names, B, M, make, planes, rounds, chunks=()):
+    """chunks: chunk_rows values of the chunked verify to time beside the unchunked launch (0: the context's pick); with any, the unchunked launch is timed twice"""
     cfg = config(names, M)
     D = cfg.num_defs
     chars, lens = make(B, M - 8, stride=M + 16)
@@ -91,10 +102,26 @@ def run_shape(label, names, B, M, make, planes, rounds):
         vkw = {}
     verdict = torch.empty((B,), dtype=torch.int64, device=DEV)
     verify = lambda s: cfg.verify_rows(d_pm, d_lens, None if planes else out[0], out[1], layout=PM_IN, out=verdict, chars_pm_stride=stride, stream=s, **vkw)
+    chunked = {}
+    for c in chunks:
+        rows_c = c if c else cfg.verify_chunk_rows(B)
+        ws = torch.empty((max(16, hra.verify_chunked_workspace_bytes(B, M, rows_c)),), dtype=torch.uint8, device=DEV)
+        v_c = torch.empty((B,), dtype=torch.int64, device=DEV)
+        name = "chunked %d%s" % (rows_c, " (the pick)" if not c else "")
+        fn = lambda s, c=c, ws=ws, v_c=v_c: cfg.verify_rows(d_pm, d_lens, None if planes else out[0], out[1], layout=PM_IN, out=v_c, chars_pm_stride=stride, stream=s,
+                                                            chunk_rows=c, workspace=ws, **vkw)
+        chunked[name] = (fn, v_c, -(-M // rows_c))
     s0 = torch.cuda.current_stream(DEV)
     witness(s0)
     verify(s0)
+    for fn, v_c, _ in chunked.values():
+        fn(s0)
     torch.cuda.synchronize()
+    for name, (fn, v_c, _) in chunked.items():
+        if not torch.equal(v_c, verdict):
+            b = int(torch.nonzero(v_c != verdict)[0])
+            print("%s: %s: string %d: %s, the unchunked launch says %s" % (label, name, b, hra.explain_verdict(int(v_c[b])), hra.explain_verdict(int(verdict[b]))))
+            return 1
     st = out[2].cpu().numpy().view(np.uint64)
     accepted = ((st & np.uint64(0xff)) == 0) & ((((st >> np.uint64(8)) & np.uint64(0xff)) == np.uint64((1 << D) - 1)) | (lens >= M))
     v = verdict.cpu().numpy().view(np.uint64)
@@ -102,7 +129,13 @@ def run_shape(label, names, B, M, make, planes, rounds):
         b = int(np.nonzero(accepted & (v != 0))[0][0])
         print("%s: string %d was accepted and its rows fail: %s" % (label, b, hra.explain_verdict(v[b])))
         return 1
-    t = time_kinds({"witness": witness, "verify": verify, "witness again": witness, "traffic pass": traffic}, rounds=rounds)
+    kinds = {"witness": witness, "verify": verify}
+    kinds.update({name: fn for name, (fn, _, _) in chunked.items()})
+    kinds["witness again"] = witness
+    if chunked:
+        kinds["verify again"] = verify
+    kinds["traffic pass"] = traffic
+    t = time_kinds(kinds, rounds=rounds)
     witness(s0)
     verify(s0)
     torch.cuda.synchronize()
@@ -114,6 +147,12 @@ def run_shape(label, names, B, M, make, planes, rounds):
     print("%-34s B=%d M=%d D=%d  accepted %d of %d, nonzero verdicts %d  witness %8.1f / %8.1f us  verify %8.1f us = %.3f of it (%.0f GB/s of rows read)  "
           "traffic pass %8.1f us" % (label, B, M, D, int(accepted.sum()), B, int((v != 0).sum()), t["witness"], t["witness again"], t["verify"], t["verify"] / w,
                                      gb / (t["verify"] * 1e-6), t["traffic pass"]), flush=True)
+    if chunked:
+        u = min(t["verify"], t["verify again"])
+        print("    unchunked verify %8.1f / %8.1f us" % (t["verify"], t["verify again"]))
+        for name, (_, _, K) in chunked.items():
+            print("    %-26s K=%-4d %8.1f us = %.3f of the unchunked launch (%.2f times as fast), %.2f of the witness launch" % (
+                name, K, t[name], t[name] / u, u / t[name], t[name] / w), flush=True)
     return 0
 
 
@@ -148,8 +187,24 @@ def main():
     ap.add_argument("--rounds", type=int, default=20)
     ap.add_argument("--long", action="store_true", help="also regex1 at 8192 x 32768")
     ap.add_argument("--torch", action="store_true", help="also the torch checker on the headline rows")
+    ap.add_argument("--chunked", action="store_true", help="the chunked verify instead: few long strings at the context's pick, the headline rows at K = 1, 2, 4 and the pick")
+    ap.add_argument("--floor-sweep", action="store_true", help="the chunked verify at chunks of 128 .. 4096 rows, regex1 x 32768 rows, 8192 and 1024 strings")
+    ap.add_argument("--long-headers-B", type=int, default=32768, help="--chunked: strings of the three header defs x 32768 rows (0: leave the shape out)")
     args = ap.parse_args()
     rc = 0
+    long_rounds = max(4, args.rounds // 4)
+    if args.floor_sweep:
+        sweep = (128, 256, 512, 1024, 2048, 4096, 0)
+        rc |= run_shape("regex1 long, interleaved", CFG_1, args.B // 8, 32768, synth.regex1_planted, False, long_rounds, chunks=sweep)
+        rc |= run_shape("regex1 long, 1024 strings", CFG_1, args.B // 64, 32768, synth.regex1_planted, False, long_rounds, chunks=sweep)
+        return rc
+    if args.chunked:
+        rc |= run_shape("regex1 long, interleaved", CFG_1, args.B // 8, 32768, synth.regex1_planted, False, long_rounds, chunks=(0,))
+        rc |= run_shape("regex1 interleaved", CFG_1, args.B, 1024, synth.regex1_planted, False, args.rounds, chunks=(1024, 512, 256, 0))
+        rc |= run_shape("three header defs interleaved", CFG_H3, args.B, 2048, synth.headers_planted, False, args.rounds, chunks=(2048, 1024, 512, 0))
+        if args.long_headers_B:
+            rc |= run_shape("three header defs long, planes", CFG_H3, args.long_headers_B, 32768, synth.headers_planted, True, long_rounds, chunks=(0,))
+        return rc
     for planes in (False, True):
         rc |= run_shape("regex1 " + ("row stripes" if planes else "interleaved"), CFG_1, args.B, 1024, synth.regex1_planted, planes, args.rounds)
         rc |= run_shape("three header defs " + ("planes" if planes else "interleaved"), CFG_H3, args.B, 2048, synth.headers_planted, planes, args.rounds)
