@@ -233,6 +233,21 @@ extern "C" {
     pub fn hrx_verify_rows_chunked_host(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
                                         records: *const u32, rec_pitch: usize, masked: *const u16, msk_pitch: usize, b: usize, m: usize,
                                         chunk_rows: usize, verdict: *mut u64) -> c_int;
+    /// LOOKUP COUNTS: per string one run of hrx_lookup_words_per_string u32 words — per def trans[T_d], start[E_d], end[E_d], how often its rows hit each row
+    /// of the circuit's three fixed lookup tables (the m column of a logUp argument) — and one misses word; strings [b_begin, b_begin + b_count)
+    pub fn hrx_lookup_words_per_string(defs: *const hrx_defs) -> usize;
+    pub fn hrx_lookup_layout(defs: *const hrx_defs, def: usize, trans_off: *mut usize, trans_rows: *mut usize, start_off: *mut usize, end_off: *mut usize,
+                             endpoint_rows: *mut usize) -> c_int;
+    pub fn hrx_lookup_counts_device(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                    records: *const u32, rec_pitch: usize, b: usize, m: usize, b_begin: usize, b_count: usize,
+                                    counts: *mut u32, misses: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_counts_device_planes(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                           record_planes: *const *const u32, n_planes: usize, b: usize, m: usize, b_begin: usize, b_count: usize,
+                                           counts: *mut u32, misses: *mut u32, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_counts_host(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                  records: *const u32, rec_pitch: usize, b: usize, m: usize, b_begin: usize, b_count: usize,
+                                  counts: *mut u32, misses: *mut u32) -> c_int;
+    pub fn hrx_ctx_lookup_group(ctx: *mut hrx_ctx, b_count: usize, group: *mut usize, passes: *mut usize) -> c_int;
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

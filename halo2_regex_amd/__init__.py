@@ -148,6 +148,12 @@ def _load():
         "hrx_verify_rows_chunked_device": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, sz, vp, sz, vp, vp]),
         "hrx_verify_rows_chunked_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, vp, sz, sz, sz, vp, sz, vp, vp]),
         "hrx_verify_rows_chunked_host": (i, [vp, i, vp, sz, vp, vp, sz, vp, sz, sz, sz, sz, vp]),
+        "hrx_lookup_words_per_string": (sz, [vp]),
+        "hrx_lookup_layout": (i, [vp, sz] + [C.POINTER(sz)] * 5),
+        "hrx_lookup_counts_device": (i, [vp, i, vp, sz, vp, vp, sz, sz, sz, sz, sz, vp, vp, vp]),
+        "hrx_lookup_counts_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, sz, sz, sz, sz, vp, vp, vp]),
+        "hrx_lookup_counts_host": (i, [vp, i, vp, sz, vp, vp, sz, sz, sz, sz, sz, vp, vp]),
+        "hrx_ctx_lookup_group": (i, [vp, sz, C.POINTER(sz), C.POINTER(sz)]),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -1355,6 +1361,93 @@ class RegexVerifyConfig:
                                         int(msk_pitch), B, M, out.ctypes.data))
         return out
 
+    def lookup_words(self):
+        """hrx_lookup_words_per_string: the u32 words of one string's run of lookup counts (a multiple of 4)"""
+        return int(lib.hrx_lookup_words_per_string(self._defs.h))
+
+    def lookup_layout(self):
+        """hrx_lookup_layout: per def a dict of slices into a string's run of lookup_words() counts — "trans" (one bin per row of load()[d][0]), "start" and
+        "end" (one bin per row of load()[d][1] each)"""
+        out = []
+        for d in range(self.num_defs):
+            v = [C.c_size_t() for _ in range(5)]
+            _check(lib.hrx_lookup_layout(self._defs.h, d, *[C.byref(x) for x in v]))
+            t_off, t_rows, s_off, e_off, e_rows = (int(x.value) for x in v)
+            out.append({"trans": slice(t_off, t_off + t_rows), "start": slice(s_off, s_off + e_rows), "end": slice(e_off, e_off + e_rows)})
+        return out
+
+    def lookup_group(self, b_count):
+        """hrx_ctx_lookup_group: (strings per workgroup, passes over the rows) of a lookup_counts call of b_count strings"""
+        g, p = C.c_size_t(), C.c_size_t()
+        _check(lib.hrx_ctx_lookup_group(self._need_ctx(), int(b_count), C.byref(g), C.byref(p)))
+        return int(g.value), int(p.value)
+
+    def lookup_counts(self, chars, lens, rec, layout=LAYOUT_STRING_MAJOR, planes=None, b_begin=0, b_count=None, out=None, misses=None, chars_pm_stride=None,
+                      rec_pitch=0, stream=None):
+        """hrx_lookup_counts_device / _planes: how often the witness rows of strings [b_begin, b_begin + b_count) of a finished batch hit each row of the three
+        fixed lookup tables per def (include/hrx.h LOOKUP COUNTS).  Returns (counts, misses): (b_count, lookup_words()) and (b_count,) int32 CUDA tensors holding
+        u32 bit patterns; lookup_layout() slices a counts row.  chars, lens, `layout`, rec / planes, rec_pitch and chars_pm_stride are verify_rows'.  out / misses: the
+        caller's contiguous int32 tensors of exactly those sizes, written in place.  One launch, asynchronous on `stream` (default: torch's current stream); the
+        context's first call also builds and uploads the image of the tables (not inside a graph capture)."""
+        assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and chars.dtype == torch.uint8
+        B, M, D, W = lens.numel(), self.max_chars_size, self.num_defs, self.lookup_words()
+        b_count = B - b_begin if b_count is None else int(b_count)
+        if chars_pm_stride is not None:
+            stride = int(chars_pm_stride)
+            assert layout & LAYOUT_INPUT_POSITION_MAJOR and chars.is_contiguous()
+        else:
+            assert not layout & LAYOUT_INPUT_POSITION_MAJOR and chars.stride(1) == 1
+            stride = chars.stride(0)
+        if out is None:
+            out = torch.empty((b_count, W), dtype=torch.int32, device=lens.device)
+        elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != b_count * W:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous int32 tensor of [%d][%d] elements" % (b_count, W))
+        if misses is None:
+            misses = torch.empty((b_count,), dtype=torch.int32, device=lens.device)
+        elif misses.dtype != torch.int32 or not misses.is_contiguous() or misses.numel() != b_count:
+            raise HrxError(HRX_ERR_ARG, "misses: a contiguous int32 tensor of %d elements" % b_count)
+        s = torch.cuda.current_stream(lens.device) if stream is None else stream
+        if planes is not None:
+            arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+            _check(lib.hrx_lookup_counts_device_planes(self._need_device(chars, lens, out, misses, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(), arr,
+                                                       len(planes), B, M, int(b_begin), b_count, out.data_ptr(), misses.data_ptr(), s.cuda_stream))
+            return out, misses
+        if not layout & LAYOUT_POSITION_MAJOR and not rec_pitch and rec.dim() == 3:
+            rec_pitch = rec.stride(0) // D
+        _check(lib.hrx_lookup_counts_device(self._need_device(chars, lens, rec, out, misses), int(layout), chars.data_ptr(), stride, lens.data_ptr(), rec.data_ptr(),
+                                            int(rec_pitch), B, M, int(b_begin), b_count, out.data_ptr(), misses.data_ptr(), s.cuda_stream))
+        return out, misses
+
+    def lookup_counts_host(self, chars, lens, rec, layout=LAYOUT_STRING_MAJOR, b_begin=0, b_count=None, out=None, misses=None, chars_pm_stride=None, rec_pitch=0):
+        """hrx_lookup_counts_host: lookup_counts over numpy arrays in host memory, on a host-only or a device context — the definition of the counts
+        (csrc/hrx_lookup.hpp) over host threads.  Returns (counts (b_count, lookup_words()) uint32, misses (b_count,) uint32).  String-major records (B, M, D) /
+        chars (B, stride), pitched views included, or the flat position-major buffers."""
+        lens = np.ascontiguousarray(lens, np.uint32)
+        B, M, D, W = len(lens), self.max_chars_size, self.num_defs, self.lookup_words()
+        b_count = B - b_begin if b_count is None else int(b_count)
+        ch, rec = np.asarray(chars), np.asarray(rec)
+        if layout & LAYOUT_POSITION_MAJOR:
+            rec = np.ascontiguousarray(rec)
+        elif not rec_pitch and rec.ndim == 3:
+            assert rec.strides[2] == 4 and rec.strides[1] == 4 * D
+            rec_pitch = rec.strides[0] // (4 * D)
+        if chars_pm_stride is not None:
+            stride, ch = int(chars_pm_stride), np.ascontiguousarray(ch)
+        else:
+            assert ch.ndim == 2 and ch.strides[1] == 1
+            stride = ch.strides[0]
+        if out is None:
+            out = np.empty((b_count, W), np.uint32)
+        elif out.dtype != np.uint32 or not out.flags.c_contiguous or out.size != b_count * W:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint32 array of [%d][%d] elements" % (b_count, W))
+        if misses is None:
+            misses = np.empty(b_count, np.uint32)
+        elif misses.dtype != np.uint32 or not misses.flags.c_contiguous or misses.size != b_count:
+            raise HrxError(HRX_ERR_ARG, "misses: a contiguous uint32 array of %d elements" % b_count)
+        _check(lib.hrx_lookup_counts_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch), B, M, int(b_begin),
+                                          b_count, out.ctypes.data, misses.ctypes.data))
+        return out, misses
+
     def witness_batch(self, chars, lens, out=None, stream=None):
         """Device-resident batch: chars (B, stride) uint8 CUDA tensor (stride % 16 == 0), lens (B,) int32 CUDA tensor.
         Asynchronous on `stream` (default: torch's current stream).  Returns (records, masked, status) tensors whose
@@ -1403,6 +1496,32 @@ def explain_verdict(v):
     if v == 0xffffffffffffffff:
         return "longer than max_chars_size"
     return " + ".join(name for bit, name in VERIFY_NAMES.items() if v & bit) + " at row %d" % verdict_row(v)
+
+
+def permuted_lookup_columns(n_table_rows, counts, n_rows):
+    """The permuted columns of halo2's lookup argument out of one lookup's counts — no sort: index arrays (A_idx, S_idx) of length n_rows into the table rows.
+    The n_rows - sum(counts) inputs not counted hit row 0 (rows outside the region evaluate to the dummy tuple) and the table is padded to n_rows with copies of
+    row 0.  A_idx is non-decreasing with counts[t] copies of t (row 0: plus the uncounted inputs); S_idx is a permutation of the padded table; for every i,
+    A_idx[i] == S_idx[i] or A_idx[i] == A_idx[i - 1].  ValueError: sum(counts) > n_rows or n_table_rows > n_rows."""
+    m = np.asarray(counts, np.int64).copy()
+    n_table_rows, n_rows = int(n_table_rows), int(n_rows)
+    if m.ndim != 1 or len(m) != n_table_rows or n_table_rows < 1:
+        raise ValueError("counts: one entry per table row")
+    if n_table_rows > n_rows:
+        raise ValueError("the table has more rows than the circuit")
+    if int(m.sum()) > n_rows:
+        raise ValueError("more counted inputs than the circuit has rows")
+    m[0] += n_rows - int(m.sum())
+    a_idx = np.repeat(np.arange(n_table_rows, dtype=np.int64), m)
+    # the padded table as a multiset: row t once, row 0 another n_rows - n_table_rows times.  Where a run of A' begins, S' holds the run's row; the other
+    # positions take what is left, in any order
+    first = np.ones(n_rows, bool)
+    first[1:] = a_idx[1:] != a_idx[:-1]
+    s_idx = np.empty(n_rows, np.int64)
+    s_idx[first] = a_idx[first]
+    left = np.concatenate([np.nonzero(m == 0)[0], np.zeros(n_rows - n_table_rows, np.int64)])
+    s_idx[~first] = left
+    return a_idx, s_idx
 
 
 FR_CANONICAL = 1                       # HRX_FR_CANONICAL

@@ -156,6 +156,9 @@ struct hrx_ctx {
     // VERIFY (hrx_verify_api.cpp): the check tables (hrx_verify.hpp build_verify_image), built at the context's first verify call, and their device copy
     std::vector<uint32_t> verify_image;
     DevBuf verify_tab;
+    // LOOKUP COUNTS (hrx_lookup_api.cpp): the image (hrx_lookup.hpp build_lookup_image), built at the context's first lookup call, and its device copy
+    std::vector<uint32_t> lookup_image;
+    DevBuf lookup_tab;
     DevBuf d_cw;                    // CLASS-WIDE image of a config of 4 .. 8 defs (DefsSet::cw_image): the single-launch def-parallel path and the fused-wide match
 #ifdef HRX_STAMPS
     DevBuf stamps;                  // tools-only build: 8 u64 per walker pair of the position-major kernel (hrx_kernel_pm.hip)

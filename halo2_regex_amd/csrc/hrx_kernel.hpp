@@ -457,5 +457,8 @@ struct VerifyArgs;     // hrx_verify.hpp
 hipError_t launch_verify_rows(const VerifyArgs &a, hipStream_t stream);
 struct VerifyChunkArgs;
 hipError_t launch_verify_chunked(const VerifyChunkArgs &ca, hipStream_t stream);      // the chunk launch, then the stitch launch
+// LOOKUP COUNTS (hrx_kernel_lookup.hip): the rule of hrx_lookup.hpp over the same row forms; a histogram per string with the bins in LDS
+struct LookupArgs;     // hrx_lookup.hpp
+hipError_t launch_lookup_counts(const LookupArgs &a, size_t lds_bytes, hipStream_t stream);
 
 }  // namespace hrx

@@ -696,6 +696,49 @@ int hrx_verify_rows_chunked_host(hrx_ctx *ctx, int layout, const uint8_t *chars,
                                  size_t B, size_t M, size_t chunk_rows, uint64_t *verdict);
 
 /* ------------------------------------------------------------------ */
+/* LOOKUP COUNTS — how often the advice rows hit each row of the fixed lookup tables (the first step of a prover over the cells)      */
+/* ------------------------------------------------------------------ */
+/* RegexVerifyConfig::configure declares three lookups per RegexDefs (src/lib.rs:206-285): "characters and their state" into the transition table,
+ * "start_state of substring" and "end_state of substring" into the endpoint table.  For each of them and each table row, in RegexTableConfig::load's
+ * order (hrx_table_transition_rows / hrx_table_endpoint_rows: T_d and E_d rows of def d), these calls count the rows of a string's witness that look
+ * that table row up: the multiplicity column m of a logUp-style argument, and what halo2's own lookup argument builds its permuted columns A', S'
+ * from (table row t, m[t] times) without a sort.  Per row r of the M rows, with en = [r < n_b], se / ee the record's start_enable / end_enable bits
+ * and next = the state of row r + 1 (the def's dummy state behind row M - 1):
+ *   trans  (en char, en cur + (1 - en) dummy, en next + (1 - en) dummy, en substr_id)     lib.rs:218-232
+ *   start  (se substr_id, se cur + (1 - se) dummy, dummy)                                   lib.rs:247-257
+ *   end    (ee substr_id, dummy, ee next + (1 - ee) dummy)                                  lib.rs:273-283
+ * each adds 1 to the table row that equals it in every component — the lowest such row where two endpoint rows hold one tuple — or, in no row, 1 to the
+ * string's `misses` word and to no bin: misses[b] != 0 exactly where hrx_verify_rows_host reports a transition, start or end lookup bit.  The lookups
+ * that exist are those VERIFY judges: with n_b == M the transition and end lookups of row M - 1 read a cell match_substrs never assigns and are neither
+ * counted nor missed.  States, ids and flag bits outside every table are misses.  n_b > M: every bin 0, misses 0xffffffff.  No status word is read:
+ * rows are counted as they lie.
+ * counts: [b_count][W] u32, 16-byte aligned, W = hrx_lookup_words_per_string(defs): per def in order trans[T_d], start[E_d], end[E_d], the total rounded
+ * up to a multiple of 4 with the pad words written as 0; hrx_lookup_layout gives one def's offsets into a string's run.  misses: [b_count] u32, or NULL.
+ * The strings are [b_begin, b_begin + b_count) of the batch, as for hrx_fr_columns_device (the dense output is large: the caller bounds it).
+ * `layout`, chars / stride / lens, records (rec_pitch string-major only, in rows; 0 = M) and the record planes are those of hrx_verify_rows_device*, at
+ * its alignments; whatever it refuses is refused, and a refused call writes nothing.  The masked rows are no argument: no lookup reads them.
+ * The device forms: one launch, asynchronous on `stream`; nothing allocated, no context scratch, no global atomics, deterministic.  The image of the
+ * tables is built and uploaded at the context's FIRST lookup call: inside a stream capture before that HRX_ERR_STATE, afterwards capturable.  A
+ * host-only context: HRX_ERR_HIP. */
+size_t hrx_lookup_words_per_string(const hrx_defs *defs);
+int hrx_lookup_layout(const hrx_defs *defs, size_t def, size_t *trans_off, size_t *trans_rows, size_t *start_off, size_t *end_off, size_t *endpoint_rows);
+int hrx_lookup_counts_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                             const uint32_t *records, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
+                             uint32_t *counts, uint32_t *misses, void *stream);
+int hrx_lookup_counts_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                    const uint32_t *const *record_planes, size_t n_planes, size_t B, size_t M, size_t b_begin, size_t b_count,
+                                    uint32_t *counts, uint32_t *misses, void *stream);
+/* The same over rows in HOST memory (as hrx_verify_rows_host takes them), on a host-only or a device context, over HRX_OPT_HOST_THREADS threads by
+ * ranges of strings.  The definition of the counts. */
+int hrx_lookup_counts_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                           const uint32_t *records, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
+                           uint32_t *counts, uint32_t *misses);
+/* How a device call of b_count strings cuts its work: a workgroup keeps the bins of *group consecutive strings of the window in LDS (a power of two,
+ * chosen from W and lowered while fewer than two workgroups per CU would come of it; 256 CUs on a host-only context) and walks the rows *passes times
+ * (more than once only where one string's bins exceed the LDS of a CU).  For tests and tools; the counts do not depend on it. */
+int hrx_ctx_lookup_group(hrx_ctx *ctx, size_t b_count, size_t *group, size_t *passes);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */
 /* ------------------------------------------------------------------ */
 /* One circuit: EXACTLY the Vecs the three derive_* calls at the top of match_substrs return (src/lib.rs:316-318), out of the string's compact records, so that the body
