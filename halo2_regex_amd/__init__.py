@@ -617,6 +617,46 @@ def shard_range(B, world, rank):
     return b.value, c.value
 
 
+def _torch_row_pitches(chars, records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride):
+    """(stride, rec_pitch, msk_pitch) as the device entry points that read witness rows take them, from CUDA tensors: a pitch of 0 is taken from a string-major
+    (B, M, D) / (B, M) view's strides.  records None: record planes; masked None: a reader without masked rows."""
+    if chars_pm_stride is not None:
+        stride = int(chars_pm_stride)
+        assert layout & LAYOUT_INPUT_POSITION_MAJOR and chars.is_contiguous()
+    else:
+        assert not layout & LAYOUT_INPUT_POSITION_MAJOR and chars.stride(1) == 1
+        stride = chars.stride(0)
+    if not layout & LAYOUT_POSITION_MAJOR:
+        if not rec_pitch and records is not None and records.dim() == 3:
+            rec_pitch = records.stride(0) // D
+        if not msk_pitch and masked is not None and masked.dim() == 2:
+            msk_pitch = masked.stride(0)
+    return stride, int(rec_pitch), int(msk_pitch)
+
+
+def _numpy_rows(chars, records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride):
+    """(chars, records, masked, stride, rec_pitch, msk_pitch) as the host entry points that read witness rows take them, from numpy arrays: the flat
+    position-major buffers contiguous, a pitch of 0 taken from a string-major view's strides.  masked None: a reader without masked rows."""
+    ch, rec = np.asarray(chars), np.asarray(records)
+    msk = None if masked is None else np.asarray(masked)
+    if layout & LAYOUT_POSITION_MAJOR:
+        rec = np.ascontiguousarray(rec)
+        msk = None if msk is None else np.ascontiguousarray(msk)
+    else:
+        if not rec_pitch and rec.ndim == 3:
+            assert rec.strides[2] == 4 and rec.strides[1] == 4 * D
+            rec_pitch = rec.strides[0] // (4 * D)
+        if not msk_pitch and msk is not None and msk.ndim == 2:
+            assert msk.strides[1] == 2
+            msk_pitch = msk.strides[0] // 2
+    if chars_pm_stride is not None:
+        stride, ch = int(chars_pm_stride), np.ascontiguousarray(ch)
+    else:
+        assert ch.ndim == 2 and ch.strides[1] == 1
+        stride = ch.strides[0]
+    return ch, rec, msk, stride, int(rec_pitch), int(msk_pitch)
+
+
 class RegexVerifyConfig:
     """Witness-side mirror of RegexVerifyConfig (src/lib.rs:96-113).
 
@@ -1281,12 +1321,7 @@ class RegexVerifyConfig:
         bytes — `workspace`, any contiguous CUDA tensor of at least that size, or one allocated here."""
         assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and chars.dtype == torch.uint8
         B, M, D = lens.numel(), self.max_chars_size, self.num_defs
-        if chars_pm_stride is not None:
-            stride = int(chars_pm_stride)
-            assert layout & LAYOUT_INPUT_POSITION_MAJOR and chars.is_contiguous()
-        else:
-            assert not layout & LAYOUT_INPUT_POSITION_MAJOR and chars.stride(1) == 1
-            stride = chars.stride(0)
+        stride, rec_pitch, msk_pitch = _torch_row_pitches(chars, None if planes is not None else records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride)
         if out is None:
             out = torch.empty((B,), dtype=torch.int64, device=lens.device)
         elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != B:
@@ -1304,11 +1339,6 @@ class RegexVerifyConfig:
                                                                  lens.data_ptr(), arr, len(planes), masked.data_ptr(), B, M, chunk_rows, workspace.data_ptr(), ws_bytes,
                                                                  out.data_ptr(), s.cuda_stream))
                 return out
-            if not layout & LAYOUT_POSITION_MAJOR:
-                if not rec_pitch and records.dim() == 3:
-                    rec_pitch = records.stride(0) // D
-                if not msk_pitch and masked.dim() == 2:
-                    msk_pitch = masked.stride(0)
             _check(lib.hrx_verify_rows_chunked_device(self._need_device(chars, lens, records, masked, out, workspace), int(layout), chars.data_ptr(), stride, lens.data_ptr(),
                                                       records.data_ptr(), int(rec_pitch), masked.data_ptr(), int(msk_pitch), B, M, chunk_rows, workspace.data_ptr(), ws_bytes,
                                                       out.data_ptr(), s.cuda_stream))
@@ -1318,11 +1348,6 @@ class RegexVerifyConfig:
             _check(lib.hrx_verify_rows_device_planes(self._need_device(chars, lens, masked, out, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(), arr, len(planes),
                                                      masked.data_ptr(), B, M, out.data_ptr(), s.cuda_stream))
             return out
-        if not layout & LAYOUT_POSITION_MAJOR:
-            if not rec_pitch and records.dim() == 3:
-                rec_pitch = records.stride(0) // D
-            if not msk_pitch and masked.dim() == 2:
-                msk_pitch = masked.stride(0)
         _check(lib.hrx_verify_rows_device(self._need_device(chars, lens, records, masked, out), int(layout), chars.data_ptr(), stride, lens.data_ptr(), records.data_ptr(),
                                           int(rec_pitch), masked.data_ptr(), int(msk_pitch), B, M, out.data_ptr(), s.cuda_stream))
         return out
@@ -1333,22 +1358,7 @@ class RegexVerifyConfig:
         chunk_rows: None — that call; 0 or a multiple of 32 — hrx_verify_rows_chunked_host, the same words from the chunk walk and fold over (string, chunk) pairs."""
         lens = np.ascontiguousarray(lens, np.uint32)
         B, M, D = len(lens), self.max_chars_size, self.num_defs
-        ch = np.asarray(chars)
-        rec, msk = np.asarray(records), np.asarray(masked)
-        if layout & LAYOUT_POSITION_MAJOR:
-            rec, msk = np.ascontiguousarray(rec), np.ascontiguousarray(msk)
-        else:
-            if not rec_pitch and rec.ndim == 3:
-                assert rec.strides[2] == 4 and rec.strides[1] == 4 * D
-                rec_pitch = rec.strides[0] // (4 * D)
-            if not msk_pitch and msk.ndim == 2:
-                assert msk.strides[1] == 2
-                msk_pitch = msk.strides[0] // 2
-        if chars_pm_stride is not None:
-            stride, ch = int(chars_pm_stride), np.ascontiguousarray(ch)
-        else:
-            assert ch.ndim == 2 and ch.strides[1] == 1
-            stride = ch.strides[0]
+        ch, rec, msk, stride, rec_pitch, msk_pitch = _numpy_rows(chars, records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride)
         if out is None:
             out = np.empty(B, np.uint64)
         elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != B:
@@ -1392,12 +1402,7 @@ class RegexVerifyConfig:
         assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and chars.dtype == torch.uint8
         B, M, D, W = lens.numel(), self.max_chars_size, self.num_defs, self.lookup_words()
         b_count = B - b_begin if b_count is None else int(b_count)
-        if chars_pm_stride is not None:
-            stride = int(chars_pm_stride)
-            assert layout & LAYOUT_INPUT_POSITION_MAJOR and chars.is_contiguous()
-        else:
-            assert not layout & LAYOUT_INPUT_POSITION_MAJOR and chars.stride(1) == 1
-            stride = chars.stride(0)
+        stride, rec_pitch, _ = _torch_row_pitches(chars, None if planes is not None else rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
         if out is None:
             out = torch.empty((b_count, W), dtype=torch.int32, device=lens.device)
         elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != b_count * W:
@@ -1412,8 +1417,6 @@ class RegexVerifyConfig:
             _check(lib.hrx_lookup_counts_device_planes(self._need_device(chars, lens, out, misses, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(), arr,
                                                        len(planes), B, M, int(b_begin), b_count, out.data_ptr(), misses.data_ptr(), s.cuda_stream))
             return out, misses
-        if not layout & LAYOUT_POSITION_MAJOR and not rec_pitch and rec.dim() == 3:
-            rec_pitch = rec.stride(0) // D
         _check(lib.hrx_lookup_counts_device(self._need_device(chars, lens, rec, out, misses), int(layout), chars.data_ptr(), stride, lens.data_ptr(), rec.data_ptr(),
                                             int(rec_pitch), B, M, int(b_begin), b_count, out.data_ptr(), misses.data_ptr(), s.cuda_stream))
         return out, misses
@@ -1425,17 +1428,7 @@ class RegexVerifyConfig:
         lens = np.ascontiguousarray(lens, np.uint32)
         B, M, D, W = len(lens), self.max_chars_size, self.num_defs, self.lookup_words()
         b_count = B - b_begin if b_count is None else int(b_count)
-        ch, rec = np.asarray(chars), np.asarray(rec)
-        if layout & LAYOUT_POSITION_MAJOR:
-            rec = np.ascontiguousarray(rec)
-        elif not rec_pitch and rec.ndim == 3:
-            assert rec.strides[2] == 4 and rec.strides[1] == 4 * D
-            rec_pitch = rec.strides[0] // (4 * D)
-        if chars_pm_stride is not None:
-            stride, ch = int(chars_pm_stride), np.ascontiguousarray(ch)
-        else:
-            assert ch.ndim == 2 and ch.strides[1] == 1
-            stride = ch.strides[0]
+        ch, rec, _, stride, rec_pitch, _ = _numpy_rows(chars, rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
         if out is None:
             out = np.empty((b_count, W), np.uint32)
         elif out.dtype != np.uint32 or not out.flags.c_contiguous or out.size != b_count * W:

@@ -331,7 +331,7 @@ void hrx_ctx_destroy(hrx_ctx *c) {
     }
     c->mp_masked.release(); c->mp_ov.release();
     c->tp_records.release(); c->tp_masked.release();
-    c->spec_cimage.release(); c->d_cw.release(); c->verify_tab.release(); c->lookup_tab.release();
+    c->spec_cimage.release(); c->d_cw.release(); c->verify_img.dev.release(); c->lookup_img.dev.release();
     for (auto &g : c->cw_groups) { g.d_cw.release(); g.status.release(); g.summary.release(); }
     c->spec_cls.release(); c->spec_ends.release(); c->spec_fail.release(); c->spec_init.release(); c->spec_vstatus.release(); c->spec_vinfo.release(); c->spec_work.release();
     if (c->d_group_counter) (void)hipFree(c->d_group_counter);
@@ -747,38 +747,30 @@ int hrx_fr_columns_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t
 int hrx_fr_columns_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *const *record_planes, size_t n_planes,
                                  const uint16_t *masked, size_t B, size_t M, size_t b_begin, size_t b_count, uint64_t *cells, int flags, void *stream) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
-    const size_t Dn = ctx->s.defs.size();
-    if (!(layout & HRX_LAYOUT_POSITION_MAJOR)) return fail(HRX_ERR_ARG, "record planes are a position-major layout");
-    if (!record_planes || !(n_planes == Dn || (Dn == 1 && n_planes == 2)) || n_planes > kMaxDefsPerLaunch) return fail(HRX_ERR_ARG, "record planes: one buffer per def (at most eight; one def: one buffer or two row stripes)");
-    for (size_t d = 0; d < n_planes; ++d)
-        if (!record_planes[d]) return fail(HRX_ERR_ARG, "NULL plane");
-    return fr_columns_any(ctx, layout, chars, stride, lens, record_planes[0], record_planes, n_planes, 0, masked, 0, B, M, b_begin, b_count, cells, flags, stream);
+    if (int rc = check_rows_planes(ctx, layout, record_planes, n_planes)) return rc;
+    return fr_columns_any(ctx, layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, masked, 0, B, M, b_begin, b_count, cells, flags, stream);
 }
 
 static int fr_columns_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, const uint32_t *const *planes, size_t n_planes,
                           size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M, size_t b_begin, size_t b_count, uint64_t *cells, int flags, void *stream) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (b_count == 0) return HRX_OK;
-    if (!chars || !lens || !records || !masked || !cells) return fail(HRX_ERR_ARG, "NULL buffer");
+    if (!chars || !lens || (!records && !planes) || !masked || !cells) return fail(HRX_ERR_ARG, "NULL buffer");
     if (b_begin > B || b_count > B - b_begin) return fail(HRX_ERR_ARG, "string range outside the batch");
-    if (M == 0 || M > (1u << 24) || B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "shape out of range");
-    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_POSITION_MAJOR &&
-        layout != (HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR))
-        return fail(HRX_ERR_ARG, "unknown layout");
+    if (M == 0 || M > kRowsMaxRows || B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "shape out of range");
+    if (int rc = check_rows_layout(layout)) return rc;
     if ((uintptr_t)cells & 15) return fail(HRX_ERR_ARG, "cells must be 16-byte aligned");
     if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
     FrArgs a{};
-    a.chars = chars; a.stride = stride; a.lens = lens; a.records = records; a.masked = masked;
+    a.chars = chars; a.stride = stride; a.lens = lens; a.records = records; a.masked = masked;       // (records == NULL: planes, checked by the caller)
+    for (size_t d = 0; planes && d < n_planes; ++d) a.planes[d] = planes[d];
+    a.n_stripes = planes && n_planes == 2 * ctx->s.defs.size() ? 2u : 1u;
     a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)ctx->s.defs.size(); a.layout = (uint32_t)layout;
-    a.rec_pitch = (uint32_t)(rec_pitch ? rec_pitch : M); a.msk_pitch = (uint32_t)(msk_pitch ? msk_pitch : M);
+    a.rec_pitch = rec_pitch ? rec_pitch : M; a.msk_pitch = msk_pitch ? msk_pitch : M;
     a.canonical = (flags & HRX_FR_CANONICAL) ? 1u : 0u;
-    if (planes) {
-        for (size_t d = 0; d < n_planes && d < kMaxDefsPerLaunch; ++d) a.rec_planes[d] = planes[d];
-        a.rec_stripes = n_planes == 2 * ctx->s.defs.size() ? 2u : 1u;
-    }
     // one launch per 32768 strings (the grid's y dimension); every launch writes its slice of each column
     const size_t total = b_count;
     for (size_t done = 0; done < total; done += 32768) {
@@ -810,21 +802,33 @@ void hrx_position_major_plane_sizes(size_t B, size_t M, size_t *plane_u32, size_
     if (masked_u16) *masked_u16 = (M + 7) / 8 * B * 8;
 }
 
+// the shape rule of the two hrx_rows_of_string_*: what hrx::RowsIn (hrx_rows.hpp) holds
+static bool rows_of_string_shape(size_t B, size_t M, size_t D, size_t b) {
+    return b < B && B <= 0xffffffffull - 64 && M != 0 && M <= kRowsMaxRows && D != 0 && D <= HRX_MAX_DEFS;
+}
+
 int hrx_rows_of_string_planes(const uint32_t *const *record_planes, size_t n_planes, const uint16_t *masked_pm, size_t B, size_t M, size_t D, size_t b, uint32_t *records, uint16_t *masked) {
     if (!record_planes && !masked_pm) return fail(HRX_ERR_ARG, "NULL buffer");
     if ((record_planes && !records) || (masked_pm && !masked)) return fail(HRX_ERR_ARG, "NULL output");
-    if (b >= B || M == 0 || D == 0 || D > HRX_MAX_DEFS) return fail(HRX_ERR_ARG, "string index or shape out of range");
+    if (!rows_of_string_shape(B, M, D, b)) return fail(HRX_ERR_ARG, "string index or shape out of range");
     if (record_planes && !(n_planes == D || (D == 1 && n_planes == 2))) return fail(HRX_ERR_ARG, "one buffer per def (one def: one buffer or two row stripes)");
-    const size_t k = b / HRX_PM_BLOCK, bl = b % HRX_PM_BLOCK, nb = std::min<size_t>(HRX_PM_BLOCK, B - k * HRX_PM_BLOCK);
-    const size_t q4 = (M + 3) / 4, R = record_planes ? n_planes / D : 1, slots = (q4 + R - 1) / R;
     if (record_planes) {
         for (size_t p = 0; p < n_planes; ++p)
             if (!record_planes[p]) return fail(HRX_ERR_ARG, "NULL plane");
+        // A plane is the position-major records of a one-def config, and so is a row stripe over the quads it holds (stripe p: quads p, p + R, ... at slots
+        // 0, 1, ...): buffer by buffer through the interleaved form's quad address (D may exceed what one launch takes)
+        const size_t R = n_planes / D, q4 = (M + 3) / 4;
+        RowsIn a{};
+        a.B = (uint32_t)B; a.M = (uint32_t)(4 * ((q4 + R - 1) / R)); a.D = 1u; a.layout = HRX_LAYOUT_POSITION_MAJOR; a.n_stripes = 1u;
         for (size_t d = 0; d < D; ++d)
-            for (size_t q = 0; q < q4; ++q) {      // quad q of def d: buffer (q % R) * D + d, slot q / R
-                const uint32_t *src = record_planes[(q % R) * D + d] + k * HRX_PM_BLOCK * slots * 4 + ((q / R) * nb + bl) * 4;
-                const size_t rows = std::min<size_t>(4, M - 4 * q);
-                for (size_t i = 0; i < rows; ++i) records[(4 * q + i) * D + d] = src[i];
+            for (size_t p = 0; p < R; ++p) {
+                a.records = record_planes[p * D + d];
+                const RowsPlace s = rows_place<false>(a, (uint32_t)b);
+                for (size_t q = p; q < q4; q += R) {
+                    const uint32_t *src = rec_quad<kRecPm>(a, s, (uint32_t)(q / R), 0u);
+                    const size_t rows = std::min<size_t>(4, M - 4 * q);
+                    for (size_t i = 0; i < rows; ++i) records[(4 * q + i) * D + d] = src[i];
+                }
             }
     }
     if (masked_pm) return hrx_rows_of_string_position_major(nullptr, masked_pm, B, M, D, b, nullptr, masked);
@@ -834,23 +838,19 @@ int hrx_rows_of_string_planes(const uint32_t *const *record_planes, size_t n_pla
 int hrx_rows_of_string_position_major(const uint32_t *records_pm, const uint16_t *masked_pm, size_t B, size_t M, size_t D, size_t b, uint32_t *records, uint16_t *masked) {
     if (!records_pm && !masked_pm) return fail(HRX_ERR_ARG, "NULL buffer");
     if ((records_pm && !records) || (masked_pm && !masked)) return fail(HRX_ERR_ARG, "NULL output");
-    if (b >= B || M == 0 || D == 0 || D > HRX_MAX_DEFS) return fail(HRX_ERR_ARG, "string index or shape out of range");
-    const size_t k = b / HRX_PM_BLOCK, bl = b % HRX_PM_BLOCK, nb = std::min<size_t>(HRX_PM_BLOCK, B - k * HRX_PM_BLOCK);
-    const size_t q4 = (M + 3) / 4, q8 = (M + 7) / 8;
-    if (records_pm) {
-        const uint32_t *base = records_pm + k * HRX_PM_BLOCK * q4 * D * 4 + bl * 4;       // quad q of def d: base + (q * D + d) * nb * 4
-        for (size_t q = 0; q < q4; ++q) {
-            const size_t rows = std::min<size_t>(4, M - 4 * q);
-            for (size_t d = 0; d < D; ++d) {
-                const uint32_t *src = base + (q * D + d) * nb * 4;
-                for (size_t i = 0; i < rows; ++i) records[(4 * q + i) * D + d] = src[i];
-            }
+    if (!rows_of_string_shape(B, M, D, b)) return fail(HRX_ERR_ARG, "string index or shape out of range");
+    RowsIn a{};
+    a.records = records_pm; a.masked = masked_pm;
+    a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)D; a.layout = HRX_LAYOUT_POSITION_MAJOR; a.n_stripes = 1u;
+    const RowsPlace s = masked_pm ? rows_place<true>(a, (uint32_t)b) : rows_place<false>(a, (uint32_t)b);
+    for (size_t q = 0; records_pm && q < (M + 3) / 4; ++q) {
+        const size_t rows = std::min<size_t>(4, M - 4 * q);
+        for (size_t d = 0; d < D; ++d) {
+            const uint32_t *src = rec_quad<kRecPm>(a, s, (uint32_t)q, (uint32_t)d);
+            for (size_t i = 0; i < rows; ++i) records[(4 * q + i) * D + d] = src[i];
         }
     }
-    if (masked_pm) {
-        const uint16_t *base = masked_pm + k * HRX_PM_BLOCK * q8 * 8 + bl * 8;
-        for (size_t o = 0; o < q8; ++o) std::memcpy(masked + 8 * o, base + o * nb * 8, 2 * std::min<size_t>(8, M - 8 * o));
-    }
+    for (size_t o = 0; masked_pm && o < (M + 7) / 8; ++o) std::memcpy(masked + 8 * o, msk_octet(s, (uint32_t)o), 2 * std::min<size_t>(8, M - 8 * o));
     return HRX_OK;
 }
 

@@ -21,6 +21,9 @@
 #include "hrx_defs.hpp"
 #include "hrx_error.hpp"
 #include "hrx_plan.hpp"
+#include "hrx_rows.hpp"
+
+namespace hrx { struct VerifyDefRows; }      // hrx_verify.hpp
 
 #define HRX_INTERNAL __attribute__((visibility("hidden")))
 
@@ -66,6 +69,12 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
+
+// an image of the circuit's table rows a context keeps once built: in host memory, and its device copy
+struct CtxImage {
+    std::vector<uint32_t> host;
+    DevBuf dev;
+};
 
 // hrx_place_api.cpp
 struct hrx_place_arena;
@@ -153,12 +162,9 @@ struct hrx_ctx {
     DevBuf match_status;             // selected "via rows": the slice's status words by slot (hrx_match_selected_device)
     hipStream_t match_stream = nullptr;
     bool match_used = false;
-    // VERIFY (hrx_verify_api.cpp): the check tables (hrx_verify.hpp build_verify_image), built at the context's first verify call, and their device copy
-    std::vector<uint32_t> verify_image;
-    DevBuf verify_tab;
-    // LOOKUP COUNTS (hrx_lookup_api.cpp): the image (hrx_lookup.hpp build_lookup_image), built at the context's first lookup call, and its device copy
-    std::vector<uint32_t> lookup_image;
-    DevBuf lookup_tab;
+    // VERIFY (hrx_verify_api.cpp): the check tables (hrx_verify.hpp build_verify_image); LOOKUP COUNTS (hrx_lookup_api.cpp): the image (hrx_lookup.hpp
+    // build_lookup_image).  Each built at the context's first call of its kind (ctx_image_host / ctx_image_device below)
+    CtxImage verify_img, lookup_img;
     DevBuf d_cw;                    // CLASS-WIDE image of a config of 4 .. 8 defs (DefsSet::cw_image): the single-launch def-parallel path and the fused-wide match
 #ifdef HRX_STAMPS
     DevBuf stamps;                  // tools-only build: 8 u64 per walker pair of the position-major kernel (hrx_kernel_pm.hip)
@@ -178,3 +184,18 @@ HRX_INTERNAL int launch_batch(hrx_ctx *ctx, const uint8_t *chars, size_t stride,
 // (one_stream: in, walk, out on one stream whatever HRX_OPT_HOST_PIPELINE says and without taking part in the context's comparison of its two transfer modes: the device part of a split call)
 HRX_INTERNAL int batch_host_locked(hrx_ctx *ctx, const uint8_t *chars, size_t stride, const uint32_t *lens, size_t B, size_t M, uint32_t *records, uint16_t *masked, uint64_t *status,
                                    bool one_stream = false);
+// hrx_rows_api.cpp: the argument rules of the entry points that read witness rows (hrx_rows.hpp), every refusal HRX_ERR_ARG.  check_rows: layout, planes,
+// pitches against M, shape range, the alignment of lens and — device / host rules — of chars, records, planes and masked (NULL: the reader has none);
+// fills `a`.  Buffers of the entry point's own (verdict, counts, cells, a workspace) are its own to check.  The field-cell entry points take the layout
+// and planes rules alone.
+HRX_INTERNAL int check_rows_layout(int layout);
+HRX_INTERNAL int check_rows_planes(const hrx_ctx *ctx, int layout, const uint32_t *const *planes, size_t n_planes);
+HRX_INTERNAL int check_rows(const hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
+                            const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M,
+                            bool device, hrx::RowsIn &a);
+// hrx_rows_api.cpp: `im` of the context ready in host memory (the caller holds ctx->mu) / on its device (... and has set the device).  First use: built by
+// `build` from the rows RegexTableConfig::load assigns (never from a walk table), and for the device uploaded — an allocation and a blocking copy: not
+// inside a stream capture.  Never rebuilt once it is there.  noun: "verify" / "lookup counts", for the messages
+using CtxImageBuilder = bool (*)(const hrx::VerifyDefRows *rows, size_t D, std::vector<uint32_t> &img);
+HRX_INTERNAL int ctx_image_host(hrx_ctx *ctx, CtxImage &im, CtxImageBuilder build, const char *noun);
+HRX_INTERNAL int ctx_image_device(hrx_ctx *ctx, CtxImage &im, CtxImageBuilder build, const char *noun, void *stream);

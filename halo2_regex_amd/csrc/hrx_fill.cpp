@@ -5,12 +5,12 @@
 //   hrx_witness_of_string    -> exactly the Vecs of lib.rs:316-318 (what bindings/rust/hrx.rs WitnessOf holds);
 //   hrx_witness_columns_host -> the integer content of every advice column the loops at lib.rs:339-348, 419-519 assign and of the two result columns (:752-771), column-major
 //                               over the circuits of the batch — the host-side, plain-integer twin of hrx_fr_columns_device (same column order).
-#include <algorithm>
 #include <cstring>
 #include <string>
 
 #include "../../include/hrx.h"
 #include "hrx_error.hpp"
+#include "hrx_rows.hpp"
 
 namespace {
 inline int bad(const char *msg) { return hrx::set_last_error(HRX_ERR_ARG, msg); }
@@ -46,40 +46,42 @@ size_t hrx_witness_num_columns(size_t D) { return 4 + 4 * D; }
 int hrx_witness_columns_host(int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch, const uint16_t *masked,
                              size_t msk_pitch, size_t B, size_t M, size_t D, size_t b_begin, size_t b_count, uint64_t *columns) {
     if (!chars || !lens || !records || !masked || !columns) return bad("hrx_witness_columns_host: NULL buffer");
-    if (D == 0 || D > HRX_MAX_DEFS || M == 0 || b_begin > B || b_count > B - b_begin) return bad("hrx_witness_columns_host: shape out of range");
-    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_POSITION_MAJOR && layout != (HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR))
-        return bad("hrx_witness_columns_host: unknown layout");
-    const bool pm = (layout & HRX_LAYOUT_POSITION_MAJOR) != 0, in_pm = (layout & HRX_LAYOUT_INPUT_POSITION_MAJOR) != 0;
+    if (D == 0 || D > HRX_MAX_DEFS || M == 0 || M > hrx::kRowsMaxRows || B > 0xffffffffull - 64 || b_begin > B || b_count > B - b_begin)
+        return bad("hrx_witness_columns_host: shape out of range");
+    if (!hrx::rows_layout_known(layout)) return bad("hrx_witness_columns_host: unknown layout");
     if (!rec_pitch) rec_pitch = M;
     if (!msk_pitch) msk_pitch = M;
-    if (!pm && (rec_pitch < M || msk_pitch < M)) return bad("hrx_witness_columns_host: pitches < M");
-    const size_t q4 = (M + 3) / 4, q8 = (M + 7) / 8, col = b_count * M;
-    for (size_t j = 0; j < b_count; ++j) {
-        const size_t b = b_begin + j;
-        const size_t k = b / HRX_PM_BLOCK, bl = b % HRX_PM_BLOCK, nb = std::min<size_t>(HRX_PM_BLOCK, B - k * HRX_PM_BLOCK);
-        const size_t n = lens[b];
-        if (n > M) return bad("hrx_witness_columns_host: a string longer than max_chars_size (its status word says so: no rows)");
-        uint64_t *c0 = columns + j * M;
-        auto rec_at = [&](size_t r, size_t d) -> uint32_t {
-            return pm ? records[k * HRX_PM_BLOCK * q4 * D * 4 + ((r / 4 * D + d) * nb + bl) * 4 + r % 4] : records[(b * rec_pitch + r) * D + d];
-        };
-        auto msk_at = [&](size_t r) -> uint16_t { return pm ? masked[k * HRX_PM_BLOCK * q8 * 8 + (r / 8 * nb + bl) * 8 + r % 8] : masked[b * msk_pitch + r]; };
-        auto chr_at = [&](size_t i) -> uint8_t { return in_pm ? chars[k * HRX_PM_BLOCK * stride + ((i / 16) * nb + bl) * 16 + i % 16] : chars[b * stride + i]; };
-        for (size_t r = 0; r < M; ++r) {
-            c0[0 * col + r] = r < n ? 1 : 0;                               // char_enable: lib.rs:339-348
-            c0[1 * col + r] = r < n ? chr_at(r) : 0;                       // characters
-            for (size_t d = 0; d < D; ++d) {
-                const uint32_t x = rec_at(r, d);
-                c0[(2 + 4 * d) * col + r] = x & 0xffffu;                   // states_array[d]: s[r], s[n], then largest + 1 (lib.rs:388-418)
-                c0[(3 + 4 * d) * col + r] = (x >> 16) & 0xffu;             // substr_ids_array[d] (lib.rs:392-395, 459-471)
-                c0[(4 + 4 * d) * col + r] = (x >> 24) & 1u;                // start_enable_array[d] (lib.rs:482-493)
-                c0[(5 + 4 * d) * col + r] = r + 1 < M ? (x >> 25) & 1u : 0;  // end_enable_array[d]; row M - 1 is never assigned (lib.rs:501-519)
+    if (!(layout & HRX_LAYOUT_POSITION_MAJOR) && (rec_pitch < M || msk_pitch < M)) return bad("hrx_witness_columns_host: pitches < M");
+    hrx::RowsIn a{};
+    a.chars = chars; a.stride = stride; a.lens = lens; a.records = records; a.masked = masked; a.n_stripes = 1u;
+    a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)D; a.layout = (uint32_t)layout;
+    a.rec_pitch = rec_pitch; a.msk_pitch = msk_pitch;
+    const size_t col = b_count * M;
+    bool too_long = false;
+    hrx::with_rows_form(a, [&](auto form) {
+        for (size_t j = 0; j < b_count; ++j) {
+            const size_t b = b_begin + j;
+            const size_t n = lens[b];
+            if (n > M) { too_long = true; return; }
+            uint64_t *c0 = columns + j * M;
+            const hrx::RowsOf<decltype(form)::value> src(a, b);
+            for (size_t r = 0; r < M; ++r) {
+                c0[0 * col + r] = r < n ? 1 : 0;                               // char_enable: lib.rs:339-348
+                c0[1 * col + r] = r < n ? src.chr(r) : 0;                      // characters
+                for (size_t d = 0; d < D; ++d) {
+                    const uint32_t x = src.rec(r, d);
+                    c0[(2 + 4 * d) * col + r] = x & 0xffffu;                   // states_array[d]: s[r], s[n], then largest + 1 (lib.rs:388-418)
+                    c0[(3 + 4 * d) * col + r] = (x >> 16) & 0xffu;             // substr_ids_array[d] (lib.rs:392-395, 459-471)
+                    c0[(4 + 4 * d) * col + r] = (x >> 24) & 1u;                // start_enable_array[d] (lib.rs:482-493)
+                    c0[(5 + 4 * d) * col + r] = r + 1 < M ? (x >> 25) & 1u : 0;  // end_enable_array[d]; row M - 1 is never assigned (lib.rs:501-519)
+                }
+                const uint16_t m = (uint16_t)src.msk(r);
+                c0[(2 + 4 * D) * col + r] = m & 0xffu;                         // masked_characters (lib.rs:752-756)
+                c0[(3 + 4 * D) * col + r] = m >> 8;                            // all_substr_ids (lib.rs:757-761)
             }
-            const uint16_t m = msk_at(r);
-            c0[(2 + 4 * D) * col + r] = m & 0xffu;                         // masked_characters (lib.rs:752-756)
-            c0[(3 + 4 * D) * col + r] = m >> 8;                            // all_substr_ids (lib.rs:757-761)
         }
-    }
+    });
+    if (too_long) return bad("hrx_witness_columns_host: a string longer than max_chars_size (its status word says so: no rows)");
     return HRX_OK;
 }
 

@@ -111,13 +111,13 @@ __global__ __launch_bounds__(256) void fr_columns_kernel(const FrArgs a) {
     const uint32_t bi = blockIdx.y;              // index inside the requested range
     const uint32_t b = a.b_begin + bi;
     const uint32_t n = min(a.lens[b], a.M);
-    const bool pm = (a.layout & 1u) != 0, in_pm = (a.layout & 2u) != 0;
+    const RowsPlace s = rows_place<true>(a, b);           // where the string's cells lie (hrx_rows.hpp)
+    const int form = rows_form(a);
     // a wave owns 32 kFrJ consecutive rows and writes them column by column: kFrJ store instructions in a row put 4 KiB
     // of ONE column down before the next column's turn (interleaving the columns instruction by instruction left every stream in
     // 1-KiB pieces)
     const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
     const uint32_t rbase = blockIdx.x * kFrRowsPerBlock + wave * (32u * kFrJ) + (lane >> 1);
-    const uint32_t blk0 = (b / kPmBlock) * kPmBlock, nb = min(kPmBlock, a.B - blk0), bl = b - blk0;   // the string's block of the position-major buffers
     const size_t col_cells = (size_t)a.col_cells;   // cells per column
     uint64_t *out0 = a.cells + ((size_t)bi * a.M + rbase) * 4u + half * 2u;
     auto put_rows = [&](const uint32_t col, const uint32_t (&v)[kFrJ]) {
@@ -143,7 +143,7 @@ __global__ __launch_bounds__(256) void fr_columns_kernel(const FrArgs a) {
         const uint32_t r = min(rbase + j * 32u, a.M - 1u);
         live[j] = (rbase + j * 32u) < n ? 1u : 0u;
         c[j] = 0;
-        if (live[j]) c[j] = in_pm ? a.chars[(size_t)blk0 * a.stride + ((size_t)(r >> 4) * nb + bl) * 16u + (r & 15u)] : a.chars[(size_t)b * a.stride + r];
+        if (live[j]) c[j] = chr_cell(s, r);
     }
     put_rows(0, live);   // char_enable                        lib.rs:342,346
     put_rows(1, c);      // characters                         lib.rs:343,347
@@ -152,12 +152,7 @@ __global__ __launch_bounds__(256) void fr_columns_kernel(const FrArgs a) {
 #pragma unroll
         for (uint32_t j = 0; j < kFrJ; ++j) {
             const uint32_t r = min(rbase + j * 32u, a.M - 1u);
-            if (a.rec_planes[0]) {      // (position-major) quad q of def d: buffer (q % R) * D + d, slot q / R of the string's block
-                const uint32_t R = a.rec_stripes == 2u ? 2u : 1u, q = r >> 2, q4 = (a.M + 3u) / 4u, slots = (q4 + R - 1u) / R;
-                rec[j] = a.rec_planes[(q % R) * a.D + d][(size_t)blk0 * slots * 4u + ((size_t)(q / R) * nb + bl) * 4u + (r & 3u)];
-            } else
-            rec[j] = pm ? a.records[((size_t)blk0 * ((a.M + 3u) / 4u) * a.D + ((size_t)(r >> 2) * a.D + d) * nb + bl) * 4u + (r & 3u)]
-                        : a.records[((size_t)b * a.rec_pitch + r) * a.D + d];
+            rec[j] = form == kRecPlanes ? rec_cell<kRecPlanes>(a, s, r, d) : form == kRecPm ? rec_cell<kRecPm>(a, s, r, d) : rec_cell<kRecSm>(a, s, r, d);
         }
 #pragma unroll
         for (uint32_t j = 0; j < kFrJ; ++j) f[j] = rec[j] & 0xffffu;
@@ -176,7 +171,7 @@ __global__ __launch_bounds__(256) void fr_columns_kernel(const FrArgs a) {
 #pragma unroll
     for (uint32_t j = 0; j < kFrJ; ++j) {
         const uint32_t r = min(rbase + j * 32u, a.M - 1u);
-        mk[j] = pm ? a.masked[((size_t)blk0 * ((a.M + 7u) / 8u) + (size_t)(r >> 3) * nb + bl) * 8u + (r & 7u)] : a.masked[(size_t)b * a.msk_pitch + r];
+        mk[j] = form == kRecSm ? msk_cell<false>(s, r) : msk_cell<true>(s, r);
     }
 #pragma unroll
     for (uint32_t j = 0; j < kFrJ; ++j) f[j] = mk[j] & 0xffu;

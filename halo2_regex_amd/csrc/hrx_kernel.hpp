@@ -9,6 +9,7 @@
 #include "hrx_defs.hpp"
 #include "hrx_extract.hpp"
 #include "hrx_route.hpp"
+#include "hrx_rows.hpp"
 
 namespace hrx {
 
@@ -436,23 +437,15 @@ struct EndpointArgs {
 hipError_t launch_endpoint_flags(const EndpointArgs &a, const uint8_t *const *member, const uint32_t *dims, hipStream_t stream);
 
 // compact witness rows of strings [b_begin, b_begin + b_count) -> bn256::Fr cells, [col][string][row][4]
-struct FrArgs {
-    const uint8_t *chars;
-    uint64_t stride;
-    const uint32_t *lens;
-    const uint32_t *records;
-    const uint16_t *masked;
-    uint32_t B, M, D, layout, rec_pitch, msk_pitch;
+struct FrArgs : RowsIn {   // the rows (hrx_rows.hpp), and
     uint32_t b_begin, b_count;
     uint32_t canonical;   // 1: plain integers instead of Montgomery form
-    const uint32_t *rec_planes[kMaxDefsPerLaunch];   // record planes / the two row stripes of one def (WitnessArgs::rec_planes, ::rec_stripes); rec_planes[0] == NULL: `records`
-    uint32_t rec_stripes;
     uint64_t *cells;      // first cell of string b_begin in column 0
     uint64_t col_cells;   // cells between consecutive columns (= strings of the whole request x M)
 };
 hipError_t launch_fr_columns(const FrArgs &a, hipStream_t stream);
 
-// VERIFY (hrx_kernel_verify.hip): the rules of hrx_verify.hpp over the rows FrArgs describes; one verdict word per string
+// VERIFY (hrx_kernel_verify.hip): the rules of hrx_verify.hpp over the same rows; one verdict word per string
 struct VerifyArgs;     // hrx_verify.hpp
 hipError_t launch_verify_rows(const VerifyArgs &a, hipStream_t stream);
 struct VerifyChunkArgs;

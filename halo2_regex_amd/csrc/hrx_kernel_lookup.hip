@@ -21,71 +21,6 @@ namespace hrx {
 
 namespace {
 
-static_assert(kVfyPmBlock == HRX_PM_BLOCK, "hrx_verify.hpp and include/hrx.h");
-enum : int { kLkSm = 0, kLkPm = 1, kLkPlanes = 2 };
-
-// where string b's cells lie (VerifySrc of hrx_kernel_verify.hip without the masked rows)
-struct LookupSrc {
-    const unsigned char *chr;   // byte i at chr + (i / 16) * chr_step + i % 16
-    size_t chr_step;
-    const uint32_t *rec;        // position-major: quad q of def d at rec + (q * D + d) * rec_step; string-major: (r, d) at rec + r * D + d
-    size_t rec_step;            // planes: quad q at plane[(q % R) * D + d] + pl_off + (q / R) * rec_step
-    size_t pl_off;
-};
-
-__device__ __forceinline__ LookupSrc lookup_src(const LookupArgs &a, const uint32_t b) {
-    LookupSrc s;
-    const bool pm = (a.layout & HRX_LAYOUT_POSITION_MAJOR) != 0, in_pm = (a.layout & HRX_LAYOUT_INPUT_POSITION_MAJOR) != 0;
-    const uint32_t blk0 = (b / kVfyPmBlock) * kVfyPmBlock, nb = min(kVfyPmBlock, a.B - blk0), bl = b - blk0;
-    const size_t q4 = (a.M + 3u) / 4u;
-    if (in_pm) {
-        s.chr = a.chars + (size_t)blk0 * a.stride + (size_t)bl * 16u;
-        s.chr_step = (size_t)nb * 16u;
-    } else {
-        s.chr = a.chars + (size_t)b * a.stride;
-        s.chr_step = 16u;
-    }
-    if (pm) {
-        s.rec = a.records ? a.records + ((size_t)blk0 * q4 * a.D + bl) * 4u : nullptr;
-        s.rec_step = (size_t)nb * 4u;
-        const size_t R = a.n_stripes == 2u ? 2u : 1u;
-        s.pl_off = ((size_t)blk0 * ((q4 + R - 1u) / R) + bl) * 4u;
-    } else {
-        s.rec = a.records + (size_t)b * a.rec_pitch * a.D;
-        s.rec_step = 0;
-        s.pl_off = 0;
-    }
-    return s;
-}
-
-// def d's records of rows 4 q .. 4 q + 3 (rows >= M: never judged)
-template <int REC>
-__device__ __forceinline__ void load_quad(const LookupArgs &a, const LookupSrc &s, const uint32_t d, const uint32_t q, uint32_t (&x)[4]) {
-    if constexpr (REC == kLkSm) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) x[j] = 4u * q + j < a.M ? s.rec[(size_t)(4u * q + j) * a.D + d] : 0u;
-    } else {
-        uint4 v;
-        if constexpr (REC == kLkPm) {
-            v = *reinterpret_cast<const uint4 *>(s.rec + ((size_t)q * a.D + d) * s.rec_step);
-        } else {
-            const uint32_t R = a.n_stripes == 2u ? 2u : 1u;
-            v = *reinterpret_cast<const uint4 *>(a.planes[(q % R) * a.D + d] + s.pl_off + (size_t)(q / R) * s.rec_step);
-        }
-        x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
-    }
-}
-
-// def d's record of row r < M alone
-template <int REC>
-__device__ __forceinline__ uint32_t load_record(const LookupArgs &a, const LookupSrc &s, const uint32_t d, const uint32_t r) {
-    if constexpr (REC == kLkSm) return s.rec[(size_t)r * a.D + d];
-    const uint32_t q = r >> 2;
-    if constexpr (REC == kLkPm) return s.rec[((size_t)q * a.D + d) * s.rec_step + (r & 3u)];
-    const uint32_t R = a.n_stripes == 2u ? 2u : 1u;
-    return a.planes[(q % R) * a.D + d][s.pl_off + (size_t)(q / R) * s.rec_step + (r & 3u)];
-}
-
 template <int REC>
 __global__ __launch_bounds__(kLkThreads) void lookup_counts_kernel(const LookupArgs a) {
     uint32_t *bins = reinterpret_cast<uint32_t *>(smem);
@@ -106,23 +41,29 @@ __global__ __launch_bounds__(kLkThreads) void lookup_counts_kernel(const LookupA
             if (dhi <= lo || dlo >= hi) continue;
             const bool count_miss = dlo >= lo;               // the pass that holds the def's first bin
             uint32_t g_cur = 0xffffffffu, n = 0;
-            LookupSrc s{};
+            RowsPlace s{};
             for (uint32_t item = tid; item < G * Q; item += kLkThreads) {
                 uint32_t g, q;
-                if constexpr (REC == kLkSm) { g = item / Q; q = item - g * Q; }
+                if constexpr (REC == kRecSm) { g = item / Q; q = item - g * Q; }
                 else { g = item & (G - 1u); q = item >> lgG; }
                 if (g >= gv) continue;
                 if (g != g_cur) {
                     const uint32_t b = a.b_begin + i0 + g;
-                    g_cur = g; n = a.lens[b]; s = lookup_src(a, b);
+                    g_cur = g; n = a.lens[b]; s = rows_place<false>(a, b);
                 }
                 if (n > M) continue;                         // the string has no rows: its bins stay 0
                 const uint32_t r0 = 4u * q;
                 uint32_t c4 = 0;
-                if (r0 < n) c4 = *reinterpret_cast<const uint32_t *>(s.chr + (size_t)(r0 >> 4) * s.chr_step + (r0 & 15u));
-                uint32_t x[4];
-                load_quad<REC>(a, s, d, q, x);
-                const uint32_t behind = r0 + 4u < M ? load_record<REC>(a, s, d, r0 + 4u) & 0xffffu : T.dummy;
+                if (r0 < n) c4 = *reinterpret_cast<const uint32_t *>(chr_chunk(s, r0) + (r0 & 15u));
+                uint32_t x[4];                               // def d's records of rows 4 q .. 4 q + 3 (rows >= M: never judged)
+                if constexpr (REC == kRecSm) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) x[j] = r0 + j < M ? rec_cell<kRecSm>(a, s, r0 + j, d) : 0u;
+                } else {
+                    const uint4 v = *reinterpret_cast<const uint4 *>(rec_quad<REC>(a, s, q, d));
+                    x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w;
+                }
+                const uint32_t behind = r0 + 4u < M ? rec_cell<REC>(a, s, r0 + 4u, d) & 0xffffu : T.dummy;
                 uint32_t *mine = bins + (size_t)g * PW;
                 // one add per run of equal bins among the quad's rows (the flagless rows' and the padding rows' tuples all hit the tables' first rows)
                 uint32_t run_at[3] = {kLkNone, kLkNone, kLkNone}, run_n[3] = {0u, 0u, 0u};
@@ -181,9 +122,11 @@ hipError_t launch_lookup_form(const LookupArgs &a, size_t lds_bytes, hipStream_t
 // the caller has checked the arguments, planned G / pass_words / passes and that ceil(b_count / G) workgroups fit a grid
 hipError_t launch_lookup_counts(const LookupArgs &a, size_t lds_bytes, hipStream_t stream) {
     if (a.b_count == 0 || a.M == 0) return hipSuccess;
-    if (!(a.layout & HRX_LAYOUT_POSITION_MAJOR)) return launch_lookup_form<kLkSm>(a, lds_bytes, stream);
-    if (a.records) return launch_lookup_form<kLkPm>(a, lds_bytes, stream);
-    return launch_lookup_form<kLkPlanes>(a, lds_bytes, stream);
+    switch (rows_form(a)) {
+        case kRecSm: return launch_lookup_form<kRecSm>(a, lds_bytes, stream);
+        case kRecPm: return launch_lookup_form<kRecPm>(a, lds_bytes, stream);
+        default: return launch_lookup_form<kRecPlanes>(a, lds_bytes, stream);
+    }
 }
 
 }  // namespace hrx

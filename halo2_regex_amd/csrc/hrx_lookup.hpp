@@ -20,7 +20,7 @@
 
 #include <vector>
 
-#include "hrx_verify.hpp"      // HRX_XHD, VerifyDefRows, kVfyMaxRows, kVfyPmBlock, kVfyMaxPlanes
+#include "hrx_verify.hpp"      // HRX_XHD, RowsIn (hrx_rows.hpp), VerifyDefRows
 
 namespace hrx {
 
@@ -188,16 +188,8 @@ inline LookupPlan plan_lookup(size_t W, size_t b_count, int num_cus) {
     return p;
 }
 
-// What a launch of lookup_counts_kernel reads; the row forms are VerifyArgs'
-struct LookupArgs {
-    const uint8_t *chars;
-    uint64_t stride;
-    const uint32_t *lens;
-    const uint32_t *records;                        // interleaved records (string-major or position-major), or NULL: planes
-    const uint32_t *planes[kVfyMaxPlanes];
-    uint32_t n_stripes;                             // 2: planes[] are the row stripes of one def
-    uint32_t B, M, D, layout;
-    uint64_t rec_pitch;                             // string-major: rows between consecutive strings
+// What a launch of lookup_counts_kernel reads: the rows (no masked rows: masked == NULL), and
+struct LookupArgs : RowsIn {
     uint32_t b_begin, b_count;                      // the window
     const uint32_t *image;                          // build_lookup_image (on the device for the kernel)
     uint32_t W;                                     // lookup_words(image, D)

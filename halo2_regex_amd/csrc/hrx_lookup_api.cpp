@@ -23,84 +23,22 @@ static size_t lookup_run_of(const DefsSet &s, size_t def, size_t *off, size_t *n
     return (w + 3) & ~(size_t)3;
 }
 
-// the context's image in host memory (the caller holds ctx->mu)
-static int lookup_image_ready(hrx_ctx *ctx) {
-    if (!ctx->lookup_image.empty()) return HRX_OK;
-    const size_t D = ctx->s.defs.size();
-    std::vector<std::vector<uint64_t>> tr(D), ep(D);
-    std::vector<VerifyDefRows> rows(D);
-    for (size_t d = 0; d < D; ++d) {
-        tr[d].resize(4 * table_transition_rows(ctx->s, d, nullptr, 0));
-        table_transition_rows(ctx->s, d, tr[d].data(), tr[d].size() / 4);
-        ep[d].resize(3 * table_endpoint_rows(ctx->s, d, nullptr, 0));
-        table_endpoint_rows(ctx->s, d, ep[d].data(), ep[d].size() / 3);
-        const AllstrRegexDef &al = ctx->s.defs[d].allstr;
-        rows[d] = VerifyDefRows{tr[d].data(), tr[d].size() / 4, ep[d].data(), ep[d].size() / 3, al.first_state_val, al.accepted_state_val};
-    }
-    std::vector<uint32_t> img;
-    if (!build_lookup_image(rows.data(), D, img)) return fail(HRX_ERR_BOUNDS, "lookup counts: the config's table rows do not fit the image's dense tables");
-    ctx->lookup_image = std::move(img);
-    return HRX_OK;
-}
-
-// the argument rules the three forms share, in the order the errors are reported: hrx_verify_rows_device's for the rows, hrx_fr_columns_device's for the window
+// the argument rules the forms share: check_rows' (hrx_rows_api.cpp) for the rows (no masked rows), hrx_fr_columns_device's for the window, the outputs'
 static int check_lookup_args(const hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
                              const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
                              uint32_t *counts, uint32_t *misses, bool device, LookupArgs &a) {
-    if (!chars || !lens || !counts || (!records && !planes)) return fail(HRX_ERR_ARG, "NULL buffer");
+    if (!counts) return fail(HRX_ERR_ARG, "NULL buffer");
     if (b_begin > B || b_count > B - b_begin) return fail(HRX_ERR_ARG, "string range outside the batch");
-    if (M == 0 || M > kVfyMaxRows || B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "shape out of range");
-    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_POSITION_MAJOR && layout != (HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR))
-        return fail(HRX_ERR_ARG, "unknown layout");
-    const bool pm = (layout & HRX_LAYOUT_POSITION_MAJOR) != 0;
-    const size_t Dn = ctx->s.defs.size();
-    if (planes) {
-        if (!pm) return fail(HRX_ERR_ARG, "record planes are a position-major layout");
-        if (!(n_planes == Dn || (Dn == 1 && n_planes == 2)) || n_planes > kVfyMaxPlanes)
-            return fail(HRX_ERR_ARG, "record planes: one buffer per def (at most eight; one def: one buffer or two row stripes)");
-        for (size_t d = 0; d < n_planes; ++d)
-            if (!planes[d]) return fail(HRX_ERR_ARG, "NULL plane");
-    }
-    if (!rec_pitch) rec_pitch = M;
-    if (!pm && rec_pitch < M) return fail(HRX_ERR_ARG, "rec_pitch < M");
-    if (((uintptr_t)counts & 15) || ((uintptr_t)misses & 3) || ((uintptr_t)lens & 3)) return fail(HRX_ERR_ARG, "counts must be 16-byte aligned, misses and lens 4-byte");
-    if (device) {     // the kernel reads 16-byte quads and 4-byte pieces of 16-byte input chunks: the alignment of the witness entry points that wrote the rows
-        bool ok = !(stride & 15) && !((uintptr_t)chars & 15) && !((uintptr_t)records & 15);
-        for (size_t d = 0; planes && d < n_planes; ++d) ok = ok && !((uintptr_t)planes[d] & 15);
-        if (!ok) return fail(HRX_ERR_ARG, "chars, records and every record plane must be 16-byte aligned, stride % 16 == 0");
-    } else if (((uintptr_t)records & 3) || ((layout & HRX_LAYOUT_INPUT_POSITION_MAJOR) && (stride & 15))) {
-        return fail(HRX_ERR_ARG, "records must be 4-byte aligned; position-major input: stride % 16 == 0");
-    }
+    if (((uintptr_t)counts & 15) || ((uintptr_t)misses & 3)) return fail(HRX_ERR_ARG, "counts must be 16-byte aligned, misses 4-byte");
     a = LookupArgs{};
-    a.chars = chars; a.stride = stride; a.lens = lens; a.records = planes ? nullptr : records;
-    for (size_t d = 0; planes && d < n_planes; ++d) a.planes[d] = planes[d];
-    a.n_stripes = planes && n_planes == 2 * Dn ? 2u : 1u;
-    a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)Dn; a.layout = (uint32_t)layout;
-    a.rec_pitch = rec_pitch;
+    if (int rc = check_rows(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, nullptr, 0, B, M, device, a)) return rc;
     a.b_begin = (uint32_t)b_begin; a.b_count = (uint32_t)b_count;
     a.counts = counts; a.misses = misses;
     return HRX_OK;
 }
 
-// the context's image on its device (the caller holds ctx->mu and has set the device).  First use: build and upload — an allocation and a blocking copy:
-// not inside a stream capture
-static int lookup_tab_ready(hrx_ctx *ctx, void *stream) {
-    if (ctx->lookup_tab.p) return HRX_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(HRX_ERR_STATE, "lookup counts: the context's image is built and uploaded at its first lookup call, not inside a stream capture");
-    if (int rc = lookup_image_ready(ctx)) return rc;
-    DevBuf tab;
-    HIP_TRY(tab.reserve(ctx->lookup_image.size() * 4));
-    const hipError_t e = hipMemcpy(tab.p, ctx->lookup_image.data(), ctx->lookup_image.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        tab.release();
-        return fail(HRX_ERR_HIP, std::string("lookup counts: image upload: ") + hipGetErrorString(e));
-    }
-    ctx->lookup_tab = tab;
-    return HRX_OK;
-}
+static int lookup_image_host(hrx_ctx *ctx) { return ctx_image_host(ctx, ctx->lookup_img, build_lookup_image, "lookup counts"); }
+static int lookup_image_device(hrx_ctx *ctx, void *stream) { return ctx_image_device(ctx, ctx->lookup_img, build_lookup_image, "lookup counts", stream); }
 
 static int lookup_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
                              const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
@@ -113,9 +51,9 @@ static int lookup_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, siz
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
-    if (int rc = lookup_tab_ready(ctx, stream)) return rc;
-    a.image = (const uint32_t *)ctx->lookup_tab.p;
-    a.W = lookup_words(ctx->lookup_image.data(), a.D);
+    if (int rc = lookup_image_device(ctx, stream)) return rc;
+    a.image = (const uint32_t *)ctx->lookup_img.dev.p;
+    a.W = lookup_words(ctx->lookup_img.host.data(), a.D);
     const LookupPlan p = plan_lookup(a.W, b_count, ctx->num_cus);
     a.G = p.G; a.pass_words = p.pass_words; a.passes = p.passes;
     if ((b_count + p.G - 1) / p.G > 0x7fffffffull) return fail(HRX_ERR_ARG, "more groups of strings than a launch has workgroups: use a smaller window");
@@ -168,10 +106,10 @@ int hrx_lookup_counts_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_
     unsigned threads;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (int rc = lookup_image_ready(ctx)) return rc;
+        if (int rc = lookup_image_host(ctx)) return rc;
         threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
     }
-    a.image = ctx->lookup_image.data();       // (never rebuilt once it is there)
+    a.image = ctx->lookup_img.host.data();       // (never rebuilt once it is there)
     a.W = lookup_words(a.image, a.D);
     lookup_counts_host(a, threads);
     return HRX_OK;

@@ -20,13 +20,7 @@
 
 #include <vector>
 
-#ifndef HRX_XHD
-#if defined(__HIP__)  // clang in HIP mode (hipcc), host and device passes alike
-#define HRX_XHD __attribute__((host)) __attribute__((device)) inline __attribute__((always_inline))
-#else
-#define HRX_XHD inline
-#endif
-#endif
+#include "hrx_rows.hpp"        // HRX_XHD, RowsIn: the rows the rules are run over
 
 #if defined(__clang__)
 #define HRX_VFY_UNROLL _Pragma("unroll")     // the tile loops index register arrays: every index a constant once unrolled
@@ -42,8 +36,6 @@ constexpr uint32_t kVfyFlags = 64, kVfyPadding = 128, kVfyMask = 256;
 constexpr uint32_t kVfyRowShift = 32;               // bits 32..56: the lowest row at which a reported check fails
 constexpr uint32_t kVfyNoRow = 0xffffffffu;
 constexpr uint32_t kVfyNoEntry = 0xffffffffu;       // transition array: no row (char, cur) in the table
-constexpr uint32_t kVfyMaxRows = 1u << 24;          // the largest M a witness entry point takes
-constexpr uint32_t kVfyPmBlock = 65536u;            // = HRX_PM_BLOCK: position-major buffers are blocked by this many strings
 
 // One def's tables inside the image (all offsets in u32 words from the image's start).  The image is [D] VerifyDef, then every def's arrays:
 //   tab    [ns][256] u32   next | substr_id << 16 of transition row (char, cur), kVfyNoEntry where the table has none
@@ -386,7 +378,7 @@ HRX_XHD void verify_fold_chunk(VerifyAcc &a, const VerifyChunk &k) {
 HRX_XHD uint32_t verify_chunk_count(uint32_t M, uint32_t chunk_rows) { return (M + chunk_rows - 1u) / chunk_rows; }
 // 0: not a chunk size (chunk_rows a positive multiple of kVfyChunkAlign, M in range)
 inline size_t verify_chunked_workspace_bytes(size_t B, size_t M, size_t chunk_rows) {
-    if (chunk_rows == 0 || chunk_rows % kVfyChunkAlign || M == 0 || M > kVfyMaxRows || B > 0xffffffffull - 64) return 0;
+    if (chunk_rows == 0 || chunk_rows % kVfyChunkAlign || M == 0 || M > kRowsMaxRows || B > 0xffffffffull - 64) return 0;
     return (size_t)kVfyChunkFields * 4u * (M / chunk_rows + (M % chunk_rows != 0)) * B;
 }
 
@@ -567,18 +559,8 @@ inline bool build_verify_image(const VerifyDefRows *rows, size_t D, std::vector<
     return true;
 }
 
-// What a launch of verify_rows_kernel reads (hrx_kernel_verify.hip); the forms are those of FrArgs (hrx_kernel.hpp)
-constexpr uint32_t kVfyMaxPlanes = 8;               // = kMaxDefsPerLaunch
-struct VerifyArgs {
-    const uint8_t *chars;
-    uint64_t stride;
-    const uint32_t *lens;
-    const uint32_t *records;                        // interleaved records (string-major or position-major), or NULL: planes
-    const uint16_t *masked;
-    const uint32_t *planes[kVfyMaxPlanes];          // record planes, or the two row stripes of one def
-    uint32_t n_stripes;                             // 2: planes[] are the row stripes of one def
-    uint32_t B, M, D, layout;
-    uint64_t rec_pitch, msk_pitch;                  // string-major: rows between consecutive strings
+// What a launch of verify_rows_kernel reads (hrx_kernel_verify.hip): the rows, and
+struct VerifyArgs : RowsIn {
     const uint32_t *image;                          // build_verify_image, on the device
     uint64_t *verdict;
 };

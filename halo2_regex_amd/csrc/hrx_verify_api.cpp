@@ -15,89 +15,25 @@ void verify_rows_host(const VerifyArgs &a, unsigned threads);      // hrx_verify
 void verify_rows_chunked_host(const VerifyArgs &a, uint32_t chunk_rows, uint32_t *summaries, unsigned threads);
 }
 using namespace hrx;
-static_assert(kVfyPmBlock == HRX_PM_BLOCK && kVfyMaxPlanes == kMaxDefsPerLaunch, "hrx_verify.hpp, include/hrx.h and hrx_kernel.hpp");
 static_assert(kVfyFirstState == HRX_VERIFY_FIRST_STATE && kVfyEnable == HRX_VERIFY_ENABLE && kVfyTransition == HRX_VERIFY_TRANSITION &&
                   kVfyStartLookup == HRX_VERIFY_START_LOOKUP && kVfyEndLookup == HRX_VERIFY_END_LOOKUP && kVfyAccept == HRX_VERIFY_ACCEPT &&
                   kVfyFlags == HRX_VERIFY_FLAGS && kVfyPadding == HRX_VERIFY_PADDING && kVfyMask == HRX_VERIFY_MASK && kVfyRowShift == HRX_VERIFY_ROW_SHIFT,
               "hrx_verify.hpp and include/hrx.h");
 
-// the context's check tables in host memory (the caller holds ctx->mu)
-static int verify_image_ready(hrx_ctx *ctx) {
-    if (!ctx->verify_image.empty()) return HRX_OK;
-    const size_t D = ctx->s.defs.size();
-    std::vector<std::vector<uint64_t>> tr(D), ep(D);
-    std::vector<VerifyDefRows> rows(D);
-    for (size_t d = 0; d < D; ++d) {
-        tr[d].resize(4 * table_transition_rows(ctx->s, d, nullptr, 0));
-        table_transition_rows(ctx->s, d, tr[d].data(), tr[d].size() / 4);
-        ep[d].resize(3 * table_endpoint_rows(ctx->s, d, nullptr, 0));
-        table_endpoint_rows(ctx->s, d, ep[d].data(), ep[d].size() / 3);
-        const AllstrRegexDef &al = ctx->s.defs[d].allstr;
-        rows[d] = VerifyDefRows{tr[d].data(), tr[d].size() / 4, ep[d].data(), ep[d].size() / 3, al.first_state_val, al.accepted_state_val};
-    }
-    std::vector<uint32_t> img;
-    if (!build_verify_image(rows.data(), D, img)) return fail(HRX_ERR_BOUNDS, "verify: the config's table rows do not fit the checker's dense tables");
-    ctx->verify_image = std::move(img);
-    return HRX_OK;
-}
-
-// the argument rules the three forms share, in the order the errors are reported; fills `a` but image and verdict's meaning
+// the argument rules the forms share: check_rows' (hrx_rows_api.cpp) for the rows, and the verdict's; fills `a` but image
 static int check_verify_args(const hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
                              const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M,
                              uint64_t *verdict, bool device, VerifyArgs &a) {
-    if (!chars || !lens || !masked || !verdict || (!records && !planes)) return fail(HRX_ERR_ARG, "NULL buffer");
-    if (M == 0 || M > kVfyMaxRows || B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "shape out of range");
-    if (layout != HRX_LAYOUT_STRING_MAJOR && layout != HRX_LAYOUT_POSITION_MAJOR && layout != (HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR))
-        return fail(HRX_ERR_ARG, "unknown layout");
-    const bool pm = (layout & HRX_LAYOUT_POSITION_MAJOR) != 0;
-    const size_t Dn = ctx->s.defs.size();
-    if (planes) {
-        if (!pm) return fail(HRX_ERR_ARG, "record planes are a position-major layout");
-        if (!(n_planes == Dn || (Dn == 1 && n_planes == 2)) || n_planes > kVfyMaxPlanes)
-            return fail(HRX_ERR_ARG, "record planes: one buffer per def (at most eight; one def: one buffer or two row stripes)");
-        for (size_t d = 0; d < n_planes; ++d)
-            if (!planes[d]) return fail(HRX_ERR_ARG, "NULL plane");
-    }
-    if (!rec_pitch) rec_pitch = M;
-    if (!msk_pitch) msk_pitch = M;
-    if (!pm && (rec_pitch < M || msk_pitch < M)) return fail(HRX_ERR_ARG, "pitches < M");
-    if (((uintptr_t)verdict & 7) || ((uintptr_t)lens & 3)) return fail(HRX_ERR_ARG, "verdict must be 8-byte aligned, lens 4-byte");
-    if (device) {     // the kernel reads 16-byte chunks, quads and octets: the alignment of the witness entry points that wrote the rows
-        bool ok = !(stride & 15) && !((uintptr_t)chars & 15) && !((uintptr_t)records & 15) && !((uintptr_t)masked & 15);
-        for (size_t d = 0; planes && d < n_planes; ++d) ok = ok && !((uintptr_t)planes[d] & 15);
-        if (!ok) return fail(HRX_ERR_ARG, "chars, records, masked and every record plane must be 16-byte aligned, stride % 16 == 0");
-    } else if (((uintptr_t)records & 3) || ((uintptr_t)masked & 1) || ((layout & HRX_LAYOUT_INPUT_POSITION_MAJOR) && (stride & 15))) {
-        return fail(HRX_ERR_ARG, "records must be 4-byte aligned, masked 2-byte; position-major input: stride % 16 == 0");
-    }
+    if (!masked || !verdict) return fail(HRX_ERR_ARG, "NULL buffer");
+    if ((uintptr_t)verdict & 7) return fail(HRX_ERR_ARG, "verdict must be 8-byte aligned");
     a = VerifyArgs{};
-    a.chars = chars; a.stride = stride; a.lens = lens; a.records = planes ? nullptr : records; a.masked = masked;
-    for (size_t d = 0; planes && d < n_planes; ++d) a.planes[d] = planes[d];
-    a.n_stripes = planes && n_planes == 2 * Dn ? 2u : 1u;
-    a.B = (uint32_t)B; a.M = (uint32_t)M; a.D = (uint32_t)Dn; a.layout = (uint32_t)layout;
-    a.rec_pitch = rec_pitch; a.msk_pitch = msk_pitch;
+    if (int rc = check_rows(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, masked, msk_pitch, B, M, device, a)) return rc;
     a.verdict = verdict;
     return HRX_OK;
 }
 
-// the context's check tables on its device (the caller holds ctx->mu and has set the device).  First use: build and upload — an allocation and a
-// blocking copy: not inside a stream capture
-static int verify_tab_ready(hrx_ctx *ctx, void *stream) {
-    if (ctx->verify_tab.p) return HRX_OK;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return fail(HRX_ERR_STATE, "verify: the context's check tables are built and uploaded at its first verify call, not inside a stream capture");
-    if (int rc = verify_image_ready(ctx)) return rc;
-    DevBuf tab;
-    HIP_TRY(tab.reserve(ctx->verify_image.size() * 4));
-    const hipError_t e = hipMemcpy(tab.p, ctx->verify_image.data(), ctx->verify_image.size() * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) {
-        tab.release();
-        return fail(HRX_ERR_HIP, std::string("verify: table upload: ") + hipGetErrorString(e));
-    }
-    ctx->verify_tab = tab;
-    return HRX_OK;
-}
+static int verify_image_host(hrx_ctx *ctx) { return ctx_image_host(ctx, ctx->verify_img, build_verify_image, "verify"); }
+static int verify_image_device(hrx_ctx *ctx, void *stream) { return ctx_image_device(ctx, ctx->verify_img, build_verify_image, "verify", stream); }
 
 static int verify_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
                              const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M,
@@ -110,8 +46,8 @@ static int verify_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, siz
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
-    if (int rc = verify_tab_ready(ctx, stream)) return rc;
-    a.image = (const uint32_t *)ctx->verify_tab.p;
+    if (int rc = verify_image_device(ctx, stream)) return rc;
+    a.image = (const uint32_t *)ctx->verify_img.dev.p;
     HIP_TRY(launch_verify_rows(a, (hipStream_t)stream));
     return HRX_OK;
 }
@@ -143,8 +79,8 @@ static int verify_chunked_device_any(hrx_ctx *ctx, int layout, const uint8_t *ch
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
-    if (int rc = verify_tab_ready(ctx, stream)) return rc;
-    ca.a.image = (const uint32_t *)ctx->verify_tab.p;
+    if (int rc = verify_image_device(ctx, stream)) return rc;
+    ca.a.image = (const uint32_t *)ctx->verify_img.dev.p;
     HIP_TRY(launch_verify_chunked(ca, (hipStream_t)stream));
     return HRX_OK;
 }
@@ -171,10 +107,10 @@ int hrx_verify_rows_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t 
     unsigned threads;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (int rc = verify_image_ready(ctx)) return rc;
+        if (int rc = verify_image_host(ctx)) return rc;
         threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
     }
-    a.image = ctx->verify_image.data();       // (never rebuilt once it is there)
+    a.image = ctx->verify_img.host.data();       // (never rebuilt once it is there)
     verify_rows_host(a, threads);
     return HRX_OK;
 }
@@ -212,10 +148,10 @@ int hrx_verify_rows_chunked_host(hrx_ctx *ctx, int layout, const uint8_t *chars,
     unsigned threads;
     {
         std::lock_guard<std::mutex> lk(ctx->mu);
-        if (int rc = verify_image_ready(ctx)) return rc;
+        if (int rc = verify_image_host(ctx)) return rc;
         threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
     }
-    a.image = ctx->verify_image.data();
+    a.image = ctx->verify_img.host.data();
     std::vector<uint32_t> summaries;      // (the device form's workspace; here the call's own)
     try {
         summaries.resize(verify_chunked_workspace_bytes(B, M, C) / 4);

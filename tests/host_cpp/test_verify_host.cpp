@@ -351,20 +351,20 @@ static void images(const std::vector<Def> &defs, uint32_t M, size_t B) {
         if (b % 3 == 2 && M > 2) R.msk[M / 2] ^= 0x0101;          // some strings carry a wrong masked cell
         lens[b] = n;
         want[b] = verify_string(img.get(), D, n, M, OneString(R));
-        const size_t k = b / kVfyPmBlock, bl = b % kVfyPmBlock, nb = std::min<size_t>(kVfyPmBlock, B - k * kVfyPmBlock);
+        const size_t k = b / HRX_PM_BLOCK, bl = b % HRX_PM_BLOCK, nb = std::min<size_t>(HRX_PM_BLOCK, B - k * HRX_PM_BLOCK);
         for (uint32_t i = 0; i < n; ++i) {
             c_sm[b * stride + i] = R.chars[i];
-            c_pm[k * kVfyPmBlock * stride + ((i / 16) * nb + bl) * 16 + i % 16] = R.chars[i];
+            c_pm[k * HRX_PM_BLOCK * stride + ((i / 16) * nb + bl) * 16 + i % 16] = R.chars[i];
         }
         for (uint32_t r = 0; r < M; ++r) {
             for (uint32_t d = 0; d < D; ++d) {
                 const uint32_t x = R.rec[(size_t)r * D + d];
                 r_sm[(b * M + r) * D + d] = x;
                 r_pit[(b * rp + r) * D + d] = x;
-                r_pm[k * kVfyPmBlock * q4 * D * 4 + ((r / 4 * D + d) * nb + bl) * 4 + r % 4] = x;
+                r_pm[k * HRX_PM_BLOCK * q4 * D * 4 + ((r / 4 * D + d) * nb + bl) * 4 + r % 4] = x;
             }
             m_sm[b * M + r] = m_pit[b * mp + r] = R.msk[r];
-            m_pm[k * kVfyPmBlock * q8 * 8 + (r / 8 * nb + bl) * 8 + r % 8] = R.msk[r];
+            m_pm[k * HRX_PM_BLOCK * q8 * 8 + (r / 8 * nb + bl) * 8 + r % 8] = R.msk[r];
         }
     }
     const auto lens_x = exact(lens);
@@ -400,7 +400,7 @@ int main() {
         images(two, M, 130);
         images(five, M, 7);
     }
-    images(one, 7, kVfyPmBlock + 3);          // a second block of three strings
+    images(one, 7, HRX_PM_BLOCK + 3);          // a second block of three strings
     // tables a dense array cannot hold are refused
     std::vector<uint64_t> tr = kDef1.transition_rows(), ep = kDef1.endpoint_rows();
     std::vector<uint32_t> img;
