@@ -248,6 +248,22 @@ extern "C" {
                                   records: *const u32, rec_pitch: usize, b: usize, m: usize, b_begin: usize, b_count: usize,
                                   counts: *mut u32, misses: *mut u32) -> c_int;
     pub fn hrx_ctx_lookup_group(ctx: *mut hrx_ctx, b_count: usize, group: *mut usize, passes: *mut usize) -> c_int;
+    /// LOOKUP COMPRESS: the three lookup tuples of every witness row (cells [3 D][b_count][M][4] u64) and the rows of the fixed tables (cells [n_theta][W][4]
+    /// in the index space of the counts) folded with a challenge theta into bn256::Fr cells; theta_stride 4 (one challenge per string / run) or 0
+    pub fn hrx_lookup_num_columns(d: usize) -> usize;
+    pub fn hrx_lookup_compress_inputs_device(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                             records: *const u32, rec_pitch: usize, b: usize, m: usize, b_begin: usize, b_count: usize,
+                                             theta: *const u64, theta_stride: usize, cells: *mut u64, flags: c_int, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_compress_inputs_device_planes(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                                    record_planes: *const *const u32, n_planes: usize, b: usize, m: usize, b_begin: usize, b_count: usize,
+                                                    theta: *const u64, theta_stride: usize, cells: *mut u64, flags: c_int, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_compress_inputs_host(ctx: *mut hrx_ctx, layout: c_int, chars: *const u8, stride: usize, lens: *const u32,
+                                           records: *const u32, rec_pitch: usize, b: usize, m: usize, b_begin: usize, b_count: usize,
+                                           theta: *const u64, theta_stride: usize, cells: *mut u64, flags: c_int) -> c_int;
+    pub fn hrx_lookup_compress_table_device(ctx: *mut hrx_ctx, theta: *const u64, theta_stride: usize, n_theta: usize, cells: *mut u64, flags: c_int,
+                                            stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_compress_table_host(ctx: *mut hrx_ctx, theta: *const u64, theta_stride: usize, n_theta: usize, cells: *mut u64, flags: c_int) -> c_int;
+    pub fn hrx_fr_mul(a: *const u64, b: *const u64, out: *mut u64);
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

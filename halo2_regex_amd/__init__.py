@@ -154,6 +154,13 @@ def _load():
         "hrx_lookup_counts_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, sz, sz, sz, sz, vp, vp, vp]),
         "hrx_lookup_counts_host": (i, [vp, i, vp, sz, vp, vp, sz, sz, sz, sz, sz, vp, vp]),
         "hrx_ctx_lookup_group": (i, [vp, sz, C.POINTER(sz), C.POINTER(sz)]),
+        "hrx_lookup_num_columns": (sz, [sz]),
+        "hrx_lookup_compress_inputs_device": (i, [vp, i, vp, sz, vp, vp, sz, sz, sz, sz, sz, vp, sz, vp, i, vp]),
+        "hrx_lookup_compress_inputs_device_planes": (i, [vp, i, vp, sz, vp, C.POINTER(vp), sz, sz, sz, sz, sz, vp, sz, vp, i, vp]),
+        "hrx_lookup_compress_inputs_host": (i, [vp, i, vp, sz, vp, vp, sz, sz, sz, sz, sz, vp, sz, vp, i]),
+        "hrx_lookup_compress_table_device": (i, [vp, vp, sz, sz, vp, i, vp]),
+        "hrx_lookup_compress_table_host": (i, [vp, vp, sz, sz, vp, i]),
+        "hrx_fr_mul": (None, [_u64p, _u64p, _u64p]),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -632,6 +639,15 @@ def _torch_row_pitches(chars, records, masked, layout, D, rec_pitch, msk_pitch, 
         if not msk_pitch and masked is not None and masked.dim() == 2:
             msk_pitch = masked.stride(0)
     return stride, int(rec_pitch), int(msk_pitch)
+
+
+def _theta_stride(theta, count, dtype):
+    """theta_stride of the compress entry points for a contiguous (count, 4) — 4 — or (4,) — 0 — array or tensor of limbs"""
+    shape = tuple(theta.shape)
+    contiguous = theta.is_contiguous() if hasattr(theta, "is_contiguous") else theta.flags.c_contiguous
+    if theta.dtype != dtype or not contiguous or shape not in ((4,), (count, 4)):
+        raise HrxError(HRX_ERR_ARG, "theta: contiguous 64-bit limbs of shape (4,) or (%d, 4)" % count)
+    return 0 if shape == (4,) else 4
 
 
 def _numpy_rows(chars, records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride):
@@ -1441,6 +1457,85 @@ class RegexVerifyConfig:
                                           b_count, out.ctypes.data, misses.ctypes.data))
         return out, misses
 
+    def lookup_compress_inputs(self, chars, lens, rec, theta, layout=LAYOUT_STRING_MAJOR, planes=None, b_begin=0, b_count=None, out=None, canonical=False,
+                               chars_pm_stride=None, rec_pitch=0, stream=None):
+        """hrx_lookup_compress_inputs_device / _planes: the three lookup tuples of every witness row of strings [b_begin, b_begin + b_count), folded with the
+        challenge into bn256::Fr cells (include/hrx.h LOOKUP COMPRESS): int64 CUDA tensor [3 D][b_count][M][4] of limbs, column 3 d + k = the transition / start
+        / end lookup of def d (FR_LOOKUP_COLUMN_NAMES).  theta: an int64 CUDA tensor of limbs, (b_count, 4) — one challenge per string — or (4,) — one for the
+        call; Montgomery limbs in and out unless canonical.  chars, lens, `layout`, rec / planes, rec_pitch and chars_pm_stride are lookup_counts'.  out: the
+        caller's contiguous int64 tensor of exactly that size, written in place.  One launch, asynchronous on `stream` (default: torch's current stream),
+        capturable from the first call."""
+        assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and chars.dtype == torch.uint8
+        B, M, D = lens.numel(), self.max_chars_size, self.num_defs
+        b_count = B - b_begin if b_count is None else int(b_count)
+        stride, rec_pitch, _ = _torch_row_pitches(chars, None if planes is not None else rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
+        theta_stride = _theta_stride(theta, b_count, torch.int64)
+        ncols = 3 * D
+        if out is None:
+            out = torch.empty((ncols, b_count, M, 4), dtype=torch.int64, device=lens.device)
+        elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != ncols * b_count * M * 4:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous int64 tensor of [%d][%d][%d][4] elements" % (ncols, b_count, M))
+        s = torch.cuda.current_stream(lens.device) if stream is None else stream
+        flags = FR_CANONICAL if canonical else 0
+        if planes is not None:
+            arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+            _check(lib.hrx_lookup_compress_inputs_device_planes(self._need_device(chars, lens, theta, out, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(),
+                                                                arr, len(planes), B, M, int(b_begin), b_count, theta.data_ptr(), theta_stride, out.data_ptr(), flags,
+                                                                s.cuda_stream))
+            return out
+        _check(lib.hrx_lookup_compress_inputs_device(self._need_device(chars, lens, rec, theta, out), int(layout), chars.data_ptr(), stride, lens.data_ptr(), rec.data_ptr(),
+                                                     int(rec_pitch), B, M, int(b_begin), b_count, theta.data_ptr(), theta_stride, out.data_ptr(), flags, s.cuda_stream))
+        return out
+
+    def lookup_compress_inputs_host(self, chars, lens, rec, theta, layout=LAYOUT_STRING_MAJOR, b_begin=0, b_count=None, out=None, canonical=False,
+                                    chars_pm_stride=None, rec_pitch=0):
+        """hrx_lookup_compress_inputs_host: lookup_compress_inputs over numpy arrays in host memory, on a host-only or a device context — the definition of the
+        cells (csrc/hrx_compress.hpp) over host threads.  theta: uint64 limbs (b_count, 4) or (4,); returns uint64 [3 D][b_count][M][4]."""
+        lens = np.ascontiguousarray(lens, np.uint32)
+        B, M, D = len(lens), self.max_chars_size, self.num_defs
+        b_count = B - b_begin if b_count is None else int(b_count)
+        ch, rec, _, stride, rec_pitch, _ = _numpy_rows(chars, rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
+        theta = np.ascontiguousarray(theta, np.uint64)
+        theta_stride = _theta_stride(theta, b_count, np.uint64)
+        ncols = 3 * D
+        if out is None:
+            out = np.empty((ncols, b_count, M, 4), np.uint64)
+        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != ncols * b_count * M * 4:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of [%d][%d][%d][4] elements" % (ncols, b_count, M))
+        _check(lib.hrx_lookup_compress_inputs_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch), B, M,
+                                                   int(b_begin), b_count, theta.ctypes.data, theta_stride, out.ctypes.data, FR_CANONICAL if canonical else 0))
+        return out
+
+    def lookup_compress_table(self, theta, out=None, canonical=False, stream=None):
+        """hrx_lookup_compress_table_device: the rows of the fixed lookup tables folded with each challenge, in the index space of the counts: int64 CUDA tensor
+        [n_theta][lookup_words()][4] — cell w of a run is the compressed table row lookup_counts' word w counts (lookup_layout() slices a run; the start and end
+        runs hold equal cells; pad words are zero cells).  theta: int64 CUDA limbs (n_theta, 4) or (4,) (one run).  The context's first call also builds and
+        uploads the tables' tuples (not inside a graph capture)."""
+        W = self.lookup_words()
+        n_theta = 1 if theta.dim() == 1 else theta.shape[0]
+        _theta_stride(theta, n_theta, torch.int64)
+        if out is None:
+            out = torch.empty((n_theta, W, 4), dtype=torch.int64, device=theta.device)
+        elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != n_theta * W * 4:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous int64 tensor of [%d][%d][4] elements" % (n_theta, W))
+        s = torch.cuda.current_stream(theta.device) if stream is None else stream
+        _check(lib.hrx_lookup_compress_table_device(self._need_device(theta, out), theta.data_ptr(), 4, n_theta, out.data_ptr(), FR_CANONICAL if canonical else 0,
+                                                    s.cuda_stream))
+        return out
+
+    def lookup_compress_table_host(self, theta, out=None, canonical=False):
+        """hrx_lookup_compress_table_host: lookup_compress_table over numpy arrays — theta uint64 limbs (n_theta, 4) or (4,); uint64 [n_theta][lookup_words()][4]"""
+        W = self.lookup_words()
+        theta = np.ascontiguousarray(theta, np.uint64)
+        n_theta = 1 if theta.ndim == 1 else theta.shape[0]
+        _theta_stride(theta, n_theta, np.uint64)
+        if out is None:
+            out = np.empty((n_theta, W, 4), np.uint64)
+        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != n_theta * W * 4:
+            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of [%d][%d][4] elements" % (n_theta, W))
+        _check(lib.hrx_lookup_compress_table_host(self._need_ctx(), theta.ctypes.data, 4, n_theta, out.ctypes.data, FR_CANONICAL if canonical else 0))
+        return out
+
     def witness_batch(self, chars, lens, out=None, stream=None):
         """Device-resident batch: chars (B, stride) uint8 CUDA tensor (stride % 16 == 0), lens (B,) int32 CUDA tensor.
         Asynchronous on `stream` (default: torch's current stream).  Returns (records, masked, status) tensors whose
@@ -1520,6 +1615,16 @@ def permuted_lookup_columns(n_table_rows, counts, n_rows):
 FR_CANONICAL = 1                       # HRX_FR_CANONICAL
 FR_COLUMN_NAMES = lambda D: (["char_enable", "characters"] + [n % d for d in range(D) for n in ("states[%d]", "substr_ids[%d]", "start_enable[%d]", "end_enable[%d]")]
                              + ["masked_characters", "all_substr_ids"])
+
+
+FR_LOOKUP_COLUMN_NAMES = lambda D: [n % d for d in range(D) for n in ("trans[%d]", "start[%d]", "end[%d]")]      # hrx_lookup_compress_inputs_*
+
+
+def fr_mul(a, b):
+    """hrx_fr_mul: the Montgomery product a * b / 2^256 mod r of two elements given as 4 little-endian u64 limbs each; 4 limbs"""
+    x, y, out = (C.c_uint64 * 4)(*[int(v) for v in a]), (C.c_uint64 * 4)(*[int(v) for v in b]), (C.c_uint64 * 4)()
+    lib.hrx_fr_mul(x, y, out)
+    return [int(v) for v in out]
 
 
 def fr_from_u64(v, canonical=False):

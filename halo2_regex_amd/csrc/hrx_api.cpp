@@ -331,7 +331,7 @@ void hrx_ctx_destroy(hrx_ctx *c) {
     }
     c->mp_masked.release(); c->mp_ov.release();
     c->tp_records.release(); c->tp_masked.release();
-    c->spec_cimage.release(); c->d_cw.release(); c->verify_img.dev.release(); c->lookup_img.dev.release();
+    c->spec_cimage.release(); c->d_cw.release(); c->verify_img.dev.release(); c->lookup_img.dev.release(); c->compress_img.dev.release();
     for (auto &g : c->cw_groups) { g.d_cw.release(); g.status.release(); g.summary.release(); }
     c->spec_cls.release(); c->spec_ends.release(); c->spec_fail.release(); c->spec_init.release(); c->spec_vstatus.release(); c->spec_vinfo.release(); c->spec_work.release();
     if (c->d_group_counter) (void)hipFree(c->d_group_counter);

@@ -163,8 +163,9 @@ struct hrx_ctx {
     hipStream_t match_stream = nullptr;
     bool match_used = false;
     // VERIFY (hrx_verify_api.cpp): the check tables (hrx_verify.hpp build_verify_image); LOOKUP COUNTS (hrx_lookup_api.cpp): the image (hrx_lookup.hpp
-    // build_lookup_image).  Each built at the context's first call of its kind (ctx_image_host / ctx_image_device below)
-    CtxImage verify_img, lookup_img;
+    // build_lookup_image); LOOKUP COMPRESS (hrx_compress_api.cpp): the tables' tuples (hrx_compress.hpp build_compress_image).  Each built at the context's
+    // first call of its kind (ctx_image_host / ctx_image_device below)
+    CtxImage verify_img, lookup_img, compress_img;
     DevBuf d_cw;                    // CLASS-WIDE image of a config of 4 .. 8 defs (DefsSet::cw_image): the single-launch def-parallel path and the fused-wide match
 #ifdef HRX_STAMPS
     DevBuf stamps;                  // tools-only build: 8 u64 per walker pair of the position-major kernel (hrx_kernel_pm.hip)

@@ -8,6 +8,8 @@
 // Here v * R mod r is computed directly: q' = floor(v * K / 2^64) with K = floor(R * 2^64 / r) underestimates
 // q = floor(v * R / r) by at most 2, so v * R - q' * r needs at most two corrective subtractions.  Plain C++ (unsigned
 // __int128) so that hipcc compiles it for the kernel and g++/hipcc for the host-side known-answer tests.
+// Below F::from: arithmetic on elements as eight u32 limbs — fr_add, fr_mul (the Montgomery product), fr_reduce (any 256-bit value mod r), and fr_fold, the
+// fold of a lookup tuple with a challenge's powers (fr_powers) that LOOKUP COMPRESS is made of (hrx_compress.hpp).
 #pragma once
 #include <stdint.h>
 
@@ -95,6 +97,144 @@ HRX_HD void fr_from_u32(uint32_t v, uint32_t (&out)[8], bool canonical = false) 
             for (int i = 0; i < 9; ++i) t[i] = u[i];
     }
     for (int i = 0; i < 8; ++i) out[i] = t[i];
+}
+
+// ---- arithmetic on elements, 8 little-endian u32 limbs each (the device's form; the host runs the same code) -----------------------------------
+// The loops index register arrays: every index is a constant once they are unrolled.
+#if defined(__clang__)
+#define HRX_FR_UNROLL _Pragma("unroll")
+#else
+#define HRX_FR_UNROLL
+#endif
+constexpr uint32_t kFrInv32 = 0xefffffffu;          // -r^-1 mod 2^32
+constexpr uint32_t kFrR2_32[8] = {0xae216da7u, 0x1bb8e645u, 0xe35c59e3u, 0x53fe3ab1u, 0x53bb8085u, 0x8c49833du, 0x7f4e44a5u, 0x0216d0b1u};   // R^2 mod r
+constexpr uint32_t kFrFoldK = 0xa948e8c4u;          // floor(2^285 / r): the quotient estimate of fr_fold
+
+// t -= m when t >= m; m = r << shift
+template <int SHIFT>
+HRX_HD void fr_sub_if_ge(uint32_t (&t)[8]) {
+    uint32_t u[8], b = 0;
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) {
+        uint32_t m = kFrModulus32[i];
+        if constexpr (SHIFT != 0) m = m << SHIFT | (i ? kFrModulus32[i ? i - 1 : 0] >> (32 - SHIFT) : 0u);
+        const uint64_t x = (uint64_t)t[i] - m - b;
+        u[i] = (uint32_t)x;
+        b = (uint32_t)(x >> 32) & 1u;
+    }
+    if (!b) {
+HRX_FR_UNROLL
+        for (int i = 0; i < 8; ++i) t[i] = u[i];
+    }
+}
+
+// x mod r for any 256-bit x: 2^256 < 6 r and 4 r < 2^256, so x - [x >= 4r] 4r < 4r, then 2r and r are taken off where they fit
+HRX_HD void fr_reduce(uint32_t (&x)[8]) {
+    fr_sub_if_ge<2>(x);
+    fr_sub_if_ge<1>(x);
+    fr_sub_if_ge<0>(x);
+}
+
+// out = a + b mod r, a and b below r (the sum is below 2^255: no carry out of the eight limbs)
+HRX_HD void fr_add(const uint32_t (&a)[8], const uint32_t (&b)[8], uint32_t (&out)[8]) {
+    uint64_t c = 0;
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) {
+        c += (uint64_t)a[i] + b[i];
+        out[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    fr_sub_if_ge<0>(out);
+}
+
+// out = a * b / R mod r — the Montgomery product: of two Montgomery forms the Montgomery form of the product; of a plain integer and a Montgomery form the
+// plain product.  a, b below r.  Word-by-word (CIOS) over 32-bit limbs: per limb of b one row of a * b[i] and one of m * r that clears the lowest limb,
+// 128 v_mad_u64_u32 in all; the running value stays below 2 r < 2^255, so one subtraction finishes.
+HRX_HD void fr_mul(const uint32_t (&a)[8], const uint32_t (&b)[8], uint32_t (&out)[8]) {
+    uint32_t t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) {
+        uint64_t c = 0;
+HRX_FR_UNROLL
+        for (int j = 0; j < 8; ++j) {      // t += a * b[i]   (a[j] b[i] + t[j] + c <= 2^64 - 1)
+            c += (uint64_t)a[j] * b[i] + t[j];
+            t[j] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[8];
+        const uint32_t top = (uint32_t)(c >> 32);
+        t[8] = (uint32_t)c;
+        const uint32_t m = t[0] * kFrInv32;
+        c = ((uint64_t)m * kFrModulus32[0] + t[0]) >> 32;      // the lowest limb of t + m r is 0
+HRX_FR_UNROLL
+        for (int j = 1; j < 8; ++j) {      // t = (t + m r) / 2^32
+            c += (uint64_t)m * kFrModulus32[j] + t[j];
+            t[j - 1] = (uint32_t)c;
+            c >>= 32;
+        }
+        c += t[8];
+        t[7] = (uint32_t)c;
+        t[8] = top + (uint32_t)(c >> 32);
+    }
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) out[i] = t[i];      // (t[8] == 0: t < 2 r)
+    fr_sub_if_ge<0>(out);
+}
+
+// The fold of a lookup tuple with a challenge: out = a0 t3 + a1 t2 + a2 t1 + a3 one mod r for components a0 .. a3 below 2^16 and t3, t2, t1, one below r.
+// With t_k = theta^k R mod r and one = R (kFrR32) that is the Montgomery form of a0 theta^3 + a1 theta^2 + a2 theta + a3 — halo2's
+// acc = acc * theta + e_i from 0 over (a0, a1, a2, a3); with t_k = theta^k mod r and one = 1 the plain integer.  A tuple of three components is (0, e0, e1, e2).
+// Four small-scalar products, one sum S < 4 * 2^16 * r < 2^272 (nine limbs), one reduction: q' = floor(floor(S / 2^240) * K / 2^45) with
+// K = floor(2^285 / r).  S / r - floor(S / 2^240) K / 2^45 < 2^240 / r + 2^32 / 2^45 < 2^-12, so q' underestimates q = floor(S / r) by at most 1 and
+// S - q' r < 2 r < 2^255: the difference needs the low eight limbs only and at most ONE corrective subtraction.
+HRX_HD void fr_fold(uint32_t a0, uint32_t a1, uint32_t a2, uint32_t a3, const uint32_t (&t3)[8], const uint32_t (&t2)[8], const uint32_t (&t1)[8],
+                    const uint32_t (&one)[8], uint32_t (&out)[8]) {
+    uint32_t s[9];
+    uint64_t c = 0;
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) {          // each product below 2^48, the four and the carry below 2^51
+        c += (uint64_t)a0 * t3[i] + (uint64_t)a1 * t2[i] + (uint64_t)a2 * t1[i] + (uint64_t)a3 * one[i];
+        s[i] = (uint32_t)c;
+        c >>= 32;
+    }
+    s[8] = (uint32_t)c;
+    const uint32_t top = s[7] >> 16 | s[8] << 16;              // floor(S / 2^240) < 2^32
+    const uint32_t q = (uint32_t)(((uint64_t)top * kFrFoldK) >> 45);
+    uint64_t d = 0;
+    uint32_t borrow = 0;
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) {          // out = S - q r mod 2^256
+        d += (uint64_t)q * kFrModulus32[i];
+        const uint64_t x = (uint64_t)s[i] - (uint32_t)d - borrow;
+        out[i] = (uint32_t)x;
+        borrow = (uint32_t)(x >> 32) & 1u;
+        d >>= 32;
+    }
+    fr_sub_if_ge<0>(out);
+}
+
+// What a fold needs of one challenge: its powers.  theta: 8 limbs of any 256-bit value, taken mod r first; canonical: theta is the plain integer and so are
+// the powers and `one` (1), otherwise everything is in Montgomery form (one = R).  Two fr_mul (canonical: three).
+struct FrPowers {
+    uint32_t t1[8], t2[8], t3[8], one[8];
+};
+HRX_HD void fr_powers(const uint32_t (&theta)[8], bool canonical, FrPowers &p) {
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) p.t1[i] = theta[i];
+    fr_reduce(p.t1);
+    if (canonical) {
+        uint32_t m[8], r2[8];
+HRX_FR_UNROLL
+        for (int i = 0; i < 8; ++i) r2[i] = kFrR2_32[i];
+        fr_mul(p.t1, r2, m);               // theta R: a plain integer times it is the plain product
+        fr_mul(p.t1, m, p.t2);
+        fr_mul(p.t2, m, p.t3);
+    } else {
+        fr_mul(p.t1, p.t1, p.t2);
+        fr_mul(p.t2, p.t1, p.t3);
+    }
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) p.one[i] = canonical ? (i == 0 ? 1u : 0u) : kFrR32[i];
 }
 
 }  // namespace hrx

@@ -453,5 +453,10 @@ hipError_t launch_verify_chunked(const VerifyChunkArgs &ca, hipStream_t stream);
 // LOOKUP COUNTS (hrx_kernel_lookup.hip): the rule of hrx_lookup.hpp over the same row forms; a histogram per string with the bins in LDS
 struct LookupArgs;     // hrx_lookup.hpp
 hipError_t launch_lookup_counts(const LookupArgs &a, size_t lds_bytes, hipStream_t stream);
+// LOOKUP COMPRESS (hrx_kernel_compress.hip): the rule of hrx_compress.hpp — the lookup tuples of the rows / the rows of the tables folded with a challenge
+struct CompressArgs;   // hrx_compress.hpp
+struct CompressTableArgs;
+hipError_t launch_compress_inputs(const CompressArgs &a, hipStream_t stream);
+hipError_t launch_compress_table(const CompressTableArgs &a, hipStream_t stream);
 
 }  // namespace hrx

@@ -739,6 +739,49 @@ int hrx_lookup_counts_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_
 int hrx_ctx_lookup_group(hrx_ctx *ctx, size_t b_count, size_t *group, size_t *passes);
 
 /* ------------------------------------------------------------------ */
+/* LOOKUP COMPRESS — the lookup tuples folded with a challenge into field cells (what the counts above are indices into)                  */
+/* ------------------------------------------------------------------ */
+/* A lookup argument does not work on tuples but on the tuple folded with the challenge theta: for the input expressions [e0 .. ek-1] of meta.lookup halo2's
+ * commit_permuted computes acc = acc * theta + e_i from 0 — A = e0 theta^3 + e1 theta^2 + e2 theta + e3 for the transition lookup, e0 theta^2 + e1 theta + e2
+ * for the two endpoint lookups — and folds the table columns the same way into S.  These calls compute both sides in bn256::Fr, so that with the counts the
+ * first phase of either lookup argument is gathers only: A'[i] = S[a_idx[i]] with the indices of a sort-free permutation of the counts, m = the counts.
+ *
+ * INPUTS.  cells: [3 D][b_count][M][4] u64 in hrx_fr_columns_device's shape (hrx_lookup_num_columns(D) = 3 D columns), 16-byte aligned; column 3 d + k
+ * holds k = 0 the transition, 1 the start, 2 the end lookup of def d; the strings are [b_begin, b_begin + b_count).  The tuples are those of LOOKUP COUNTS,
+ * as integers, and nothing is left out: with n_b == M the transition and end cells of row M - 1 are computed from next = the dummy state like any other (the
+ * cell match_substrs never assigns).  Values are folded as they lie: a state, id or flag outside every table is folded as the integer the record holds, so
+ * a tampered row's cell is in no table row.  n_b > M: the string has no rows, every limb of every one of its cells is 0.
+ * theta: 4 u64 limbs per challenge, 8-byte aligned, in DEVICE memory for the device forms (a transcript running on the device can write it, and the call
+ * stays capturable); theta_stride in u64 words: 4 — theta[4 i] is the challenge of string b_begin + i; 0 — one for the whole call; anything else
+ * HRX_ERR_ARG.  The limbs are taken mod r first.  flags: 0 — theta and the cells are Montgomery limbs (x * 2^256 mod r, the in-memory form of Fr); or
+ * HRX_FR_CANONICAL — both are plain integers; other bits HRX_ERR_ARG.
+ * `layout`, chars / stride / lens, records (rec_pitch) and the record planes are those of hrx_lookup_counts_device*: whatever it refuses is refused, and a
+ * refused call writes nothing.  The device forms: one launch (per 32768 strings), asynchronous on `stream`; nothing allocated, no context scratch, no
+ * atomics, deterministic; no image of the tables is read, so they are capturable from the first call.  A host-only context: HRX_ERR_HIP. */
+size_t hrx_lookup_num_columns(size_t D);
+int hrx_lookup_compress_inputs_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                      const uint32_t *records, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
+                                      const uint64_t *theta, size_t theta_stride, uint64_t *cells, int flags, void *stream);
+int hrx_lookup_compress_inputs_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                             const uint32_t *const *record_planes, size_t n_planes, size_t B, size_t M, size_t b_begin, size_t b_count,
+                                             const uint64_t *theta, size_t theta_stride, uint64_t *cells, int flags, void *stream);
+/* The same over rows, theta and cells in HOST memory, on a host-only or a device context, over HRX_OPT_HOST_THREADS threads by ranges of strings.  The
+ * definition of the cells. */
+int hrx_lookup_compress_inputs_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens,
+                                    const uint32_t *records, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
+                                    const uint64_t *theta, size_t theta_stride, uint64_t *cells, int flags);
+/* TABLE.  cells: [n_theta][W][4] u64, 16-byte aligned, W = hrx_lookup_words_per_string(defs), in the index space of the counts: cell w of a run is the
+ * compressed table row that counts[w] counts.  trans[T_d]: the fold of (char, cur, next, substr_id) of transition row t; start[E_d] and end[E_d]: both the
+ * fold of (substr_id, start_state, end_state) of endpoint row e — the two lookups share the endpoint table's columns, the runs hold equal cells and the
+ * indices stay those of hrx_lookup_layout; the pad words are zero cells.  Run t is folded with theta[t * theta_stride] (theta, theta_stride and flags as
+ * above; n_theta at most 65535).  The rows are those RegexTableConfig::load assigns, never a walk's table; their flat tuple array is built — and for the
+ * device form uploaded — at the context's FIRST call of this kind: inside a stream capture before that HRX_ERR_STATE, afterwards one launch, capturable. */
+int hrx_lookup_compress_table_device(hrx_ctx *ctx, const uint64_t *theta, size_t theta_stride, size_t n_theta, uint64_t *cells, int flags, void *stream);
+int hrx_lookup_compress_table_host(hrx_ctx *ctx, const uint64_t *theta, size_t theta_stride, size_t n_theta, uint64_t *cells, int flags);
+/* The Montgomery product a * b / 2^256 mod r on the host (the kernels' arithmetic): Montgomery limbs of two elements below r in, Montgomery limbs out. */
+void hrx_fr_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */
 /* ------------------------------------------------------------------ */
 /* One circuit: EXACTLY the Vecs the three derive_* calls at the top of match_substrs return (src/lib.rs:316-318), out of the string's compact records, so that the body

@@ -1,0 +1,384 @@
+// test_compress_host.cpp — csrc/hrx_fr.h, csrc/hrx_compress.hpp and csrc/hrx_compress_host.cpp (the arithmetic, the rule and the host forms of LOOKUP COMPRESS,
+// include/hrx.h) as a program of their own, built with -fsanitize=address,undefined by tests/test_compress_cpu.py.  Every array is a heap block of exactly
+// its size, so one element too far is a sanitizer error.  The yardstick is written here and shares nothing with hrx_fr.h: a schoolbook product of 16-bit
+// digits and a binary long division by r.
+// Checked: fr_mul and fr_add against it on edge values and a seeded stream; fr_reduce on every multiple of r below 2^256 and its neighbours; the fold at its
+// extremes (every component 0xffff, theta = r - 1, the powers r - 1: the largest sum, where the quotient estimate is corrected) and on a seeded stream; the
+// per-string loop over hand-made rows in the string-major, pitched and position-major images, n = 0 .. M + 1, Montgomery and canonical; the table's tuples.
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <memory>
+#include <vector>
+
+#include "../../halo2_regex_amd/csrc/hrx_compress_host.cpp"
+
+using namespace hrx;
+
+static int failures = 0;
+#define EXPECT(c)                                                     \
+    do {                                                              \
+        if (!(c)) {                                                   \
+            std::printf("line %d: %s\n", __LINE__, #c);               \
+            ++failures;                                               \
+        }                                                             \
+    } while (0)
+
+// ---- the yardstick: unsigned integers as little-endian 16-bit digits --------------------------------------------------------------------------
+typedef std::vector<uint32_t> Big;       // digits below 2^16
+
+static Big big_of_limbs(const uint32_t *w, int n) {
+    Big b;
+    for (int i = 0; i < n; ++i) { b.push_back(w[i] & 0xffffu); b.push_back(w[i] >> 16); }
+    return b;
+}
+static void trim(Big &a) { while (!a.empty() && a.back() == 0) a.pop_back(); }
+static Big big_mul(const Big &a, const Big &b) {          // schoolbook
+    std::vector<uint64_t> acc(a.size() + b.size() + 1, 0);
+    for (size_t i = 0; i < a.size(); ++i)
+        for (size_t j = 0; j < b.size(); ++j) acc[i + j] += (uint64_t)a[i] * b[j];
+    Big out(acc.size(), 0);
+    uint64_t c = 0;
+    for (size_t i = 0; i < acc.size(); ++i) { c += acc[i]; out[i] = (uint32_t)(c & 0xffffu); c >>= 16; }
+    return out;
+}
+static Big big_add(const Big &a, const Big &b) {
+    Big out(std::max(a.size(), b.size()) + 1, 0);
+    uint32_t c = 0;
+    for (size_t i = 0; i < out.size(); ++i) {
+        c += (i < a.size() ? a[i] : 0u) + (i < b.size() ? b[i] : 0u);
+        out[i] = c & 0xffffu;
+        c >>= 16;
+    }
+    return out;
+}
+static int big_cmp(Big a, Big b) {
+    trim(a); trim(b);
+    if (a.size() != b.size()) return a.size() < b.size() ? -1 : 1;
+    for (size_t i = a.size(); i-- > 0;)
+        if (a[i] != b[i]) return a[i] < b[i] ? -1 : 1;
+    return 0;
+}
+static Big big_sub(const Big &a, const Big &b) {          // a >= b
+    Big out(a.size(), 0);
+    int32_t borrow = 0;
+    for (size_t i = 0; i < a.size(); ++i) {
+        int32_t x = (int32_t)a[i] - (int32_t)(i < b.size() ? b[i] : 0u) - borrow;
+        borrow = x < 0;
+        out[i] = (uint32_t)(x + (borrow << 16));
+    }
+    return out;
+}
+static Big big_mod(const Big &a, const Big &m) {          // binary long division: bit by bit from the top
+    Big d = m;
+    trim(d);
+    const size_t k = d.size();
+    Big rem(k + 1, 0);                                    // the remainder so far, in place: shifted, compared, reduced
+    for (size_t i = a.size() * 16; i-- > 0;) {
+        uint32_t c = (a[i / 16] >> (i % 16)) & 1u;
+        for (size_t j = 0; j <= k; ++j) { const uint32_t x = rem[j] << 1 | c; rem[j] = x & 0xffffu; c = x >> 16; }
+        bool ge = rem[k] != 0;
+        if (!ge) {
+            ge = true;
+            for (size_t j = k; j-- > 0;)
+                if (rem[j] != d[j]) { ge = rem[j] > d[j]; break; }
+        }
+        if (ge) {
+            int32_t borrow = 0;
+            for (size_t j = 0; j <= k; ++j) {
+                const int32_t x = (int32_t)rem[j] - (int32_t)(j < k ? d[j] : 0u) - borrow;
+                borrow = x < 0;
+                rem[j] = (uint32_t)(x + (borrow << 16));
+            }
+        }
+    }
+    rem.resize(k);
+    return rem;
+}
+static void limbs_of_big(Big a, uint32_t (&w)[8]) {
+    a.resize(16, 0);
+    for (int i = 0; i < 8; ++i) w[i] = a[2 * i] | a[2 * i + 1] << 16;
+}
+static Big modulus() { return big_of_limbs(kFrModulus32, 8); }
+static Big two_pow_256() { Big b(17, 0); b[16] = 1; return b; }
+
+// a * b / 2^256 mod r by the yardstick: the x below r with x * 2^256 = a * b (mod r) — found as a * b * Rinv with Rinv from 2^256 by Fermat
+static Big big_pow_mod(Big base, Big e, const Big &m) {
+    Big acc{1};
+    trim(e);
+    for (size_t i = 0; i < e.size() * 16; ++i) {
+        if ((e[i / 16] >> (i % 16)) & 1u) acc = big_mod(big_mul(acc, base), m);
+        base = big_mod(big_mul(base, base), m);
+    }
+    return acc;
+}
+static Big r_inverse() {
+    static Big inv;
+    if (inv.empty()) inv = big_pow_mod(big_mod(two_pow_256(), modulus()), big_sub(modulus(), Big{2}), modulus());
+    return inv;
+}
+
+static uint64_t rng_state = 0x243f6a8885a308d3ull;
+static uint32_t rnd() {                                  // splitmix64
+    uint64_t z = (rng_state += 0x9e3779b97f4a7c15ull);
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+    return (uint32_t)((z ^ (z >> 31)) >> 16);
+}
+static void rnd_below_r(uint32_t (&w)[8]) {
+    for (int i = 0; i < 8; ++i) w[i] = rnd();
+    limbs_of_big(big_mod(big_of_limbs(w, 8), modulus()), w);
+}
+static bool same(const uint32_t (&a)[8], const uint32_t (&b)[8]) { return memcmp(a, b, 32) == 0; }
+
+static void check_mul_add() {
+    const Big m = modulus();
+    std::vector<std::vector<uint32_t>> vals;
+    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    vals.emplace_back(w, w + 8);                           // 0
+    w[0] = 1; vals.emplace_back(w, w + 8);                 // 1
+    limbs_of_big(big_sub(m, Big{1}), w); vals.emplace_back(w, w + 8);      // r - 1
+    vals.emplace_back(kFrR32, kFrR32 + 8);                 // R
+    vals.emplace_back(kFrR2_32, kFrR2_32 + 8);             // R^2
+    for (int i = 0; i < 40; ++i) { rnd_below_r(w); vals.emplace_back(w, w + 8); }
+    EXPECT(big_cmp(big_mod(big_mul(big_mod(two_pow_256(), m), big_mod(two_pow_256(), m)), m), big_of_limbs(kFrR2_32, 8)) == 0);
+    EXPECT(big_cmp(big_mod(two_pow_256(), m), big_of_limbs(kFrR32, 8)) == 0);
+    for (size_t i = 0; i < vals.size(); ++i)
+        for (size_t j = 0; j < (i < 5 ? vals.size() : 8); ++j) {
+            uint32_t a[8], b[8], got[8], want[8];
+            memcpy(a, vals[i].data(), 32); memcpy(b, vals[j].data(), 32);
+            fr_mul(a, b, got);
+            limbs_of_big(big_mod(big_mul(big_mul(big_of_limbs(a, 8), big_of_limbs(b, 8)), r_inverse()), m), want);
+            EXPECT(same(got, want));
+            fr_add(a, b, got);
+            limbs_of_big(big_mod(big_add(big_of_limbs(a, 8), big_of_limbs(b, 8)), m), want);
+            EXPECT(same(got, want));
+        }
+}
+
+static void check_reduce() {
+    const Big m = modulus();
+    Big k{0};
+    for (int q = 0; q < 6; ++q) {                          // q r - 1, q r, q r + 1 for every q r below 2^256
+        for (int delta = -1; delta <= 1; ++delta) {
+            if (q == 0 && delta < 0) continue;
+            Big x = delta < 0 ? big_sub(k, Big{1}) : delta > 0 ? big_add(k, Big{1}) : k;
+            if (big_cmp(x, two_pow_256()) >= 0) continue;
+            uint32_t w[8], want[8];
+            limbs_of_big(x, w);
+            limbs_of_big(big_mod(x, m), want);
+            fr_reduce(w);
+            EXPECT(same(w, want));
+        }
+        k = big_add(k, m);
+    }
+    uint32_t w[8], want[8];
+    for (int i = 0; i < 8; ++i) w[i] = 0xffffffffu;        // 2^256 - 1
+    limbs_of_big(big_mod(big_of_limbs(w, 8), m), want);
+    fr_reduce(w);
+    EXPECT(same(w, want));
+    for (int i = 0; i < 200; ++i) {
+        for (int j = 0; j < 8; ++j) w[j] = rnd();
+        limbs_of_big(big_mod(big_of_limbs(w, 8), m), want);
+        fr_reduce(w);
+        EXPECT(same(w, want));
+    }
+}
+
+static void fold_by_the_yardstick(const uint32_t (&e)[4], const FrPowers &p, uint32_t (&want)[8]) {
+    Big s = big_mul(Big{e[0]}, big_of_limbs(p.t3, 8));
+    s = big_add(s, big_mul(Big{e[1]}, big_of_limbs(p.t2, 8)));
+    s = big_add(s, big_mul(Big{e[2]}, big_of_limbs(p.t1, 8)));
+    s = big_add(s, big_mul(Big{e[3]}, big_of_limbs(p.one, 8)));
+    limbs_of_big(big_mod(s, modulus()), want);
+}
+
+static void check_fold() {
+    const Big m = modulus();
+    FrPowers p;
+    uint32_t top[8], got[8], want[8];
+    limbs_of_big(big_sub(m, Big{1}), top);
+    // the largest sum there is: every component 0xffff, every power and `one` r - 1
+    for (int i = 0; i < 8; ++i) p.t1[i] = p.t2[i] = p.t3[i] = p.one[i] = top[i];
+    const uint32_t ffff[4] = {0xffffu, 0xffffu, 0xffffu, 0xffffu};
+    fr_fold(ffff[0], ffff[1], ffff[2], ffff[3], p.t3, p.t2, p.t1, p.one, got);
+    fold_by_the_yardstick(ffff, p, want);
+    EXPECT(same(got, want));
+    // theta = r - 1 in both forms, every component 0xffff and the single-component corners
+    for (int canonical = 0; canonical < 2; ++canonical) {
+        fr_powers(top, canonical != 0, p);
+        // (r - 1)^2 = 1, (r - 1)^3 = r - 1 mod r; in Montgomery form theta = (r - 1) / R, whose powers the yardstick gives
+        uint32_t t2[8], t3[8];
+        if (canonical) {
+            limbs_of_big(big_mod(big_mul(big_of_limbs(top, 8), big_of_limbs(top, 8)), m), t2);
+            limbs_of_big(big_mod(big_mul(big_of_limbs(t2, 8), big_of_limbs(top, 8)), m), t3);
+        } else {
+            limbs_of_big(big_mod(big_mul(big_mul(big_of_limbs(top, 8), big_of_limbs(top, 8)), r_inverse()), m), t2);
+            limbs_of_big(big_mod(big_mul(big_mul(big_of_limbs(t2, 8), big_of_limbs(top, 8)), r_inverse()), m), t3);
+        }
+        EXPECT(same(p.t1, top) && same(p.t2, t2) && same(p.t3, t3));
+        for (uint32_t mask = 0; mask < 16; ++mask) {
+            uint32_t e[4];
+            for (int i = 0; i < 4; ++i) e[i] = (mask >> i) & 1u ? 0xffffu : 0u;
+            fr_fold(e[0], e[1], e[2], e[3], p.t3, p.t2, p.t1, p.one, got);
+            fold_by_the_yardstick(e, p, want);
+            EXPECT(same(got, want));
+        }
+    }
+    for (int i = 0; i < 300; ++i) {
+        uint32_t th[8], e[4];
+        for (int j = 0; j < 8; ++j) th[j] = rnd();         // any 256-bit value: taken mod r first
+        fr_powers(th, (i & 1) != 0, p);
+        uint32_t t1[8];
+        limbs_of_big(big_mod(big_of_limbs(th, 8), m), t1);
+        EXPECT(same(p.t1, t1));
+        for (int j = 0; j < 4; ++j) e[j] = rnd() & 0xffffu;
+        fr_fold(e[0], e[1], e[2], e[3], p.t3, p.t2, p.t1, p.one, got);
+        fold_by_the_yardstick(e, p, want);
+        EXPECT(same(got, want));
+    }
+}
+
+// ---- the per-string loop over hand-made rows ----------------------------------------------------------------------------------------------------
+template <class T>
+static std::unique_ptr<T[]> exact(const std::vector<T> &v) {      // a heap block of exactly v.size() elements
+    std::unique_ptr<T[]> p(new T[v.size()]);
+    std::copy(v.begin(), v.end(), p.get());
+    return p;
+}
+
+static void check_rows(uint32_t M) {
+    const uint32_t D = 2, B = M + 2;                       // string b has n = b characters: 0 .. M + 1
+    const uint32_t dummy[2] = {7, 300};
+    std::vector<uint8_t> chars((size_t)B * 16 * ((M + 16) / 16), 0);
+    const size_t stride = chars.size() / B;
+    std::vector<uint32_t> lens(B), rec((size_t)B * M * D);
+    for (uint32_t b = 0; b < B; ++b) {
+        lens[b] = b;
+        for (uint32_t r = 0; r < M; ++r) {
+            chars[b * stride + r] = (uint8_t)rnd();
+            for (uint32_t d = 0; d < D; ++d) rec[((size_t)b * M + r) * D + d] = rnd() & ((r + b) % 5 == 0 ? 0xffffffffu : 0x0303ffffu);     // some out of every range
+        }
+    }
+    std::vector<uint64_t> theta((size_t)B * 4);
+    for (uint64_t &t : theta) t = (uint64_t)rnd() << 32 | rnd();
+    for (int canonical = 0; canonical < 2; ++canonical) {
+        // the yardstick: tuples as lib.rs:218-283 writes them, folded digit by digit
+        std::vector<uint64_t> want((size_t)3 * D * B * M * 4, 0);
+        for (uint32_t b = 0; b < B; ++b) {
+            const uint32_t n = lens[b];
+            if (n > M) continue;
+            uint32_t th[8];
+            compress_theta_limbs(&theta[4 * b], th);
+            FrPowers p;
+            fr_powers(th, canonical != 0, p);
+            for (uint32_t d = 0; d < D; ++d)
+                for (uint32_t r = 0; r < M; ++r) {
+                    const uint32_t x = rec[((size_t)b * M + r) * D + d], en = r < n, dm = dummy[d];
+                    const uint32_t cur = x & 0xffffu, sid = (x >> 16) & 0xffu, se = (x >> 24) & 1u, ee = (x >> 25) & 1u;
+                    const uint32_t nxt = r + 1 < M ? rec[((size_t)b * M + r + 1) * D + d] & 0xffffu : dm;
+                    const uint32_t c = en ? chars[b * stride + r] : 0u;
+                    const uint32_t tup[3][4] = {{en * c, en * cur + (1 - en) * dm, en * nxt + (1 - en) * dm, en * sid},
+                                                {0, se * sid, se * cur + (1 - se) * dm, dm},
+                                                {0, ee * sid, dm, ee * nxt + (1 - ee) * dm}};
+                    for (uint32_t k = 0; k < 3; ++k) {
+                        uint32_t w[8];
+                        fold_by_the_yardstick(tup[k], p, w);
+                        compress_put_cell(&want[(((size_t)(3 * d + k) * B + b) * M + r) * 4], w);
+                    }
+                }
+        }
+        // string-major tight and pitched, position-major with either input layout: exact heap blocks
+        const uint32_t pitch = M + 3, q4 = (M + 3) / 4;
+        std::vector<uint32_t> rec_p((size_t)B * pitch * D, 0xffffffffu), rec_pm((size_t)q4 * D * B * 4, 0);
+        std::vector<uint8_t> chars_pm(chars.size(), 0);
+        for (uint32_t b = 0; b < B; ++b) {
+            for (uint32_t r = 0; r < M; ++r)
+                for (uint32_t d = 0; d < D; ++d) {
+                    rec_p[((size_t)b * pitch + r) * D + d] = rec[((size_t)b * M + r) * D + d];
+                    rec_pm[(((size_t)(r / 4) * D + d) * B + b) * 4 + r % 4] = rec[((size_t)b * M + r) * D + d];
+                }
+            for (size_t i = 0; i < stride; ++i) chars_pm[((i / 16) * B + b) * 16 + i % 16] = chars[b * stride + i];
+        }
+        auto h_chars = exact(chars), h_chars_pm = exact(chars_pm);
+        auto h_lens = exact(lens);
+        auto h_rec = exact(rec), h_rec_p = exact(rec_p), h_rec_pm = exact(rec_pm);
+        auto h_theta = exact(theta);
+        struct Form { int layout; const uint8_t *chars; const uint32_t *rec; uint64_t pitch; } forms[4] = {
+            {HRX_LAYOUT_STRING_MAJOR, h_chars.get(), h_rec.get(), M}, {HRX_LAYOUT_STRING_MAJOR, h_chars.get(), h_rec_p.get(), pitch},
+            {HRX_LAYOUT_POSITION_MAJOR, h_chars.get(), h_rec_pm.get(), M},
+            {HRX_LAYOUT_POSITION_MAJOR | HRX_LAYOUT_INPUT_POSITION_MAJOR, h_chars_pm.get(), h_rec_pm.get(), M}};
+        for (const Form &f : forms)
+            for (uint32_t b_begin : {0u, 1u}) {
+                const uint32_t b_count = B - b_begin - (b_begin ? 1u : 0u);
+                std::unique_ptr<uint64_t[]> cells(new uint64_t[(size_t)3 * D * b_count * M * 4]);
+                CompressArgs a{};
+                a.chars = f.chars; a.stride = stride; a.lens = h_lens.get(); a.records = f.rec; a.B = B; a.M = M; a.D = D; a.layout = (uint32_t)f.layout;
+                a.rec_pitch = f.pitch; a.msk_pitch = M; a.n_stripes = 1;
+                a.b_begin = b_begin; a.b_count = b_count; a.theta = h_theta.get() + 4 * b_begin; a.theta_stride = 4; a.canonical = (uint32_t)canonical;
+                a.cells = cells.get(); a.col_cells = (uint64_t)b_count * M;
+                a.dummy[0] = (uint16_t)dummy[0]; a.dummy[1] = (uint16_t)dummy[1];
+                compress_inputs_host(a, 3);
+                bool all = true;
+                for (uint32_t col = 0; col < 3 * D; ++col)
+                    for (uint32_t i = 0; i < b_count; ++i)
+                        all = all && memcmp(&cells[((size_t)col * b_count + i) * M * 4], &want[((size_t)col * B + b_begin + i) * M * 4], (size_t)M * 32) == 0;
+                EXPECT(all);
+            }
+    }
+}
+
+static void check_table() {
+    const uint64_t tr[] = {0, 5, 5, 0, 97, 0, 1, 0, 98, 1, 2, 3, 255, 4, 65535, 255};
+    const uint64_t ep[] = {0, 5, 5, 3, 1, 5, 3, 5, 2};
+    VerifyDefRows rows[2] = {{tr, 4, ep, 3, 0, 2}, {tr, 3, ep, 2, 0, 2}};
+    std::vector<uint32_t> img;
+    EXPECT(build_compress_image(rows, 2, img));
+    const uint32_t W = (uint32_t)(img.size() / 4);
+    EXPECT(W == 20 && img.size() == 80);                   // 4 + 3 + 3 + 3 + 2 + 2 = 17 tuples, rounded up
+    const uint32_t first_ep[4] = {0, 0, 5, 5}, second_def[4] = {0, 5, 5, 0};
+    EXPECT(memcmp(&img[16], first_ep, 16) == 0 && memcmp(&img[28], first_ep, 16) == 0 && memcmp(&img[40], second_def, 16) == 0);
+    const uint64_t big[] = {0, 65536, 65536, 0};
+    VerifyDefRows bad{big, 1, ep, 1, 0, 0};
+    std::vector<uint32_t> none;
+    EXPECT(!build_compress_image(&bad, 1, none) && !build_compress_image(rows, 0, none));
+    auto h_img = exact(img);
+    std::vector<uint64_t> theta = {3, 0, 0, 0, ~0ull, ~0ull, ~0ull, ~0ull, 0, 0, 0, 0};
+    auto h_theta = exact(theta);
+    for (int canonical = 0; canonical < 2; ++canonical) {
+        std::unique_ptr<uint64_t[]> cells(new uint64_t[(size_t)3 * W * 4]);
+        CompressTableArgs a{h_img.get(), W, h_theta.get(), 4, 3, (uint32_t)canonical, cells.get()};
+        compress_table_host(a, 2);
+        for (uint32_t t = 0; t < 3; ++t) {
+            uint32_t th[8];
+            compress_theta_limbs(&theta[4 * t], th);
+            FrPowers p;
+            fr_powers(th, canonical != 0, p);
+            for (uint32_t w = 0; w < W; ++w) {
+                uint32_t e[4] = {img[4 * w], img[4 * w + 1], img[4 * w + 2], img[4 * w + 3]}, want[8];
+                uint64_t cell[4];
+                fold_by_the_yardstick(e, p, want);
+                compress_put_cell(cell, want);
+                EXPECT(memcmp(cell, &cells[((size_t)t * W + w) * 4], 32) == 0);
+                if (w >= 17) EXPECT((cell[0] | cell[1] | cell[2] | cell[3]) == 0);
+            }
+        }
+        if (canonical) {                                   // theta = 3: the second transition row (97, 0, 1, 0) is 97 * 27 + 0 + 3 + 0
+            EXPECT(cells[4] == 97u * 27u + 3u && cells[5] == 0 && cells[6] == 0 && cells[7] == 0);
+        }
+    }
+}
+
+int main() {
+    check_mul_add();
+    check_reduce();
+    check_fold();
+    for (uint32_t M : {1u, 4u, 5u, 9u, 33u}) check_rows(M);
+    check_table();
+    if (failures) {
+        std::printf("compress host: %d failures\n", failures);
+        return 1;
+    }
+    std::printf("compress host: ok\n");
+    return 0;
+}
