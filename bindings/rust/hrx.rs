@@ -264,6 +264,17 @@ extern "C" {
                                             stream: *mut c_void) -> c_int;
     pub fn hrx_lookup_compress_table_host(ctx: *mut hrx_ctx, theta: *const u64, theta_stride: usize, n_theta: usize, cells: *mut u64, flags: c_int) -> c_int;
     pub fn hrx_fr_mul(a: *const u64, b: *const u64, out: *mut u64);
+    /// LOOKUP PERMUTE: the permuted columns A', S' of the lookup argument out of the counts, no sort: index columns [3 D][b_count][pitch] u32 into a
+    /// string's run and / or the cells [3 D][b_count][pitch][4] u64 gathered from the compressed table (table_stride 0: one run, 4 W: one per string);
+    /// overflow: bit 3 d + k where a lookup's counts exceed n_rows
+    pub fn hrx_lookup_permute_workspace_bytes(defs: *const hrx_defs, b_count: usize, n_rows: usize) -> usize;
+    pub fn hrx_lookup_permute_device(ctx: *mut hrx_ctx, counts: *const u32, b_count: usize, n_rows: usize, pitch: usize, a_idx: *mut u32, s_idx: *mut u32,
+                                     table_cells: *const u64, table_stride: usize, a_cells: *mut u64, s_cells: *mut u64, overflow: *mut u32,
+                                     workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_permute_host(ctx: *mut hrx_ctx, counts: *const u32, b_count: usize, n_rows: usize, pitch: usize, a_idx: *mut u32, s_idx: *mut u32,
+                                   table_cells: *const u64, table_stride: usize, a_cells: *mut u64, s_cells: *mut u64, overflow: *mut u32) -> c_int;
+    pub fn hrx_ctx_lookup_permute_plan(ctx: *mut hrx_ctx, b_count: usize, n_rows: usize, tile_rows: *mut usize, chunk_rows: *mut usize,
+                                       group_rows: *mut usize, groups: *mut usize) -> c_int;
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

@@ -161,6 +161,10 @@ def _load():
         "hrx_lookup_compress_table_device": (i, [vp, vp, sz, sz, vp, i, vp]),
         "hrx_lookup_compress_table_host": (i, [vp, vp, sz, sz, vp, i]),
         "hrx_fr_mul": (None, [_u64p, _u64p, _u64p]),
+        "hrx_lookup_permute_workspace_bytes": (sz, [vp, sz, sz]),
+        "hrx_lookup_permute_device": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
+        "hrx_lookup_permute_host": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]),
+        "hrx_ctx_lookup_permute_plan": (i, [vp, sz, sz] + [C.POINTER(sz)] * 4),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -1535,6 +1539,111 @@ class RegexVerifyConfig:
             raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of [%d][%d][4] elements" % (n_theta, W))
         _check(lib.hrx_lookup_compress_table_host(self._need_ctx(), theta.ctypes.data, 4, n_theta, out.ctypes.data, FR_CANONICAL if canonical else 0))
         return out
+
+    def lookup_permute_workspace_bytes(self, b_count, n_rows):
+        """hrx_lookup_permute_workspace_bytes: the device workspace of a lookup_permute call (0 unless a table has more rows than the kernel keeps in LDS)"""
+        return int(lib.hrx_lookup_permute_workspace_bytes(self._defs.h, int(b_count), int(n_rows)))
+
+    def lookup_permute_plan(self, b_count, n_rows):
+        """hrx_ctx_lookup_permute_plan: how a lookup_permute call cuts its work — a dict of tile_rows (positions of one expansion step), chunk_rows (table rows
+        held in LDS at once), group_rows (positions per workgroup) and groups (workgroups per (string, lookup))"""
+        v = [C.c_size_t() for _ in range(4)]
+        _check(lib.hrx_ctx_lookup_permute_plan(self._need_ctx(), int(b_count), int(n_rows), *[C.byref(x) for x in v]))
+        return dict(zip(("tile_rows", "chunk_rows", "group_rows", "groups"), (int(x.value) for x in v)))
+
+    def lookup_permute(self, counts, n_rows, table=None, pitch=0, out=("idx", "cells"), overflow=True, workspace=None, stream=None):
+        """hrx_lookup_permute_device: the permuted columns A', S' of halo2's lookup argument out of lookup_counts' counts, no sort (include/hrx.h LOOKUP
+        PERMUTE).  counts: (b_count, lookup_words()) int32 CUDA tensor.  Returns a dict: "a_idx", "s_idx" — int32 [3 D][b_count][pitch] word indices into a
+        string's run (the index space of the counts and of lookup_compress_table) — where "idx" is in `out`; "a_cells", "s_cells" — int64
+        [3 D][b_count][pitch][4], the table cells at those indices — where `table` is given and "cells" is in `out`; "overflow" — int32 (b_count,), bit
+        3 d + k where that lookup's counts exceed n_rows (its indices are 0xffffffff, its cells 0) — unless overflow is False.  table: lookup_compress_table's
+        int64 tensor, (W, 4) — one run for the call — or (b_count, W, 4).  pitch: a multiple of 4, at least n_rows (0: n_rows rounded up); entries
+        [n_rows, pitch) are never written.  `out` may also be a dict of the caller's contiguous tensors under those names (and "overflow"), written in place.
+        workspace: an int8 CUDA tensor of lookup_permute_workspace_bytes() bytes (allocated where needed and not given).  One launch (two with overflow),
+        asynchronous on `stream` (default: torch's current stream), capturable from the first call."""
+        assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous()
+        W, ncols = self.lookup_words(), 3 * self.num_defs
+        b_count = counts.numel() // W if W else 0
+        if counts.numel() != b_count * W:
+            raise HrxError(HRX_ERR_ARG, "counts: a contiguous int32 tensor of [b_count][%d] elements" % W)
+        n_rows, pitch = int(n_rows), int(pitch)
+        p = pitch if pitch else (n_rows + 3) & ~3
+        given = out if isinstance(out, dict) else {}
+        want_idx = "a_idx" in given if given else "idx" in out
+        want_cells = "a_cells" in given if given else (table is not None and "cells" in out)
+        res = {}
+
+        def buf(name, shape, dtype):
+            t = given.get(name)
+            if t is None:
+                t = torch.empty(shape, dtype=dtype, device=counts.device)
+            elif t.dtype != dtype or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
+                raise HrxError(HRX_ERR_ARG, "%s: a contiguous tensor of %s elements" % (name, "x".join(str(x) for x in shape)))
+            res[name] = t
+            return t
+
+        a_idx = s_idx = a_cells = s_cells = ov = None
+        if want_idx:
+            a_idx, s_idx = buf("a_idx", (ncols, b_count, p), torch.int32), buf("s_idx", (ncols, b_count, p), torch.int32)
+        table_stride = 0
+        if want_cells:
+            if table is None or table.dtype != torch.int64 or not table.is_contiguous() or tuple(table.shape) not in ((W, 4), (b_count, W, 4)):
+                raise HrxError(HRX_ERR_ARG, "table: a contiguous int64 tensor of [%d][4] or [%d][%d][4] limbs" % (W, b_count, W))
+            table_stride = 4 * W if table.dim() == 3 else 0
+            a_cells, s_cells = buf("a_cells", (ncols, b_count, p, 4), torch.int64), buf("s_cells", (ncols, b_count, p, 4), torch.int64)
+        if overflow or "overflow" in given:
+            ov = buf("overflow", (b_count,), torch.int32)
+        need = self.lookup_permute_workspace_bytes(b_count, n_rows)
+        if workspace is None and need:
+            workspace = torch.empty(need, dtype=torch.int8, device=counts.device)
+        s = torch.cuda.current_stream(counts.device) if stream is None else stream
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        _check(lib.hrx_lookup_permute_device(self._need_device(counts, a_idx, s_idx, table if want_cells else None, a_cells, s_cells, ov, workspace), counts.data_ptr(),
+                                             b_count, n_rows, pitch, ptr(a_idx), ptr(s_idx), ptr(table) if want_cells else None, table_stride, ptr(a_cells),
+                                             ptr(s_cells), ptr(ov), ptr(workspace), workspace.numel() if workspace is not None else 0, s.cuda_stream))
+        return res
+
+    def lookup_permute_host(self, counts, n_rows, table=None, pitch=0, out=("idx", "cells"), overflow=True):
+        """hrx_lookup_permute_host: lookup_permute over numpy arrays in host memory, on a host-only or a device context — the definition of the columns
+        (csrc/hrx_permute.hpp) over host threads.  counts uint32 (b_count, lookup_words()); table uint64 (W, 4) or (b_count, W, 4); the dict's arrays are
+        uint32 / uint64.  Entries [n_rows, pitch) are never written (arrays allocated here hold zeros there)."""
+        counts = np.ascontiguousarray(counts, np.uint32)
+        W, ncols = self.lookup_words(), 3 * self.num_defs
+        b_count = counts.size // W if W else 0
+        if counts.size != b_count * W:
+            raise HrxError(HRX_ERR_ARG, "counts: a contiguous uint32 array of [b_count][%d] elements" % W)
+        n_rows, pitch = int(n_rows), int(pitch)
+        p = pitch if pitch else (n_rows + 3) & ~3
+        given = out if isinstance(out, dict) else {}
+        want_idx = "a_idx" in given if given else "idx" in out
+        want_cells = "a_cells" in given if given else (table is not None and "cells" in out)
+        res = {}
+
+        def buf(name, shape, dtype):
+            t = given.get(name)
+            if t is None:
+                t = np.zeros(shape, dtype)
+            elif t.dtype != dtype or not t.flags.c_contiguous or t.size != int(np.prod(shape)):
+                raise HrxError(HRX_ERR_ARG, "%s: a contiguous array of %s elements" % (name, "x".join(str(x) for x in shape)))
+            res[name] = t
+            return t
+
+        a_idx = s_idx = a_cells = s_cells = ov = None
+        if want_idx:
+            a_idx, s_idx = buf("a_idx", (ncols, b_count, p), np.uint32), buf("s_idx", (ncols, b_count, p), np.uint32)
+        table_stride = 0
+        if want_cells:
+            table = None if table is None else np.ascontiguousarray(table, np.uint64)
+            if table is None or tuple(table.shape) not in ((W, 4), (b_count, W, 4)):
+                raise HrxError(HRX_ERR_ARG, "table: uint64 limbs of shape [%d][4] or [%d][%d][4]" % (W, b_count, W))
+            table_stride = 4 * W if table.ndim == 3 else 0
+            a_cells, s_cells = buf("a_cells", (ncols, b_count, p, 4), np.uint64), buf("s_cells", (ncols, b_count, p, 4), np.uint64)
+        if overflow or "overflow" in given:
+            ov = buf("overflow", (b_count,), np.uint32)
+        ptr = lambda t: t.ctypes.data if t is not None else None
+        _check(lib.hrx_lookup_permute_host(self._need_ctx(), counts.ctypes.data, b_count, n_rows, pitch, ptr(a_idx), ptr(s_idx), ptr(table) if want_cells else None,
+                                           table_stride, ptr(a_cells), ptr(s_cells), ptr(ov)))
+        return res
 
     def witness_batch(self, chars, lens, out=None, stream=None):
         """Device-resident batch: chars (B, stride) uint8 CUDA tensor (stride % 16 == 0), lens (B,) int32 CUDA tensor.

@@ -458,5 +458,9 @@ struct CompressArgs;   // hrx_compress.hpp
 struct CompressTableArgs;
 hipError_t launch_compress_inputs(const CompressArgs &a, hipStream_t stream);
 hipError_t launch_compress_table(const CompressTableArgs &a, hipStream_t stream);
+// LOOKUP PERMUTE (hrx_kernel_permute.hip): the rule of hrx_permute.hpp — the permuted columns of the lookup argument out of the counts; the overflow
+// words' launch (where asked for), then the columns' launch
+struct PermuteArgs;    // hrx_permute.hpp
+hipError_t launch_lookup_permute(const PermuteArgs &a, hipStream_t stream);
 
 }  // namespace hrx

@@ -782,6 +782,55 @@ int hrx_lookup_compress_table_host(hrx_ctx *ctx, const uint64_t *theta, size_t t
 void hrx_fr_mul(const uint64_t *a, const uint64_t *b, uint64_t *out);
 
 /* ------------------------------------------------------------------ */
+/* LOOKUP PERMUTE — the permuted columns A', S' of halo2's lookup argument out of the counts, without a sort                                */
+/* ------------------------------------------------------------------ */
+/* halo2's prover (lookup::prover::commit_permuted) commits for every lookup to a permutation A' of the compressed inputs and a permutation S' of the
+ * compressed table with A'[0] = S'[0] and, for every row i, A'[i] = S'[i] or A'[i] = A'[i - 1].  Any such pair is a valid witness; these calls build one
+ * from the counts alone, for every lookup of every string of a window, as indices and — optionally — as cells gathered from the compressed table.
+ * The rule, for one lookup with a table of T rows (T_d or E_d of hrx_lookup_layout), its counts m[0 .. T) in the string's run and n_rows usable rows:
+ *   sum = the sum of m[t], in 64 bits; sum > n_rows: the lookup OVERFLOWS (below).  Otherwise m'[0] = m[0] + (n_rows - sum), m'[t] = m[t] elsewhere:
+ *   the circuit's rows that no row of the string covers evaluate to the tables' first row, the dummy tuple.  A_idx is non-decreasing and holds row t
+ *   m'[t] times.  Position i is a first position where i == 0 or A_idx[i] != A_idx[i - 1]; there S_idx[i] = A_idx[i].  The j-th position (from 0) that is
+ *   no first position takes the j-th element of the fill list: the rows with m'[t] == 0 ascending, then row 0 n_rows - T times (the table padded to the
+ *   circuit's rows with copies of its first row).
+ * counts: [b_count][W] u32 exactly as hrx_lookup_counts_device writes them, 16-byte aligned.  `misses` is no argument: the columns are built from the
+ * counts as they lie, and a caller who wants a valid argument checks misses == 0 itself.  M is no argument either: rows beyond a string's own are the
+ * n_rows - sum rows of row 0.  With n_b == M the counts leave the transition and end lookups of row M - 1 out (LOOKUP COUNTS), so in A' those two inputs
+ * appear as the dummy row's cell, not as the cell hrx_lookup_compress_inputs_device computes for that row.
+ * n_rows: at least every T_d and E_d of the defs, at most 2^24.  pitch: the entries between consecutive (column, string) runs of the outputs, at least
+ * n_rows and a multiple of 4 (a caller passes 2^k to write straight into polynomial buffers); 0 = n_rows rounded up to a multiple of 4.  Entries
+ * [n_rows, pitch) are never written: the blinding rows are the caller's.
+ * a_idx, s_idx: [3 D][b_count][pitch] u32, 16-byte aligned, column 3 d + k in hrx_lookup_num_columns' order (k = 0 trans, 1 start, 2 end); the entries are
+ * word indices into the string's run — trans_off + t, start_off + e, end_off + e: the index space of the counts and of hrx_lookup_compress_table_device.
+ * Both or neither.  a_cells, s_cells: [3 D][b_count][pitch][4] u64, 16-byte aligned: the table cell at the index, copied limb for limb (Montgomery and
+ * canonical limbs alike; no arithmetic).  table_cells: [runs][W][4] u64 as hrx_lookup_compress_table_device writes it, 16-byte aligned; table_stride in
+ * u64 words: 0 — one run for the whole call; 4 W — run i belongs to string i of the window; anything else HRX_ERR_ARG.  All three or none; at least one
+ * of the index pair and the cell pair.
+ * overflow: [b_count] u32 or NULL (at most 10 defs with it): bit 3 d + k is set where that lookup's sum exceeds n_rows.  Of such a lookup every index in
+ * [0, n_rows) is 0xffffffff and every limb of its cells 0; the string's other lookups are not affected.  No count value ever forms an address.
+ * Refused with HRX_ERR_ARG, nothing written: NULL counts, half-given pairs or no output, misaligned buffers, a bad table_stride, n_rows or pitch, and for
+ * the device form a missing, misaligned (256 bytes) or too small workspace.  A host-only context: HRX_ERR_HIP for the device form.
+ * The device form: one launch, one more with `overflow`, asynchronous on `stream`; nothing allocated, no context scratch, no global atomics,
+ * deterministic; no image of the tables is read, so it is capturable from a context's first call.  workspace: device memory of
+ * hrx_lookup_permute_workspace_bytes(defs, b_count, n_rows) bytes — 0, and NULL accepted, unless a table of the defs has more rows than the kernel keeps
+ * in LDS at once (its lists of empty rows then lie there); its contents do not matter and it is free again once the call's work on `stream` is done. */
+size_t hrx_lookup_permute_workspace_bytes(const hrx_defs *defs, size_t b_count, size_t n_rows);
+int hrx_lookup_permute_device(hrx_ctx *ctx, const uint32_t *counts, size_t b_count, size_t n_rows, size_t pitch,
+                              uint32_t *a_idx, uint32_t *s_idx,
+                              const uint64_t *table_cells, size_t table_stride, uint64_t *a_cells, uint64_t *s_cells,
+                              uint32_t *overflow, void *workspace, size_t workspace_bytes, void *stream);
+/* The same with everything in HOST memory, on a host-only or a device context, over HRX_OPT_HOST_THREADS threads by ranges of strings.  The definition
+ * of the columns. */
+int hrx_lookup_permute_host(hrx_ctx *ctx, const uint32_t *counts, size_t b_count, size_t n_rows, size_t pitch,
+                            uint32_t *a_idx, uint32_t *s_idx,
+                            const uint64_t *table_cells, size_t table_stride, uint64_t *a_cells, uint64_t *s_cells,
+                            uint32_t *overflow);
+/* How a device call cuts its work: a workgroup serves one (string, lookup) and *group_rows positions of it (*groups workgroups per lookup: 1 unless the
+ * window is too small to fill the device), expands them *tile_rows positions at a time on absolute tile borders, and walks the table *chunk_rows rows at
+ * a time (a table of more rows: one workgroup per lookup, and a workspace).  For tests and tools; the columns do not depend on it. */
+int hrx_ctx_lookup_permute_plan(hrx_ctx *ctx, size_t b_count, size_t n_rows, size_t *tile_rows, size_t *chunk_rows, size_t *group_rows, size_t *groups);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */
 /* ------------------------------------------------------------------ */
 /* One circuit: EXACTLY the Vecs the three derive_* calls at the top of match_substrs return (src/lib.rs:316-318), out of the string's compact records, so that the body
