@@ -654,6 +654,23 @@ def _theta_stride(theta, count, dtype):
     return 0 if shape == (4,) else 4
 
 
+def _out_buffer(buf, name, shape, dtype, device=None, zeros=False):
+    """An output buffer of `shape` and `dtype` (a torch dtype: a tensor on `device`; otherwise a numpy array): the caller's `buf` if it has this dtype, is
+    contiguous and holds exactly that many elements, else HrxError(HRX_ERR_ARG); buf None: a fresh one, uninitialised unless zeros (numpy only)."""
+    on_torch = isinstance(dtype, torch.dtype)
+    if buf is None:
+        return torch.empty(shape, dtype=dtype, device=device) if on_torch else (np.zeros if zeros else np.empty)(shape, dtype)
+    if buf.dtype != dtype or not (buf.is_contiguous() if on_torch else buf.flags.c_contiguous) or (buf.numel() if on_torch else buf.size) != int(np.prod(shape)):
+        kind = "%s tensor" % str(dtype).replace("torch.", "") if on_torch else "%s array" % np.dtype(dtype).name
+        raise HrxError(HRX_ERR_ARG, "%s: a contiguous %s of %s elements" % (name, kind, "".join("[%d]" % x for x in shape)))
+    return buf
+
+
+def _planes_array(planes):
+    """the `const uint32_t *const *record_planes` argument of the _planes entry points out of a list of CUDA tensors"""
+    return (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+
+
 def _numpy_rows(chars, records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride):
     """(chars, records, masked, stride, rec_pitch, msk_pitch) as the host entry points that read witness rows take them, from numpy arrays: the flat
     position-major buffers contiguous, a pitch of 0 taken from a string-major view's strides.  masked None: a reader without masked rows."""
@@ -1342,10 +1359,7 @@ class RegexVerifyConfig:
         assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous() and chars.dtype == torch.uint8
         B, M, D = lens.numel(), self.max_chars_size, self.num_defs
         stride, rec_pitch, msk_pitch = _torch_row_pitches(chars, None if planes is not None else records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride)
-        if out is None:
-            out = torch.empty((B,), dtype=torch.int64, device=lens.device)
-        elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != B:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous int64 tensor of %d elements" % B)
+        out = _out_buffer(out, "out", (B,), torch.int64, lens.device)
         s = torch.cuda.current_stream(lens.device) if stream is None else stream
         if chunk_rows is not None:
             chunk_rows = int(chunk_rows)
@@ -1354,7 +1368,7 @@ class RegexVerifyConfig:
                 workspace = torch.empty((max(need, 16),), dtype=torch.uint8, device=lens.device)
             ws_bytes = workspace.numel() * workspace.element_size()
             if planes is not None:
-                arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+                arr = _planes_array(planes)
                 _check(lib.hrx_verify_rows_chunked_device_planes(self._need_device(chars, lens, masked, out, workspace, *planes), int(layout), chars.data_ptr(), stride,
                                                                  lens.data_ptr(), arr, len(planes), masked.data_ptr(), B, M, chunk_rows, workspace.data_ptr(), ws_bytes,
                                                                  out.data_ptr(), s.cuda_stream))
@@ -1364,7 +1378,7 @@ class RegexVerifyConfig:
                                                       out.data_ptr(), s.cuda_stream))
             return out
         if planes is not None:
-            arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+            arr = _planes_array(planes)
             _check(lib.hrx_verify_rows_device_planes(self._need_device(chars, lens, masked, out, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(), arr, len(planes),
                                                      masked.data_ptr(), B, M, out.data_ptr(), s.cuda_stream))
             return out
@@ -1379,10 +1393,7 @@ class RegexVerifyConfig:
         lens = np.ascontiguousarray(lens, np.uint32)
         B, M, D = len(lens), self.max_chars_size, self.num_defs
         ch, rec, msk, stride, rec_pitch, msk_pitch = _numpy_rows(chars, records, masked, layout, D, rec_pitch, msk_pitch, chars_pm_stride)
-        if out is None:
-            out = np.empty(B, np.uint64)
-        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != B:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of %d elements" % B)
+        out = _out_buffer(out, "out", (B,), np.uint64)
         if chunk_rows is not None:
             _check(lib.hrx_verify_rows_chunked_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch),
                                                     msk.ctypes.data, int(msk_pitch), B, M, int(chunk_rows), out.ctypes.data))
@@ -1423,17 +1434,11 @@ class RegexVerifyConfig:
         B, M, D, W = lens.numel(), self.max_chars_size, self.num_defs, self.lookup_words()
         b_count = B - b_begin if b_count is None else int(b_count)
         stride, rec_pitch, _ = _torch_row_pitches(chars, None if planes is not None else rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
-        if out is None:
-            out = torch.empty((b_count, W), dtype=torch.int32, device=lens.device)
-        elif out.dtype != torch.int32 or not out.is_contiguous() or out.numel() != b_count * W:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous int32 tensor of [%d][%d] elements" % (b_count, W))
-        if misses is None:
-            misses = torch.empty((b_count,), dtype=torch.int32, device=lens.device)
-        elif misses.dtype != torch.int32 or not misses.is_contiguous() or misses.numel() != b_count:
-            raise HrxError(HRX_ERR_ARG, "misses: a contiguous int32 tensor of %d elements" % b_count)
+        out = _out_buffer(out, "out", (b_count, W), torch.int32, lens.device)
+        misses = _out_buffer(misses, "misses", (b_count,), torch.int32, lens.device)
         s = torch.cuda.current_stream(lens.device) if stream is None else stream
         if planes is not None:
-            arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+            arr = _planes_array(planes)
             _check(lib.hrx_lookup_counts_device_planes(self._need_device(chars, lens, out, misses, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(), arr,
                                                        len(planes), B, M, int(b_begin), b_count, out.data_ptr(), misses.data_ptr(), s.cuda_stream))
             return out, misses
@@ -1449,14 +1454,8 @@ class RegexVerifyConfig:
         B, M, D, W = len(lens), self.max_chars_size, self.num_defs, self.lookup_words()
         b_count = B - b_begin if b_count is None else int(b_count)
         ch, rec, _, stride, rec_pitch, _ = _numpy_rows(chars, rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
-        if out is None:
-            out = np.empty((b_count, W), np.uint32)
-        elif out.dtype != np.uint32 or not out.flags.c_contiguous or out.size != b_count * W:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint32 array of [%d][%d] elements" % (b_count, W))
-        if misses is None:
-            misses = np.empty(b_count, np.uint32)
-        elif misses.dtype != np.uint32 or not misses.flags.c_contiguous or misses.size != b_count:
-            raise HrxError(HRX_ERR_ARG, "misses: a contiguous uint32 array of %d elements" % b_count)
+        out = _out_buffer(out, "out", (b_count, W), np.uint32)
+        misses = _out_buffer(misses, "misses", (b_count,), np.uint32)
         _check(lib.hrx_lookup_counts_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch), B, M, int(b_begin),
                                           b_count, out.ctypes.data, misses.ctypes.data))
         return out, misses
@@ -1474,15 +1473,11 @@ class RegexVerifyConfig:
         b_count = B - b_begin if b_count is None else int(b_count)
         stride, rec_pitch, _ = _torch_row_pitches(chars, None if planes is not None else rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
         theta_stride = _theta_stride(theta, b_count, torch.int64)
-        ncols = 3 * D
-        if out is None:
-            out = torch.empty((ncols, b_count, M, 4), dtype=torch.int64, device=lens.device)
-        elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != ncols * b_count * M * 4:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous int64 tensor of [%d][%d][%d][4] elements" % (ncols, b_count, M))
+        out = _out_buffer(out, "out", (3 * D, b_count, M, 4), torch.int64, lens.device)
         s = torch.cuda.current_stream(lens.device) if stream is None else stream
         flags = FR_CANONICAL if canonical else 0
         if planes is not None:
-            arr = (C.c_void_p * len(planes))(*[p.data_ptr() for p in planes])
+            arr = _planes_array(planes)
             _check(lib.hrx_lookup_compress_inputs_device_planes(self._need_device(chars, lens, theta, out, *planes), int(layout), chars.data_ptr(), stride, lens.data_ptr(),
                                                                 arr, len(planes), B, M, int(b_begin), b_count, theta.data_ptr(), theta_stride, out.data_ptr(), flags,
                                                                 s.cuda_stream))
@@ -1501,11 +1496,7 @@ class RegexVerifyConfig:
         ch, rec, _, stride, rec_pitch, _ = _numpy_rows(chars, rec, None, layout, D, rec_pitch, 0, chars_pm_stride)
         theta = np.ascontiguousarray(theta, np.uint64)
         theta_stride = _theta_stride(theta, b_count, np.uint64)
-        ncols = 3 * D
-        if out is None:
-            out = np.empty((ncols, b_count, M, 4), np.uint64)
-        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != ncols * b_count * M * 4:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of [%d][%d][%d][4] elements" % (ncols, b_count, M))
+        out = _out_buffer(out, "out", (3 * D, b_count, M, 4), np.uint64)
         _check(lib.hrx_lookup_compress_inputs_host(self._need_ctx(), int(layout), ch.ctypes.data, stride, lens.ctypes.data, rec.ctypes.data, int(rec_pitch), B, M,
                                                    int(b_begin), b_count, theta.ctypes.data, theta_stride, out.ctypes.data, FR_CANONICAL if canonical else 0))
         return out
@@ -1518,10 +1509,7 @@ class RegexVerifyConfig:
         W = self.lookup_words()
         n_theta = 1 if theta.dim() == 1 else theta.shape[0]
         _theta_stride(theta, n_theta, torch.int64)
-        if out is None:
-            out = torch.empty((n_theta, W, 4), dtype=torch.int64, device=theta.device)
-        elif out.dtype != torch.int64 or not out.is_contiguous() or out.numel() != n_theta * W * 4:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous int64 tensor of [%d][%d][4] elements" % (n_theta, W))
+        out = _out_buffer(out, "out", (n_theta, W, 4), torch.int64, theta.device)
         s = torch.cuda.current_stream(theta.device) if stream is None else stream
         _check(lib.hrx_lookup_compress_table_device(self._need_device(theta, out), theta.data_ptr(), 4, n_theta, out.data_ptr(), FR_CANONICAL if canonical else 0,
                                                     s.cuda_stream))
@@ -1533,10 +1521,7 @@ class RegexVerifyConfig:
         theta = np.ascontiguousarray(theta, np.uint64)
         n_theta = 1 if theta.ndim == 1 else theta.shape[0]
         _theta_stride(theta, n_theta, np.uint64)
-        if out is None:
-            out = np.empty((n_theta, W, 4), np.uint64)
-        elif out.dtype != np.uint64 or not out.flags.c_contiguous or out.size != n_theta * W * 4:
-            raise HrxError(HRX_ERR_ARG, "out: a contiguous uint64 array of [%d][%d][4] elements" % (n_theta, W))
+        out = _out_buffer(out, "out", (n_theta, W, 4), np.uint64)
         _check(lib.hrx_lookup_compress_table_host(self._need_ctx(), theta.ctypes.data, 4, n_theta, out.ctypes.data, FR_CANONICAL if canonical else 0))
         return out
 
@@ -1562,56 +1547,43 @@ class RegexVerifyConfig:
         workspace: an int8 CUDA tensor of lookup_permute_workspace_bytes() bytes (allocated where needed and not given).  One launch (two with overflow),
         asynchronous on `stream` (default: torch's current stream), capturable from the first call."""
         assert counts.is_cuda and counts.dtype == torch.int32 and counts.is_contiguous()
-        W, ncols = self.lookup_words(), 3 * self.num_defs
-        b_count = counts.numel() // W if W else 0
-        if counts.numel() != b_count * W:
-            raise HrxError(HRX_ERR_ARG, "counts: a contiguous int32 tensor of [b_count][%d] elements" % W)
-        n_rows, pitch = int(n_rows), int(pitch)
-        p = pitch if pitch else (n_rows + 3) & ~3
-        given = out if isinstance(out, dict) else {}
-        want_idx = "a_idx" in given if given else "idx" in out
-        want_cells = "a_cells" in given if given else (table is not None and "cells" in out)
-        res = {}
-
-        def buf(name, shape, dtype):
-            t = given.get(name)
-            if t is None:
-                t = torch.empty(shape, dtype=dtype, device=counts.device)
-            elif t.dtype != dtype or not t.is_contiguous() or t.numel() != int(np.prod(shape)):
-                raise HrxError(HRX_ERR_ARG, "%s: a contiguous tensor of %s elements" % (name, "x".join(str(x) for x in shape)))
-            res[name] = t
-            return t
-
-        a_idx = s_idx = a_cells = s_cells = ov = None
-        if want_idx:
-            a_idx, s_idx = buf("a_idx", (ncols, b_count, p), torch.int32), buf("s_idx", (ncols, b_count, p), torch.int32)
-        table_stride = 0
-        if want_cells:
-            if table is None or table.dtype != torch.int64 or not table.is_contiguous() or tuple(table.shape) not in ((W, 4), (b_count, W, 4)):
-                raise HrxError(HRX_ERR_ARG, "table: a contiguous int64 tensor of [%d][4] or [%d][%d][4] limbs" % (W, b_count, W))
-            table_stride = 4 * W if table.dim() == 3 else 0
-            a_cells, s_cells = buf("a_cells", (ncols, b_count, p, 4), torch.int64), buf("s_cells", (ncols, b_count, p, 4), torch.int64)
-        if overflow or "overflow" in given:
-            ov = buf("overflow", (b_count,), torch.int32)
-        need = self.lookup_permute_workspace_bytes(b_count, n_rows)
-        if workspace is None and need:
-            workspace = torch.empty(need, dtype=torch.int8, device=counts.device)
         s = torch.cuda.current_stream(counts.device) if stream is None else stream
-        ptr = lambda t: t.data_ptr() if t is not None else None
-        _check(lib.hrx_lookup_permute_device(self._need_device(counts, a_idx, s_idx, table if want_cells else None, a_cells, s_cells, ov, workspace), counts.data_ptr(),
-                                             b_count, n_rows, pitch, ptr(a_idx), ptr(s_idx), ptr(table) if want_cells else None, table_stride, ptr(a_cells),
-                                             ptr(s_cells), ptr(ov), ptr(workspace), workspace.numel() if workspace is not None else 0, s.cuda_stream))
-        return res
+
+        def call(b_count, pitch, a_idx, s_idx, table, table_stride, a_cells, s_cells, ov):
+            ws = workspace
+            need = self.lookup_permute_workspace_bytes(b_count, n_rows)
+            if ws is None and need:
+                ws = torch.empty(need, dtype=torch.int8, device=counts.device)
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            return lib.hrx_lookup_permute_device(self._need_device(counts, a_idx, s_idx, table, a_cells, s_cells, ov, ws), counts.data_ptr(), b_count, int(n_rows),
+                                                 pitch, ptr(a_idx), ptr(s_idx), ptr(table), table_stride, ptr(a_cells), ptr(s_cells), ptr(ov), ptr(ws),
+                                                 ws.numel() if ws is not None else 0, s.cuda_stream)
+
+        return self._lookup_permute(counts, n_rows, table, pitch, out, overflow, torch.int32, torch.int64, counts.device, call)
 
     def lookup_permute_host(self, counts, n_rows, table=None, pitch=0, out=("idx", "cells"), overflow=True):
         """hrx_lookup_permute_host: lookup_permute over numpy arrays in host memory, on a host-only or a device context — the definition of the columns
         (csrc/hrx_permute.hpp) over host threads.  counts uint32 (b_count, lookup_words()); table uint64 (W, 4) or (b_count, W, 4); the dict's arrays are
         uint32 / uint64.  Entries [n_rows, pitch) are never written (arrays allocated here hold zeros there)."""
         counts = np.ascontiguousarray(counts, np.uint32)
+        table = None if table is None else np.ascontiguousarray(table, np.uint64)
+
+        def call(b_count, pitch, a_idx, s_idx, table, table_stride, a_cells, s_cells, ov):
+            ptr = lambda t: t.ctypes.data if t is not None else None
+            return lib.hrx_lookup_permute_host(self._need_ctx(), counts.ctypes.data, b_count, int(n_rows), pitch, ptr(a_idx), ptr(s_idx), ptr(table), table_stride,
+                                               ptr(a_cells), ptr(s_cells), ptr(ov))
+
+        return self._lookup_permute(counts, n_rows, table, pitch, out, overflow, np.uint32, np.uint64, None, call)
+
+    def _lookup_permute(self, counts, n_rows, table, pitch, out, overflow, u32, u64, device, call):
+        """what lookup_permute (torch: u32 / u64 are torch.int32 / torch.int64, buffers on `device`) and lookup_permute_host (numpy, device None) share: which
+        outputs the caller wants, their buffers — the caller's or fresh ones; numpy's zeroed — and the call: call(b_count, pitch, a_idx, s_idx, table,
+        table_stride, a_cells, s_cells, overflow) with None for what is not wanted"""
         W, ncols = self.lookup_words(), 3 * self.num_defs
-        b_count = counts.size // W if W else 0
-        if counts.size != b_count * W:
-            raise HrxError(HRX_ERR_ARG, "counts: a contiguous uint32 array of [b_count][%d] elements" % W)
+        size = counts.numel() if device is not None else counts.size
+        b_count = size // W if W else 0
+        if size != b_count * W:
+            raise HrxError(HRX_ERR_ARG, "counts: a contiguous 32-bit array or tensor of [b_count][%d] elements" % W)
         n_rows, pitch = int(n_rows), int(pitch)
         p = pitch if pitch else (n_rows + 3) & ~3
         given = out if isinstance(out, dict) else {}
@@ -1620,29 +1592,22 @@ class RegexVerifyConfig:
         res = {}
 
         def buf(name, shape, dtype):
-            t = given.get(name)
-            if t is None:
-                t = np.zeros(shape, dtype)
-            elif t.dtype != dtype or not t.flags.c_contiguous or t.size != int(np.prod(shape)):
-                raise HrxError(HRX_ERR_ARG, "%s: a contiguous array of %s elements" % (name, "x".join(str(x) for x in shape)))
-            res[name] = t
-            return t
+            res[name] = _out_buffer(given.get(name), name, shape, dtype, device, zeros=True)
+            return res[name]
 
         a_idx = s_idx = a_cells = s_cells = ov = None
         if want_idx:
-            a_idx, s_idx = buf("a_idx", (ncols, b_count, p), np.uint32), buf("s_idx", (ncols, b_count, p), np.uint32)
-        table_stride = 0
+            a_idx, s_idx = buf("a_idx", (ncols, b_count, p), u32), buf("s_idx", (ncols, b_count, p), u32)
         if want_cells:
-            table = None if table is None else np.ascontiguousarray(table, np.uint64)
-            if table is None or tuple(table.shape) not in ((W, 4), (b_count, W, 4)):
-                raise HrxError(HRX_ERR_ARG, "table: uint64 limbs of shape [%d][4] or [%d][%d][4]" % (W, b_count, W))
-            table_stride = 4 * W if table.ndim == 3 else 0
-            a_cells, s_cells = buf("a_cells", (ncols, b_count, p, 4), np.uint64), buf("s_cells", (ncols, b_count, p, 4), np.uint64)
+            contiguous = table is not None and (table.is_contiguous() if device is not None else table.flags.c_contiguous)
+            if not contiguous or table.dtype != u64 or tuple(table.shape) not in ((W, 4), (b_count, W, 4)):
+                raise HrxError(HRX_ERR_ARG, "table: contiguous 64-bit limbs of shape [%d][4] or [%d][%d][4]" % (W, b_count, W))
+            a_cells, s_cells = buf("a_cells", (ncols, b_count, p, 4), u64), buf("s_cells", (ncols, b_count, p, 4), u64)
+        else:
+            table = None
         if overflow or "overflow" in given:
-            ov = buf("overflow", (b_count,), np.uint32)
-        ptr = lambda t: t.ctypes.data if t is not None else None
-        _check(lib.hrx_lookup_permute_host(self._need_ctx(), counts.ctypes.data, b_count, n_rows, pitch, ptr(a_idx), ptr(s_idx), ptr(table) if want_cells else None,
-                                           table_stride, ptr(a_cells), ptr(s_cells), ptr(ov)))
+            ov = buf("overflow", (b_count,), u32)
+        _check(call(b_count, pitch, a_idx, s_idx, table, 4 * W if table is not None and len(table.shape) == 3 else 0, a_cells, s_cells, ov))
         return res
 
     def witness_batch(self, chars, lens, out=None, stream=None):

@@ -756,7 +756,7 @@ static int fr_columns_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (b_count == 0) return HRX_OK;
     if (!chars || !lens || (!records && !planes) || !masked || !cells) return fail(HRX_ERR_ARG, "NULL buffer");
-    if (b_begin > B || b_count > B - b_begin) return fail(HRX_ERR_ARG, "string range outside the batch");
+    if (int rc = check_window(B, b_begin, b_count)) return rc;
     if (M == 0 || M > kRowsMaxRows || B > 0xffffffffull - 64) return fail(HRX_ERR_ARG, "shape out of range");
     if (int rc = check_rows_layout(layout)) return rc;
     if ((uintptr_t)cells & 15) return fail(HRX_ERR_ARG, "cells must be 16-byte aligned");

@@ -13,7 +13,7 @@
 // every one of its cells is 0.
 //
 // Cells: [3 D][strings][M][4] u64, column 3 d + k: k = 0 trans, 1 start, 2 end of def d.  Table cells: per theta one run of W cells in the index space of
-// the counts (hrx_lookup.hpp): per def trans[T_d], start[E_d], end[E_d] — the two endpoint runs hold equal cells — and zero cells for the pad words.
+// the counts (the run of hrx_lookup_run.hpp) — the two endpoint runs of a def hold equal cells — and zero cells for the pad words.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -21,7 +21,8 @@
 #include <vector>
 
 #include "hrx_fr.h"
-#include "hrx_verify.hpp"      // HRX_XHD, RowsIn (hrx_rows.hpp), VerifyDefRows
+#include "hrx_lookup_run.hpp"  // the run's layout
+#include "hrx_verify.hpp"     // HRX_XHD, RowsIn (hrx_rows.hpp), VerifyDefRows
 
 namespace hrx {
 
@@ -87,13 +88,16 @@ inline void compress_string(const CompressArgs &a, size_t i, uint32_t n, const S
     }
 }
 
-// The rows of the fixed tables in the index space of the counts, as a flat (a0, a1, a2, a3) u32 array: 4 W words, W = lookup_words.  trans[T_d]: (char, cur,
-// next, sid) of transition row t; start[E_d] and end[E_d]: (0, sid, start_state, end_state) of endpoint row e, both runs; the pad words (0, 0, 0, 0), whose
-// fold is the zero cell.  false: a value that is no 16-bit tuple component (whatever build_lookup_image refuses for its size), or no rows.
+// The rows of the fixed tables in the index space of the counts, as a flat (a0, a1, a2, a3) u32 array: 4 W words, W the run's of hrx_lookup_run.hpp.
+// trans[T_d]: (char, cur, next, sid) of transition row t; start[E_d] and end[E_d]: (0, sid, start_state, end_state) of endpoint row e, both runs; the pad
+// words (0, 0, 0, 0), whose fold is the zero cell.  false: a value that is no 16-bit tuple component, no rows, a run lookup_run_fill refuses, or an image
+// that did not come out at the run's 4 W words.
 inline bool build_compress_image(const VerifyDefRows *rows, size_t D, std::vector<uint32_t> &img) {
     if (D == 0) return false;
+    LookupRun run;
+    if (!lookup_run_fill(run, D, [rows](size_t d, size_t &t, size_t &e) { t = rows[d].n_tr; e = rows[d].n_ep; })) return false;
     img.clear();
-    for (size_t d = 0; d < D; ++d) {
+    for (size_t d = 0; d < D; ++d) {      // appended in the run's order: trans, start, end of each def
         const VerifyDefRows &R = rows[d];
         if (R.n_tr < 1 || R.n_ep < 1) return false;
         for (size_t k = 0; k < 4 * R.n_tr; ++k) {
@@ -108,10 +112,9 @@ inline bool build_compress_image(const VerifyDefRows *rows, size_t D, std::vecto
                     img.push_back((uint32_t)R.ep[3 * k + j]);
                 }
             }
-        if (img.size() / 4 > 0x7fffffffull) return false;
     }
-    img.resize((img.size() / 4 + 3) / 4 * 16, 0u);
-    return true;
+    img.resize(4 * (size_t)lookup_run_words(img.size() / 4), 0u);
+    return img.size() == 4 * (size_t)run.W;
 }
 
 // What a compress call over the table is told

@@ -2,7 +2,8 @@
 // hrx_fr_mul (include/hrx.h LOOKUP COMPRESS): the lookup tuples of the witness rows and the rows of the fixed tables folded with a challenge into field
 // cells.  The rule is hrx_compress.hpp's, the kernels hrx_kernel_compress.hip, the host forms hrx_compress_host.cpp.  The calls over rows read no image of
 // the tables (a def's dummy state travels in the arguments): one launch from the first call on.  The table calls read the context's flat tuple array, built
-// from the rows RegexTableConfig::load assigns at the context's first call of this kind, under its lock, and for a device call uploaded then.  DESIGN.md §20.
+// from the rows RegexTableConfig::load assigns at the context's first call of this kind, under its lock, and for a device call uploaded then — one run of
+// hrx_lookup_run.hpp's layout.  DESIGN.md §20.
 #include "hrx_compress.hpp"
 #include "hrx_ctx.hpp"
 #include "hrx_kernel.hpp"
@@ -21,14 +22,13 @@ static int check_theta(const uint64_t *theta, size_t theta_stride, const uint64_
     return HRX_OK;
 }
 
-// the argument rules the forms over rows share: check_rows' (hrx_rows_api.cpp) for the rows (no masked rows), hrx_lookup_counts_device's for the window
-static int check_compress_args(const hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
-                               const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
-                               const uint64_t *theta, size_t theta_stride, uint64_t *cells, int flags, bool device, CompressArgs &a) {
+// the argument rules the forms over rows share: check_rows' (hrx_rows_api.cpp) for the rows (no masked rows), check_window's
+static int check_compress_args(const hrx_ctx *ctx, const RowsCall &c, size_t b_begin, size_t b_count, const uint64_t *theta, size_t theta_stride, uint64_t *cells,
+                               int flags, bool device, CompressArgs &a) {
     if (int rc = check_theta(theta, theta_stride, cells, flags)) return rc;
-    if (b_begin > B || b_count > B - b_begin) return fail(HRX_ERR_ARG, "string range outside the batch");
+    if (int rc = check_window(c.B, b_begin, b_count)) return rc;
     a = CompressArgs{};
-    if (int rc = check_rows(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, nullptr, 0, B, M, device, a)) return rc;
+    if (int rc = check_rows(ctx, c, device, a)) return rc;
     if (a.D > HRX_MAX_DEFS) return fail(HRX_ERR_ARG, "more defs than HRX_MAX_DEFS");
     for (uint32_t d = 0; d < a.D; ++d) {
         const uint64_t dummy = ctx->s.defs[d].allstr.largest_state_val + 1;      // table.rs:67
@@ -37,21 +37,20 @@ static int check_compress_args(const hrx_ctx *ctx, int layout, const uint8_t *ch
     }
     a.b_begin = (uint32_t)b_begin; a.b_count = (uint32_t)b_count;
     a.theta = theta; a.theta_stride = (uint32_t)theta_stride; a.canonical = (flags & HRX_FR_CANONICAL) ? 1u : 0u;
-    a.cells = cells; a.col_cells = (uint64_t)b_count * M;
+    a.cells = cells; a.col_cells = (uint64_t)b_count * c.M;
     return HRX_OK;
 }
 
-static int compress_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
-                               const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, size_t B, size_t M, size_t b_begin, size_t b_count,
-                               const uint64_t *theta, size_t theta_stride, uint64_t *cells, int flags, void *stream) {
+static int compress_device_any(hrx_ctx *ctx, const RowsCall &c, size_t b_begin, size_t b_count, const uint64_t *theta, size_t theta_stride, uint64_t *cells,
+                               int flags, void *stream) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (b_count == 0) return HRX_OK;
     CompressArgs a;
-    if (int rc = check_compress_args(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, B, M, b_begin, b_count, theta, theta_stride, cells, flags, true, a)) return rc;
-    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (int rc = check_compress_args(ctx, c, b_begin, b_count, theta, theta_stride, cells, flags, true, a)) return rc;
+    if (int rc = check_has_device(ctx)) return rc;
     DeviceGuard guard;      // (stateless: no context scratch, no image, no lock)
     HIP_TRY(guard.set(ctx->device));
-    const size_t tiles_of_string = (M + kCzRowsPerTile - 1) / kCzRowsPerTile;
+    const size_t M = c.M, tiles_of_string = (M + kCzRowsPerTile - 1) / kCzRowsPerTile;
     a.tiles = (uint32_t)std::min<size_t>(tiles_of_string, kCzMaxTiles);
     // one launch per 32768 strings (the grid's y dimension), as the field cells have it; every launch writes its slice of each column
     for (size_t done = 0; done < b_count; done += 32768) {
@@ -64,16 +63,18 @@ static int compress_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, s
     return HRX_OK;
 }
 
-static int compress_image_host(hrx_ctx *ctx) { return ctx_image_host(ctx, ctx->compress_img, build_compress_image, "lookup compress"); }
+static int compress_image_host(hrx_ctx *ctx) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return ctx_image_host(ctx, ctx->compress_img, build_compress_image, "lookup compress");
+}
 static int compress_image_device(hrx_ctx *ctx, void *stream) { return ctx_image_device(ctx, ctx->compress_img, build_compress_image, "lookup compress", stream); }
 
-static int check_table_args(const hrx_ctx *ctx, const uint64_t *theta, size_t theta_stride, size_t n_theta, uint64_t *cells, int flags, CompressTableArgs &a) {
+static int check_table_args(const uint64_t *theta, size_t theta_stride, size_t n_theta, uint64_t *cells, int flags, CompressTableArgs &a) {
     if (int rc = check_theta(theta, theta_stride, cells, flags)) return rc;
     if (n_theta > 0xffffu) return fail(HRX_ERR_ARG, "n_theta: at most 65535 runs a call");
     a = CompressTableArgs{};
     a.theta = theta; a.theta_stride = (uint32_t)theta_stride; a.n_theta = (uint32_t)n_theta; a.canonical = (flags & HRX_FR_CANONICAL) ? 1u : 0u;
     a.cells = cells;
-    (void)ctx;
     return HRX_OK;
 }
 
@@ -93,14 +94,16 @@ void hrx_fr_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) {
 int hrx_lookup_compress_inputs_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
                                       size_t B, size_t M, size_t b_begin, size_t b_count, const uint64_t *theta, size_t theta_stride, uint64_t *cells, int flags,
                                       void *stream) {
-    return compress_device_any(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, B, M, b_begin, b_count, theta, theta_stride, cells, flags, stream);
+    return compress_device_any(ctx, RowsCall{layout, chars, stride, lens, records, nullptr, 0, rec_pitch, nullptr, 0, B, M}, b_begin, b_count, theta, theta_stride,
+                               cells, flags, stream);
 }
 
 int hrx_lookup_compress_inputs_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *const *record_planes,
                                              size_t n_planes, size_t B, size_t M, size_t b_begin, size_t b_count, const uint64_t *theta, size_t theta_stride,
                                              uint64_t *cells, int flags, void *stream) {
     if (!record_planes) return fail(HRX_ERR_ARG, "NULL buffer");
-    return compress_device_any(ctx, layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, B, M, b_begin, b_count, theta, theta_stride, cells, flags, stream);
+    return compress_device_any(ctx, RowsCall{layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, nullptr, 0, B, M}, b_begin, b_count, theta,
+                               theta_stride, cells, flags, stream);
 }
 
 int hrx_lookup_compress_inputs_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
@@ -108,13 +111,9 @@ int hrx_lookup_compress_inputs_host(hrx_ctx *ctx, int layout, const uint8_t *cha
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (b_count == 0) return HRX_OK;
     CompressArgs a;
-    if (int rc = check_compress_args(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, B, M, b_begin, b_count, theta, theta_stride, cells, flags, false, a)) return rc;
-    unsigned threads;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
-    }
-    compress_inputs_host(a, threads);
+    const RowsCall c{layout, chars, stride, lens, records, nullptr, 0, rec_pitch, nullptr, 0, B, M};
+    if (int rc = check_compress_args(ctx, c, b_begin, b_count, theta, theta_stride, cells, flags, false, a)) return rc;
+    compress_inputs_host(a, ctx_host_threads(ctx));
     return HRX_OK;
 }
 
@@ -122,8 +121,8 @@ int hrx_lookup_compress_table_device(hrx_ctx *ctx, const uint64_t *theta, size_t
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (n_theta == 0) return HRX_OK;
     CompressTableArgs a;
-    if (int rc = check_table_args(ctx, theta, theta_stride, n_theta, cells, flags, a)) return rc;
-    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (int rc = check_table_args(theta, theta_stride, n_theta, cells, flags, a)) return rc;
+    if (int rc = check_has_device(ctx)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
@@ -138,16 +137,11 @@ int hrx_lookup_compress_table_host(hrx_ctx *ctx, const uint64_t *theta, size_t t
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (n_theta == 0) return HRX_OK;
     CompressTableArgs a;
-    if (int rc = check_table_args(ctx, theta, theta_stride, n_theta, cells, flags, a)) return rc;
-    unsigned threads;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (int rc = compress_image_host(ctx)) return rc;
-        threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
-    }
+    if (int rc = check_table_args(theta, theta_stride, n_theta, cells, flags, a)) return rc;
+    if (int rc = compress_image_host(ctx)) return rc;
     a.image = ctx->compress_img.host.data();     // (never rebuilt once it is there)
     a.W = (uint32_t)(ctx->compress_img.host.size() / 4);
-    compress_table_host(a, threads);
+    compress_table_host(a, ctx_host_threads(ctx));
     return HRX_OK;
 }
 

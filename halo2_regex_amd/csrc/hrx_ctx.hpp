@@ -23,7 +23,7 @@
 #include "hrx_plan.hpp"
 #include "hrx_rows.hpp"
 
-namespace hrx { struct VerifyDefRows; }      // hrx_verify.hpp
+namespace hrx { struct VerifyDefRows; struct LookupRun; }      // hrx_verify.hpp, hrx_lookup_run.hpp
 
 #define HRX_INTERNAL __attribute__((visibility("hidden")))
 
@@ -191,9 +191,15 @@ HRX_INTERNAL int batch_host_locked(hrx_ctx *ctx, const uint8_t *chars, size_t st
 // and planes rules alone.
 HRX_INTERNAL int check_rows_layout(int layout);
 HRX_INTERNAL int check_rows_planes(const hrx_ctx *ctx, int layout, const uint32_t *const *planes, size_t n_planes);
-HRX_INTERNAL int check_rows(const hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
-                            const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M,
-                            bool device, hrx::RowsIn &a);
+HRX_INTERNAL int check_rows(const hrx_ctx *ctx, const hrx::RowsCall &c, bool device, hrx::RowsIn &a);
+// ... and three rules the entry points over rows and runs state alike: the window [b_begin, b_begin + b_count) inside the batch; a device to launch on;
+// the host threads of a host form (HRX_OPT_HOST_THREADS; 0: the form's own pick), read under the context's lock
+HRX_INTERNAL int check_window(size_t B, size_t b_begin, size_t b_count);
+HRX_INTERNAL int check_has_device(const hrx_ctx *ctx);
+HRX_INTERNAL unsigned ctx_host_threads(hrx_ctx *ctx);
+// hrx_rows_api.cpp: the run of one string in the lookup argument (hrx_lookup_run.hpp) for a config, from the rows table_transition_rows /
+// table_endpoint_rows count.  Computed per call.  false: lookup_run_fill's
+HRX_INTERNAL bool defs_lookup_run(const hrx::DefsSet &s, hrx::LookupRun &run);
 // hrx_rows_api.cpp: `im` of the context ready in host memory (the caller holds ctx->mu) / on its device (... and has set the device).  First use: built by
 // `build` from the rows RegexTableConfig::load assigns (never from a walk table), and for the device uploaded — an allocation and a blocking copy: not
 // inside a stream capture.  Never rebuilt once it is there.  noun: "verify" / "lookup counts", for the messages

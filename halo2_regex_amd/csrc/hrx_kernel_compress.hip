@@ -41,61 +41,13 @@ __device__ __forceinline__ void powers_of(const uint64_t *theta, const bool cano
     }
 }
 
-// TAB (tools build only, `make compresstab`: the second candidate, measured against the fold in place and not kept — DESIGN.md §20): per-workgroup LDS tables
-// v t_k mod r for v < 256 and the four multipliers t3, t2, t1, one (4 x 256 x 32 B = 32 KiB, one entry of each per lane), a cell = the modular sum of
-// its components' entries (fr_add); a component of 256 or more is multiplied in place.
-template <int REC, bool TAB>
+template <int REC>
 __global__ __launch_bounds__(kCzThreads) void compress_inputs_kernel(const CompressArgs a) {
     __shared__ FrPowers pw;
-    __shared__ uint4 tab[TAB ? 4u * 256u * 2u : 1u];
     const uint32_t bi = blockIdx.y;              // index inside the launch's strings
     const uint32_t b = a.b_begin + bi;
     FrPowers p;
     powers_of(a.theta + (size_t)bi * a.theta_stride, a.canonical != 0, &pw, p);
-    // v * (multiplier m: 0 one, 1 t1, 2 t2, 3 t3) mod r
-    auto scaled = [&](const uint32_t m, const uint32_t v, uint32_t (&w)[8]) {
-        if (m == 0u) fr_fold(0u, 0u, 0u, v, p.t3, p.t2, p.t1, p.one, w);
-        else if (m == 1u) fr_fold(0u, 0u, v, 0u, p.t3, p.t2, p.t1, p.one, w);
-        else if (m == 2u) fr_fold(0u, v, 0u, 0u, p.t3, p.t2, p.t1, p.one, w);
-        else fr_fold(v, 0u, 0u, 0u, p.t3, p.t2, p.t1, p.one, w);
-    };
-    if constexpr (TAB) {
-#pragma unroll
-        for (uint32_t m = 0; m < 4u; ++m) {
-            uint32_t w[8];
-            scaled(m, threadIdx.x, w);
-            tab[(m * 256u + threadIdx.x) * 2u] = make_uint4(w[0], w[1], w[2], w[3]);
-            tab[(m * 256u + threadIdx.x) * 2u + 1u] = make_uint4(w[4], w[5], w[6], w[7]);
-        }
-        __syncthreads();
-    }
-    // the cell of one tuple; FOUR: the tuple has a component e0 (the transition lookup)
-    auto cell_of = [&](const bool four, const uint32_t e0, const uint32_t e1, const uint32_t e2, const uint32_t e3, uint32_t (&w)[8]) {
-        if constexpr (!TAB) {
-            fr_fold(e0, e1, e2, e3, p.t3, p.t2, p.t1, p.one, w);
-        } else {
-            auto term = [&](const uint32_t m, const uint32_t v, uint32_t (&x)[8]) {
-                if (v < 256u) {
-                    const uint4 lo = tab[(m * 256u + v) * 2u], hi = tab[(m * 256u + v) * 2u + 1u];
-                    x[0] = lo.x; x[1] = lo.y; x[2] = lo.z; x[3] = lo.w; x[4] = hi.x; x[5] = hi.y; x[6] = hi.z; x[7] = hi.w;
-                } else {
-                    scaled(m, v, x);
-                }
-            };
-            uint32_t x[8], y[8];
-            term(0u, e3, w);
-            term(1u, e2, x);
-            fr_add(w, x, y);
-            term(2u, e1, x);
-            fr_add(y, x, w);
-            if (four) {
-                term(3u, e0, x);
-                fr_add(w, x, y);
-#pragma unroll
-                for (int i = 0; i < 8; ++i) w[i] = y[i];
-            }
-        }
-    };
     const uint32_t M = a.M, n = a.lens[b];
     const bool none = n > M;                     // the string has no rows: zero cells, nothing read
     const RowsPlace s = rows_place<false>(a, b);
@@ -140,7 +92,7 @@ __global__ __launch_bounds__(kCzThreads) void compress_inputs_kernel(const Compr
 #pragma unroll
                 for (uint32_t pr = 0; pr < kPairs; ++pr) {
                     uint32_t w[8];
-                    cell_of(col == 0u, e[pr][0], e[pr][1], e[pr][2], e[pr][3], w);
+                    fr_fold(e[pr][0], e[pr][1], e[pr][2], e[pr][3], p.t3, p.t2, p.t1, p.one, w);      // (a tuple of three components has e[0] = 0)
                     // the even lane sends the high half of its cell and takes the low half of the odd lane's
                     uint32_t got[4];
 #pragma unroll
@@ -187,16 +139,10 @@ __global__ __launch_bounds__(kCzThreads) void compress_table_kernel(const Compre
     }
 }
 
-#ifdef HRX_COMPRESS_LDS_TABLE
-constexpr bool kCzTab = true;
-#else
-constexpr bool kCzTab = false;
-#endif
-
 template <int REC>
 hipError_t launch_compress_form(const CompressArgs &a, hipStream_t stream) {
     const uint32_t rows_per_group = a.tiles * kCzRowsPerTile;
-    hipLaunchKernelGGL((compress_inputs_kernel<REC, kCzTab>), dim3((a.M + rows_per_group - 1u) / rows_per_group, a.b_count), dim3(kCzThreads), 0, stream, a);
+    hipLaunchKernelGGL(compress_inputs_kernel<REC>, dim3((a.M + rows_per_group - 1u) / rows_per_group, a.b_count), dim3(kCzThreads), 0, stream, a);
     return hipGetLastError();
 }
 

@@ -12,7 +12,7 @@
 // transition and end lookups of row M - 1 read a cell match_substrs never assigns: they are neither counted nor missed.  States, ids and flags outside every
 // table are misses and index nothing outside the image.
 //
-// A string's counts are one run of W u32 words: per def in order trans[T_d], start[E_d], end[E_d]; W a multiple of 4, the pad words 0.
+// A string's counts are one run of W u32 words, laid out as hrx_lookup_run.hpp states it; the pad words 0.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -20,6 +20,7 @@
 
 #include <vector>
 
+#include "hrx_lookup_run.hpp"  // the run's layout
 #include "hrx_verify.hpp"      // HRX_XHD, RowsIn (hrx_rows.hpp), VerifyDefRows
 
 namespace hrx {
@@ -83,11 +84,10 @@ HRX_XHD LookupHit lookup_def_row(const uint32_t *img, const LookupDef &T, uint32
     return h;
 }
 
-// words of one string's run: the defs' bins, rounded up to a multiple of 4
+// words of one string's run, read back from the image: where the last def's bins end, rounded as hrx_lookup_run.hpp rounds
 HRX_XHD uint32_t lookup_words(const uint32_t *img, uint32_t D) {
-    const LookupDef *defs = reinterpret_cast<const LookupDef *>(img);
-    const uint32_t w = defs[D - 1].off + defs[D - 1].n_tr + 2u * defs[D - 1].n_ep;
-    return (w + 3u) & ~3u;
+    const LookupDef &T = reinterpret_cast<const LookupDef *>(img)[D - 1];
+    return (uint32_t)lookup_run_words(T.off + lookup_run_def_words(T.n_tr, T.n_ep));
 }
 
 // One string of n characters over verify_string's accessor — src.chr(r) (r < n only), src.rec(r, d) — into counts[W] and its misses word: the definition.
@@ -115,11 +115,12 @@ inline uint32_t lookup_string(const uint32_t *img, uint32_t D, uint32_t n, uint3
 
 // The image of a config out of the rows RegexTableConfig::load assigns (build_verify_image's inputs).  false: rows the image cannot hold — whatever
 // build_verify_image refuses (the first row of either table is not the dummy row, a value out of range, two rows with one (char, cur) key that disagree),
-// or more bins than a u32 run indexes.  Two transition rows with one key that agree: the lower row takes the counts, as with endpoint rows.
+// or a run lookup_run_fill refuses.  Two transition rows with one key that agree: the lower row takes the counts, as with endpoint rows.
 inline bool build_lookup_image(const VerifyDefRows *rows, size_t D, std::vector<uint32_t> &img) {
     if (D == 0) return false;
+    LookupRun run;
+    if (!lookup_run_fill(run, D, [rows](size_t d, size_t &t, size_t &e) { t = rows[d].n_tr; e = rows[d].n_ep; })) return false;
     img.assign(D * kLkDefWords, 0u);
-    uint64_t off = 0;
     for (size_t d = 0; d < D; ++d) {
         const VerifyDefRows &R = rows[d];
         if (R.n_tr < 1 || R.n_ep < 1) return false;
@@ -131,9 +132,7 @@ inline bool build_lookup_image(const VerifyDefRows *rows, size_t D, std::vector<
         for (size_t k = 0; k < R.n_ep; ++k) max_sid = R.ep[3 * k] > max_sid ? R.ep[3 * k] : max_sid;
         if (max_sid > 0xffu) return false;
         T.nsid = (uint32_t)max_sid + 1u;
-        if (off + R.n_tr + 2 * R.n_ep > 0x7fffffffull) return false;
-        T.n_tr = (uint32_t)R.n_tr; T.n_ep = (uint32_t)R.n_ep; T.off = (uint32_t)off;
-        off += R.n_tr + 2 * R.n_ep;
+        T.n_tr = run.def[d].n_tr; T.n_ep = run.def[d].n_ep; T.off = run.def[d].off;
         const size_t keys = (size_t)T.nsid * T.ns;
         T.tab = (uint32_t)img.size();
         T.start = T.tab + T.ns * 512u;

@@ -20,8 +20,7 @@
 
 #include <algorithm>
 
-#include "../../include/hrx.h" // HRX_MAX_DEFS
-#include "hrx_rows.hpp"        // HRX_XHD
+#include "hrx_lookup_run.hpp"  // HRX_XHD, HRX_MAX_DEFS, PermuteCol: a lookup's place in a string's run
 
 namespace hrx {
 
@@ -60,12 +59,8 @@ inline PermutePlan plan_permute(size_t T_max, size_t W, size_t lookups, size_t b
     if (T_max > kPmChunkRows) {
         p.workspace_bytes = b_count * W * 4u;
     } else {
-#ifdef HRX_PERMUTE_TILE_GRID                        // tools build only (`make permutetiles`): the second candidate, a grid over row tiles — DESIGN.md §21
-        p.groups = (uint32_t)(tiles ? tiles : 1);
-#else
         const size_t want = 4u * (size_t)(num_cus > 0 ? num_cus : 256), have = b_count * lookups;
         if (have && have < want) p.groups = (uint32_t)std::min<size_t>(tiles ? tiles : 1, (want + have - 1) / have);
-#endif
     }
     const size_t per = tiles ? (tiles + p.groups - 1) / p.groups : 1;
     p.group_rows = (uint32_t)(per * kPmTileRows);
@@ -73,7 +68,6 @@ inline PermutePlan plan_permute(size_t T_max, size_t W, size_t lookups, size_t b
     return p;
 }
 
-struct PermuteCol { uint32_t off, T; };             // one lookup: where its counts begin in a string's run, and its table's rows
 // What a launch of the permute kernels, or the host form, reads
 struct PermuteArgs {
     const uint32_t *counts;                         // [b_count][W]
@@ -85,7 +79,7 @@ struct PermuteArgs {
     uint32_t *overflow;                             // [b_count], or NULL
     uint32_t *zrows;                                // the workspace: [b_count][W] (the kernel only, where a table has more than one chunk)
     uint32_t groups, group_rows;                    // plan_permute (the kernel only)
-    PermuteCol col[3 * HRX_MAX_DEFS];
+    PermuteCol col[3 * HRX_MAX_DEFS];               // lookup_run_col (hrx_lookup_run.hpp) of every lookup
 };
 
 }  // namespace hrx

@@ -1,7 +1,8 @@
 // hrx_permute_api.cpp — hrx_lookup_permute_device / _host / hrx_lookup_permute_workspace_bytes / hrx_ctx_lookup_permute_plan (include/hrx.h LOOKUP
 // PERMUTE): the permuted columns A', S' of halo2's lookup argument out of the counts, as indices into a string's run and as cells of the compressed table.
 // The rule is hrx_permute.hpp's, the kernels hrx_kernel_permute.hip, the host form hrx_permute_host.cpp.  The calls read no image of the tables (the runs'
-// layout comes from the defs' row counts): the device form is its launches from the first call on, stateless, no lock.  DESIGN.md §21.
+// layout is hrx_lookup_run.hpp's over the defs' row counts: defs_lookup_run of hrx_rows_api.cpp): the device form is its launches from the first call on,
+// stateless, no lock.  DESIGN.md §21.
 #include "hrx_ctx.hpp"
 #include "hrx_kernel.hpp"
 #include "hrx_permute.hpp"
@@ -11,24 +12,7 @@ void permute_host(const PermuteArgs &a, unsigned threads);      // hrx_permute_h
 }
 using namespace hrx;
 
-// the lookups of a config in hrx_lookup_num_columns' order, as hrx_lookup_layout places them; returns W (0: more defs than HRX_MAX_DEFS)
-static size_t permute_cols_of(const DefsSet &s, PermuteCol *col, size_t &T_max) {
-    size_t w = 0;
-    T_max = 0;
-    if (s.defs.size() > HRX_MAX_DEFS) return 0;
-    for (size_t d = 0; d < s.defs.size(); ++d) {
-        const size_t t = table_transition_rows(s, d, nullptr, 0), e = table_endpoint_rows(s, d, nullptr, 0);
-        if (w + t + 2 * e > 0x7fffffffull) return 0;
-        if (col) {
-            col[3 * d] = PermuteCol{(uint32_t)w, (uint32_t)t};
-            col[3 * d + 1] = PermuteCol{(uint32_t)(w + t), (uint32_t)e};
-            col[3 * d + 2] = PermuteCol{(uint32_t)(w + t + e), (uint32_t)e};
-        }
-        T_max = std::max(T_max, std::max(t, e));
-        w += t + 2 * e;
-    }
-    return (w + 3) & ~(size_t)3;
-}
+static const char *const kNoRun = "lookup permute: more defs than HRX_MAX_DEFS, or more bins than a u32 run indexes";
 
 // the argument rules both forms share; fills `a` (but the plan and the workspace) and T_max
 static int check_permute_args(const hrx_ctx *ctx, const uint32_t *counts, size_t b_count, size_t n_rows, size_t pitch, uint32_t *a_idx, uint32_t *s_idx,
@@ -43,9 +27,11 @@ static int check_permute_args(const hrx_ctx *ctx, const uint32_t *counts, size_t
         ((uintptr_t)s_cells & 15) || ((uintptr_t)overflow & 3))
         return fail(HRX_ERR_ARG, "counts, the index columns, the table and the cells must be 16-byte aligned, overflow 4-byte");
     a = PermuteArgs{};
-    const size_t W = permute_cols_of(ctx->s, a.col, T_max);
-    if (W == 0) return fail(HRX_ERR_ARG, "lookup permute: more defs than HRX_MAX_DEFS, or more bins than a u32 run indexes");
-    const size_t ncols = 3 * ctx->s.defs.size();
+    LookupRun run;
+    if (!defs_lookup_run(ctx->s, run)) return fail(HRX_ERR_ARG, kNoRun);
+    const size_t W = run.W, ncols = 3 * (size_t)run.D;
+    T_max = run.T_max;
+    for (uint32_t c = 0; c < ncols; ++c) a.col[c] = lookup_run_col(run, c);
     if (overflow && ncols > kPmMaxOverflowCols) return fail(HRX_ERR_ARG, "overflow: a word has bits for 32 lookups (10 defs)");
     if (table_cells && table_stride != 0 && table_stride != 4 * W) return fail(HRX_ERR_ARG, "table_stride: 4 W (one run per string) or 0 (one for the call)");
     if (n_rows < T_max || n_rows > kPmMaxRows) return fail(HRX_ERR_ARG, "n_rows: at least the rows of every table of the defs, at most 2^24");
@@ -62,17 +48,15 @@ extern "C" {
 
 size_t hrx_lookup_permute_workspace_bytes(const hrx_defs *defs, size_t b_count, size_t n_rows) {
     if (!defs || defs->s.defs.empty()) return 0;
-    size_t T_max;
-    const size_t W = permute_cols_of(defs->s, nullptr, T_max);
-    return W ? plan_permute(T_max, W, 3 * defs->s.defs.size(), b_count, n_rows, 0).workspace_bytes : 0;
+    LookupRun run;
+    return defs_lookup_run(defs->s, run) ? plan_permute(run.T_max, run.W, 3 * (size_t)run.D, b_count, n_rows, 0).workspace_bytes : 0;
 }
 
 int hrx_ctx_lookup_permute_plan(hrx_ctx *ctx, size_t b_count, size_t n_rows, size_t *tile_rows, size_t *chunk_rows, size_t *group_rows, size_t *groups) {
     if (!ctx || !tile_rows || !chunk_rows || !group_rows || !groups) return fail(HRX_ERR_ARG, "NULL argument");
-    size_t T_max;
-    const size_t W = permute_cols_of(ctx->s, nullptr, T_max);
-    if (W == 0) return fail(HRX_ERR_ARG, "lookup permute: more defs than HRX_MAX_DEFS, or more bins than a u32 run indexes");
-    const PermutePlan p = plan_permute(T_max, W, 3 * ctx->s.defs.size(), b_count, n_rows, ctx->num_cus);
+    LookupRun run;
+    if (!defs_lookup_run(ctx->s, run)) return fail(HRX_ERR_ARG, kNoRun);
+    const PermutePlan p = plan_permute(run.T_max, run.W, 3 * (size_t)run.D, b_count, n_rows, ctx->num_cus);
     *tile_rows = p.tile_rows; *chunk_rows = p.chunk_rows; *group_rows = p.group_rows; *groups = p.groups;
     return HRX_OK;
 }
@@ -93,7 +77,7 @@ int hrx_lookup_permute_device(hrx_ctx *ctx, const uint32_t *counts, size_t b_cou
     }
     if ((uint64_t)b_count * a.ncols * p.groups > 0x7fffffffull) return fail(HRX_ERR_ARG, "more workgroups than a launch has: use a smaller window");
     a.groups = p.groups; a.group_rows = p.group_rows;
-    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (int rc = check_has_device(ctx)) return rc;
     DeviceGuard guard;      // (stateless: no context scratch, no image, no lock)
     HIP_TRY(guard.set(ctx->device));
     HIP_TRY(launch_lookup_permute(a, (hipStream_t)stream));
@@ -107,12 +91,7 @@ int hrx_lookup_permute_host(hrx_ctx *ctx, const uint32_t *counts, size_t b_count
     PermuteArgs a;
     size_t T_max;
     if (int rc = check_permute_args(ctx, counts, b_count, n_rows, pitch, a_idx, s_idx, table_cells, table_stride, a_cells, s_cells, overflow, a, T_max)) return rc;
-    unsigned threads;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
-    }
-    permute_host(a, threads);
+    permute_host(a, ctx_host_threads(ctx));
     return HRX_OK;
 }
 

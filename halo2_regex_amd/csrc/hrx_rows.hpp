@@ -38,6 +38,19 @@ struct RowsIn {
     uint64_t rec_pitch, msk_pitch;                  // string-major: rows between consecutive strings
 };
 
+// A caller's rows as an entry point receives them, before any check: what check_rows (hrx_rows_api.cpp) makes a RowsIn of.  records or planes / n_planes,
+// the other NULL / 0; masked NULL and msk_pitch 0 where the reader has no masked rows; a pitch of 0: M
+struct RowsCall {
+    int layout;
+    const uint8_t *chars;
+    size_t stride;
+    const uint32_t *lens, *records;
+    const uint32_t *const *planes;
+    size_t n_planes, rec_pitch;
+    const uint16_t *masked;
+    size_t msk_pitch, B, M;
+};
+
 // the record form: a template parameter of the kernels, a run-time value (rows_form) of the host readers
 enum : int { kRecSm = 0, kRecPm = 1, kRecPlanes = 2 };
 HRX_XHD int rows_form(const RowsIn &a) { return !(a.layout & HRX_LAYOUT_POSITION_MAJOR) ? kRecSm : a.records ? kRecPm : kRecPlanes; }

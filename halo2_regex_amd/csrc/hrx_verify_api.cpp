@@ -21,28 +21,27 @@ static_assert(kVfyFirstState == HRX_VERIFY_FIRST_STATE && kVfyEnable == HRX_VERI
               "hrx_verify.hpp and include/hrx.h");
 
 // the argument rules the forms share: check_rows' (hrx_rows_api.cpp) for the rows, and the verdict's; fills `a` but image
-static int check_verify_args(const hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
-                             const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M,
-                             uint64_t *verdict, bool device, VerifyArgs &a) {
-    if (!masked || !verdict) return fail(HRX_ERR_ARG, "NULL buffer");
+static int check_verify_args(const hrx_ctx *ctx, const RowsCall &c, uint64_t *verdict, bool device, VerifyArgs &a) {
+    if (!c.masked || !verdict) return fail(HRX_ERR_ARG, "NULL buffer");
     if ((uintptr_t)verdict & 7) return fail(HRX_ERR_ARG, "verdict must be 8-byte aligned");
     a = VerifyArgs{};
-    if (int rc = check_rows(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, masked, msk_pitch, B, M, device, a)) return rc;
+    if (int rc = check_rows(ctx, c, device, a)) return rc;
     a.verdict = verdict;
     return HRX_OK;
 }
 
-static int verify_image_host(hrx_ctx *ctx) { return ctx_image_host(ctx, ctx->verify_img, build_verify_image, "verify"); }
+static int verify_image_host(hrx_ctx *ctx) {
+    std::lock_guard<std::mutex> lk(ctx->mu);
+    return ctx_image_host(ctx, ctx->verify_img, build_verify_image, "verify");
+}
 static int verify_image_device(hrx_ctx *ctx, void *stream) { return ctx_image_device(ctx, ctx->verify_img, build_verify_image, "verify", stream); }
 
-static int verify_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
-                             const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B, size_t M,
-                             uint64_t *verdict, void *stream) {
+static int verify_device_any(hrx_ctx *ctx, const RowsCall &c, uint64_t *verdict, void *stream) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
-    if (B == 0) return HRX_OK;
+    if (c.B == 0) return HRX_OK;
     VerifyArgs a;
-    if (int rc = check_verify_args(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, masked, msk_pitch, B, M, verdict, true, a)) return rc;
-    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (int rc = check_verify_args(ctx, c, verdict, true, a)) return rc;
+    if (int rc = check_has_device(ctx)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
@@ -61,13 +60,13 @@ static int resolve_chunk_rows(const hrx_ctx *ctx, size_t B, size_t M, size_t chu
     return HRX_OK;
 }
 
-static int verify_chunked_device_any(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records,
-                                     const uint32_t *const *planes, size_t n_planes, size_t rec_pitch, const uint16_t *masked, size_t msk_pitch, size_t B,
-                                     size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes, uint64_t *verdict, void *stream) {
+static int verify_chunked_device_any(hrx_ctx *ctx, const RowsCall &c, size_t chunk_rows, void *workspace, size_t workspace_bytes, uint64_t *verdict,
+                                     void *stream) {
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
+    const size_t B = c.B, M = c.M;
     if (B == 0) return HRX_OK;
     VerifyChunkArgs ca{};
-    if (int rc = check_verify_args(ctx, layout, chars, stride, lens, records, planes, n_planes, rec_pitch, masked, msk_pitch, B, M, verdict, true, ca.a)) return rc;
+    if (int rc = check_verify_args(ctx, c, verdict, true, ca.a)) return rc;
     if (int rc = resolve_chunk_rows(ctx, B, M, chunk_rows, ca.chunk_rows)) return rc;
     ca.K = verify_chunk_count(ca.a.M, ca.chunk_rows);
     if (!workspace || ((uintptr_t)workspace & 15)) return fail(HRX_ERR_ARG, "workspace must be 16-byte aligned and not NULL");
@@ -75,7 +74,7 @@ static int verify_chunked_device_any(hrx_ctx *ctx, int layout, const uint8_t *ch
         return fail(HRX_ERR_ARG, "workspace smaller than hrx_verify_chunked_workspace_bytes(B, M, chunk_rows)");
     if ((B + 63) / 64 * (size_t)ca.K > 0x7fffffffull) return fail(HRX_ERR_ARG, "more (64 strings, chunk) pairs than a launch has workgroups: use larger chunks");
     ca.summaries = (uint32_t *)workspace;
-    if (ctx->device == HRX_DEVICE_NONE) return fail(HRX_ERR_HIP, "host-only context (HRX_DEVICE_NONE): no device to launch on");
+    if (int rc = check_has_device(ctx)) return rc;
     std::lock_guard<std::mutex> lk(ctx->mu);
     DeviceGuard guard;
     HIP_TRY(guard.set(ctx->device));
@@ -89,13 +88,13 @@ extern "C" {
 
 int hrx_verify_rows_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
                            const uint16_t *masked, size_t msk_pitch, size_t B, size_t M, uint64_t *verdict, void *stream) {
-    return verify_device_any(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M, verdict, stream);
+    return verify_device_any(ctx, RowsCall{layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M}, verdict, stream);
 }
 
 int hrx_verify_rows_device_planes(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *const *record_planes,
                                   size_t n_planes, const uint16_t *masked, size_t B, size_t M, uint64_t *verdict, void *stream) {
     if (!record_planes) return fail(HRX_ERR_ARG, "NULL buffer");
-    return verify_device_any(ctx, layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, masked, 0, B, M, verdict, stream);
+    return verify_device_any(ctx, RowsCall{layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, masked, 0, B, M}, verdict, stream);
 }
 
 int hrx_verify_rows_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
@@ -103,15 +102,11 @@ int hrx_verify_rows_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t 
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (B == 0) return HRX_OK;
     VerifyArgs a;
-    if (int rc = check_verify_args(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M, verdict, false, a)) return rc;
-    unsigned threads;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (int rc = verify_image_host(ctx)) return rc;
-        threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
-    }
+    const RowsCall c{layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M};
+    if (int rc = check_verify_args(ctx, c, verdict, false, a)) return rc;
+    if (int rc = verify_image_host(ctx)) return rc;
     a.image = ctx->verify_img.host.data();       // (never rebuilt once it is there)
-    verify_rows_host(a, threads);
+    verify_rows_host(a, ctx_host_threads(ctx));
     return HRX_OK;
 }
 
@@ -125,7 +120,7 @@ size_t hrx_ctx_verify_chunk_rows(hrx_ctx *ctx, size_t B, size_t M) {
 int hrx_verify_rows_chunked_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
                                    const uint16_t *masked, size_t msk_pitch, size_t B, size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes,
                                    uint64_t *verdict, void *stream) {
-    return verify_chunked_device_any(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M, chunk_rows, workspace,
+    return verify_chunked_device_any(ctx, RowsCall{layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M}, chunk_rows, workspace,
                                      workspace_bytes, verdict, stream);
 }
 
@@ -133,8 +128,8 @@ int hrx_verify_rows_chunked_device_planes(hrx_ctx *ctx, int layout, const uint8_
                                           size_t n_planes, const uint16_t *masked, size_t B, size_t M, size_t chunk_rows, void *workspace, size_t workspace_bytes,
                                           uint64_t *verdict, void *stream) {
     if (!record_planes) return fail(HRX_ERR_ARG, "NULL buffer");
-    return verify_chunked_device_any(ctx, layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, masked, 0, B, M, chunk_rows, workspace, workspace_bytes,
-                                     verdict, stream);
+    return verify_chunked_device_any(ctx, RowsCall{layout, chars, stride, lens, nullptr, record_planes, n_planes, 0, masked, 0, B, M}, chunk_rows, workspace,
+                                     workspace_bytes, verdict, stream);
 }
 
 int hrx_verify_rows_chunked_host(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,
@@ -142,15 +137,11 @@ int hrx_verify_rows_chunked_host(hrx_ctx *ctx, int layout, const uint8_t *chars,
     if (!ctx) return fail(HRX_ERR_ARG, "NULL ctx");
     if (B == 0) return HRX_OK;
     VerifyArgs a;
-    if (int rc = check_verify_args(ctx, layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M, verdict, false, a)) return rc;
+    const RowsCall c{layout, chars, stride, lens, records, nullptr, 0, rec_pitch, masked, msk_pitch, B, M};
+    if (int rc = check_verify_args(ctx, c, verdict, false, a)) return rc;
     uint32_t C;
     if (int rc = resolve_chunk_rows(ctx, B, M, chunk_rows, C)) return rc;
-    unsigned threads;
-    {
-        std::lock_guard<std::mutex> lk(ctx->mu);
-        if (int rc = verify_image_host(ctx)) return rc;
-        threads = ctx->host_threads > 0 ? (unsigned)ctx->host_threads : 0u;
-    }
+    if (int rc = verify_image_host(ctx)) return rc;
     a.image = ctx->verify_img.host.data();
     std::vector<uint32_t> summaries;      // (the device form's workspace; here the call's own)
     try {
@@ -158,7 +149,7 @@ int hrx_verify_rows_chunked_host(hrx_ctx *ctx, int layout, const uint8_t *chars,
     } catch (const std::bad_alloc &) {
         return fail(HRX_ERR_BOUNDS, "verify: no memory for the chunk summaries: use larger chunks");
     }
-    verify_rows_chunked_host(a, C, summaries.data(), threads);
+    verify_rows_chunked_host(a, C, summaries.data(), ctx_host_threads(ctx));
     return HRX_OK;
 }
 

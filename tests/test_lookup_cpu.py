@@ -12,7 +12,7 @@ import halo2_regex_amd as hra
 from halo2_regex_amd import synth
 from lookup_ref import LookupRef
 from oracle_lib import OracleDefs, ROOT
-from test_match_cpu import CFG_1, CFG_A, CFG_3, CFG_H4, _cfg
+from test_match_cpu import CFG_1, CFG_A, CFG_3, CFG_23, CFG_H4, _cfg
 
 CFG_123 = CFG_A + CFG_3
 LOOKUP_BITS = hra.VERIFY_TRANSITION | hra.VERIFY_START_LOOKUP | hra.VERIFY_END_LOOKUP
@@ -254,6 +254,50 @@ def test_permuted_lookup_columns_on_real_counts():
         hra.permuted_lookup_columns(3000, np.zeros(3000, np.uint32), 2999)
     A, S = hra.permuted_lookup_columns(3, [0, 2, 1], 3)             # no padding at all: row 0 is never looked up
     assert A.tolist() == [1, 1, 2] and sorted(S.tolist()) == [0, 1, 2] and S[0] == 1 and S[2] == 2
+
+
+def test_the_stages_agree_on_the_run_layout():
+    """counts, compress and permute read one layout of a string's run (csrc/hrx_lookup_run.hpp): two host-only contexts alive at once — one def, two defs —
+    used alternately; the layout's slices tile the unpadded run in the order trans, start, end with load()'s row counts, the compressed table has
+    lookup_words() cells per run and zero cells at the pad words alone, and every index lookup_permute_host gives lies in its lookup's slice"""
+    M = 16
+    cfgs = [_cfg(CFG_1, M), _cfg(CFG_23, M)]
+    chars, lens = small_batch(M)
+    pick = [2, 4, 6]                                        # n = 1, M - 1, M
+    chars, lens = np.ascontiguousarray(chars[pick]), lens[pick]
+    assert lens.tolist() == [1, M - 1, M]
+    theta = np.array([7, 0, 0, 0], np.uint64)               # canonical: the cell of (a0, a1, a2, a3) is the integer 343 a0 + 49 a1 + 7 a2 + a3
+    lays, counts, used = {}, {}, {}
+    for step in ("layout", "table", "counts", "permute"):
+        for i, cfg in enumerate(cfgs):
+            W = cfg.lookup_words()
+            if step == "layout":
+                lay, rows, at = cfg.lookup_layout(), cfg.load(), 0
+                assert W % 4 == 0 and len(lay) == cfg.num_defs == len(rows)
+                for d in range(cfg.num_defs):
+                    for name, n in (("trans", len(rows[d][0])), ("start", len(rows[d][1])), ("end", len(rows[d][1]))):
+                        assert lay[d][name] == slice(at, at + n), (i, d, name)
+                        at += n
+                assert at <= W < at + 4
+                lays[i], used[i] = lay, at
+            elif step == "table":
+                cells = cfg.lookup_compress_table_host(theta, canonical=True)
+                assert cells.shape == (1, W, 4)
+                zero = ~cells[0].any(axis=1)
+                assert not zero[:used[i]].any() and zero[used[i]:].all()
+            elif step == "counts":
+                rec, msk, st = cfg.witness_batch_host(chars, lens)
+                counts[i], misses = cfg.lookup_counts_host(chars, lens, rec)
+                assert counts[i].shape == (3, W) and not counts[i][:, used[i]:].any()
+            else:
+                n_rows = max(sl.stop - sl.start for lay in lays[i] for sl in lay.values()) + 1
+                res = cfg.lookup_permute_host(counts[i], n_rows)
+                assert not res["overflow"].any()
+                for d, lay in enumerate(lays[i]):
+                    for k, name in enumerate(("trans", "start", "end")):
+                        for key in ("a_idx", "s_idx"):
+                            v = res[key][3 * d + k, :, :n_rows]
+                            assert (v >= lay[name].start).all() and (v < lay[name].stop).all(), (i, d, name, key)
 
 
 def test_standalone_program_under_the_sanitizers(tmp_path):

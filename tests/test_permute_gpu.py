@@ -276,6 +276,42 @@ def test_capture_replay_as_the_first_call_of_a_fresh_context_and_a_side_stream()
     assert np.array_equal(got["s_cells"][:, :, :n_rows], want["s_cells"][:, :, :n_rows])
 
 
+def test_the_chain_of_stages_on_two_contexts_used_alternately():
+    """witness_batch -> lookup_counts -> lookup_compress_table -> lookup_permute on two device contexts alive at once (one def, two defs), stage by stage in
+    turn on the current stream: every stage reads the run's one layout (csrc/hrx_lookup_run.hpp), every output word is the host form's on the same rows"""
+    M, B = 16, 3
+    cfgs = [hra.RegexVerifyConfig.configure(M, defs_of_files(names), device=0) for names in (CFG_1, CFG_23)]
+    chars, lens = batch(B, M, seed=5)
+    d_chars, d_lens = torch.from_numpy(chars).to(DEV), torch.from_numpy(lens.astype(np.int32)).to(DEV)
+    theta = thetas_for(8, seed=8)[0][7]
+    d_theta = on_device(theta)
+    rows, d_counts, d_table, res = {}, {}, {}, {}
+    for step in range(4):
+        for i, cfg in enumerate(cfgs):
+            if step == 0:
+                rows[i] = cfg.witness_batch(d_chars, d_lens)
+            elif step == 1:
+                d_counts[i] = cfg.lookup_counts(d_chars, d_lens, rows[i][0])
+            elif step == 2:
+                d_table[i] = cfg.lookup_compress_table(d_theta)
+            else:
+                res[i] = cfg.lookup_permute(d_counts[i][0], t_max(cfg) + 1, table=d_table[i][0])
+    torch.cuda.synchronize()
+    for i, cfg in enumerate(cfgs):
+        W, n_rows = cfg.lookup_words(), t_max(cfg) + 1
+        rec = rows[i][0].cpu().numpy().view(np.uint32)
+        counts, misses = cfg.lookup_counts_host(chars, lens, rec)
+        assert np.array_equal(d_counts[i][0].cpu().numpy().view(np.uint32), counts) and np.array_equal(d_counts[i][1].cpu().numpy().view(np.uint32), misses)
+        table = cfg.lookup_compress_table_host(theta)
+        assert table.shape == (1, W, 4) and np.array_equal(d_table[i].cpu().numpy().view(np.uint64), table)
+        want = cfg.lookup_permute_host(counts, n_rows, table=table[0])
+        assert set(res[i]) == set(want) == {"a_idx", "s_idx", "a_cells", "s_cells", "overflow"}
+        for k in want:
+            got = res[i][k].cpu().numpy().view(want[k].dtype)
+            assert np.array_equal(got if k == "overflow" else got[:, :, :n_rows], want[k] if k == "overflow" else want[k][:, :, :n_rows]), (i, k)
+        assert not want["overflow"].any()
+
+
 def test_refused_calls_write_nothing_and_a_host_only_context():
     M = 19
     cfg = hra.RegexVerifyConfig.configure(M, defs_of_files(CFG_23), device=0)

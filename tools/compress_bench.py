@@ -10,8 +10,8 @@ the tool stops otherwise.
 Nobody has measured such a kernel here and no threshold is set.  In the same run, on the same rows, the two yardsticks that exist without it are timed:
 hrx_fr_columns_device, as bytes of cells written per second (the same store pattern without a fold), and the host twin's wall time on 16 threads.  Per shape:
 us per call; the fraction of 8 TB/s over the algorithmic bytes, rows x (1 + 4 D) read plus 32 x 3 D per row written; the ratio of the cell byte rates; the
-ratio to the host twin.  --json FILE: the figures as a JSON list (profiles/compress_bench.json); --label: which kernel variant the library under
-HRX_LIB_PATH holds."""
+ratio to the host twin.  --json FILE: the figures as a JSON list (profiles/compress_bench.json); --label: the name the figures carry, for runs
+that compare two libraries through HRX_LIB_PATH."""
 import argparse
 import json
 import os

@@ -10,7 +10,8 @@ out, HRX_OPT_HOST_THREADS = 16); the tool stops otherwise.  The host twin's wall
 
 Nobody has measured such a kernel here and no threshold is set.  Per shape and mode: us; the fraction of 8 TB/s over the algorithmic bytes — per lookup 4 T
 read, 8 n_rows written, 64 n_rows more with cells; the byte rate of the cells against that of hrx_fr_columns_device on the same rows in the same run; the
-ratio to the host twin.  --json FILE: the figures as a JSON list (profiles/permute_bench.json); --label: which mapping the library under HRX_LIB_PATH holds."""
+ratio to the host twin.  --json FILE: the figures as a JSON list (profiles/permute_bench.json); --label: the name the figures carry, for runs that compare two
+libraries through HRX_LIB_PATH."""
 import argparse
 import json
 import os
