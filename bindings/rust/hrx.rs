@@ -275,6 +275,23 @@ extern "C" {
                                    table_cells: *const u64, table_stride: usize, a_cells: *mut u64, s_cells: *mut u64, overflow: *mut u32) -> c_int;
     pub fn hrx_ctx_lookup_permute_plan(ctx: *mut hrx_ctx, b_count: usize, n_rows: usize, tile_rows: *mut usize, chunk_rows: *mut usize,
                                        group_rows: *mut usize, groups: *mut usize) -> c_int;
+    /// LOOKUP PRODUCT: the inverse tables 1 / (S + shift) of compressed table runs [n_runs][W][4] (zeros stay zero, pad words zero), and the grand product
+    /// Z [3 D][b_count][z_pitch][4] of the lookup argument — entries [0, n_rows] written — out of LOOKUP COMPRESS's input cells, LOOKUP PERMUTE's index
+    /// columns, the table and its two inverse tables; open: bit 3 d + k where Z[n_rows] != 1
+    pub fn hrx_lookup_invert_workspace_bytes(defs: *const hrx_defs, n_runs: usize) -> usize;
+    pub fn hrx_lookup_invert_table_device(ctx: *mut hrx_ctx, table_cells: *const u64, n_runs: usize, shift: *const u64, shift_stride: usize, inv_cells: *mut u64,
+                                          flags: c_int, workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_invert_table_host(ctx: *mut hrx_ctx, table_cells: *const u64, n_runs: usize, shift: *const u64, shift_stride: usize, inv_cells: *mut u64,
+                                        flags: c_int) -> c_int;
+    pub fn hrx_lookup_product_device(ctx: *mut hrx_ctx, lens: *const u32, m: usize, b_begin: usize, b_count: usize, in_cells: *const u64, a_idx: *const u32,
+                                     s_idx: *const u32, n_rows: usize, idx_pitch: usize, table_cells: *const u64, inv_beta: *const u64, inv_gamma: *const u64,
+                                     table_stride: usize, beta: *const u64, gamma: *const u64, challenge_stride: usize, z: *mut u64, z_pitch: usize,
+                                     open: *mut u32, flags: c_int, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_product_host(ctx: *mut hrx_ctx, lens: *const u32, m: usize, b_begin: usize, b_count: usize, in_cells: *const u64, a_idx: *const u32,
+                                   s_idx: *const u32, n_rows: usize, idx_pitch: usize, table_cells: *const u64, inv_beta: *const u64, inv_gamma: *const u64,
+                                   table_stride: usize, beta: *const u64, gamma: *const u64, challenge_stride: usize, z: *mut u64, z_pitch: usize,
+                                   open: *mut u32, flags: c_int) -> c_int;
+    pub fn hrx_ctx_lookup_product_plan(ctx: *mut hrx_ctx, b_count: usize, n_rows: usize, tile_rows: *mut usize, rows_per_lane: *mut usize) -> c_int;
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

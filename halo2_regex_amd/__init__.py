@@ -165,6 +165,12 @@ def _load():
         "hrx_lookup_permute_device": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp, vp, sz, vp]),
         "hrx_lookup_permute_host": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, vp, vp, vp]),
         "hrx_ctx_lookup_permute_plan": (i, [vp, sz, sz] + [C.POINTER(sz)] * 4),
+        "hrx_lookup_invert_workspace_bytes": (sz, [vp, sz]),
+        "hrx_lookup_invert_table_device": (i, [vp, vp, sz, vp, sz, vp, i, vp, sz, vp]),
+        "hrx_lookup_invert_table_host": (i, [vp, vp, sz, vp, sz, vp, i]),
+        "hrx_lookup_product_device": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i, vp]),
+        "hrx_lookup_product_host": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i]),
+        "hrx_ctx_lookup_product_plan": (i, [vp, sz, sz] + [C.POINTER(sz)] * 2),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -1608,6 +1614,118 @@ class RegexVerifyConfig:
         if overflow or "overflow" in given:
             ov = buf("overflow", (b_count,), u32)
         _check(call(b_count, pitch, a_idx, s_idx, table, 4 * W if table is not None and len(table.shape) == 3 else 0, a_cells, s_cells, ov))
+        return res
+
+    def lookup_invert_workspace_bytes(self, n_runs):
+        """hrx_lookup_invert_workspace_bytes: the device workspace of a lookup_invert_table call (0 in this build: a run is inverted inside one workgroup)"""
+        return int(lib.hrx_lookup_invert_workspace_bytes(self._defs.h, int(n_runs)))
+
+    def lookup_invert_table(self, table, shift, out=None, canonical=False, workspace=None, stream=None):
+        """hrx_lookup_invert_table_device: 1 / (S + shift) for every cell of lookup_compress_table's runs (include/hrx.h LOOKUP PRODUCT): table int64 CUDA limbs
+        (n_runs, W, 4) or (W, 4); shift int64 CUDA limbs (n_runs, 4) — one per run — or (4,) — one for the call.  Returns int64 limbs of table's shape: the zero
+        cell where S + shift is zero and in the pad words.  Montgomery limbs in and out unless canonical.  workspace: an int8 CUDA tensor of
+        lookup_invert_workspace_bytes() bytes (allocated where needed and not given).  One launch, asynchronous on `stream` (default: torch's current stream),
+        capturable from the first call."""
+        W = self.lookup_words()
+        assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous()
+        if tuple(table.shape[-2:]) != (W, 4) or table.dim() not in (2, 3):
+            raise HrxError(HRX_ERR_ARG, "table: contiguous 64-bit limbs of shape [%d][4] or [n_runs][%d][4]" % (W, W))
+        n_runs = 1 if table.dim() == 2 else table.shape[0]
+        stride = _theta_stride(shift, n_runs, torch.int64)
+        out = _out_buffer(out, "out", tuple(table.shape), torch.int64, table.device)
+        ws = workspace
+        need = self.lookup_invert_workspace_bytes(n_runs)
+        if ws is None and need:
+            ws = torch.empty(need, dtype=torch.int8, device=table.device)
+        s = torch.cuda.current_stream(table.device) if stream is None else stream
+        _check(lib.hrx_lookup_invert_table_device(self._need_device(table, shift, out, ws), table.data_ptr(), n_runs, shift.data_ptr(), stride, out.data_ptr(),
+                                                  FR_CANONICAL if canonical else 0, ws.data_ptr() if ws is not None else None,
+                                                  ws.numel() if ws is not None else 0, s.cuda_stream))
+        return out
+
+    def lookup_invert_table_host(self, table, shift, out=None, canonical=False):
+        """hrx_lookup_invert_table_host: lookup_invert_table over numpy arrays — table uint64 (n_runs, W, 4) or (W, 4), shift uint64 (n_runs, 4) or (4,); the
+        definition of the inverse cells (csrc/hrx_product.hpp) over host threads"""
+        W = self.lookup_words()
+        table = np.ascontiguousarray(table, np.uint64)
+        shift = np.ascontiguousarray(shift, np.uint64)
+        if tuple(table.shape[-2:]) != (W, 4) or table.ndim not in (2, 3):
+            raise HrxError(HRX_ERR_ARG, "table: 64-bit limbs of shape [%d][4] or [n_runs][%d][4]" % (W, W))
+        n_runs = 1 if table.ndim == 2 else table.shape[0]
+        stride = _theta_stride(shift, n_runs, np.uint64)
+        out = _out_buffer(out, "out", tuple(table.shape), np.uint64)
+        _check(lib.hrx_lookup_invert_table_host(self._need_ctx(), table.ctypes.data, n_runs, shift.ctypes.data, stride, out.ctypes.data,
+                                                FR_CANONICAL if canonical else 0))
+        return out
+
+    def lookup_product_plan(self, b_count, n_rows):
+        """hrx_ctx_lookup_product_plan: how a lookup_product call cuts its work — a dict of tile_rows (entries of a Z column a workgroup takes per step) and
+        rows_per_lane (consecutive entries per lane)"""
+        v = [C.c_size_t() for _ in range(2)]
+        _check(lib.hrx_ctx_lookup_product_plan(self._need_ctx(), int(b_count), int(n_rows), *[C.byref(x) for x in v]))
+        return dict(zip(("tile_rows", "rows_per_lane"), (int(x.value) for x in v)))
+
+    def lookup_product(self, lens, in_cells, a_idx, s_idx, n_rows, table, inv_beta, inv_gamma, beta, gamma, b_begin=0, z_pitch=0, canonical=False, open=True,
+                       out=None, stream=None):
+        """hrx_lookup_product_device: the grand product Z of halo2's lookup argument for every lookup of the strings [b_begin, b_begin + b_count) (include/hrx.h
+        LOOKUP PRODUCT).  lens: the batch's int32 CUDA tensor; in_cells: lookup_compress_inputs' int64 [3 D][b_count][M][4]; a_idx, s_idx: lookup_permute's int32
+        [3 D][b_count][idx_pitch]; table, inv_beta, inv_gamma: int64 limbs, all three (W, 4) — one run for the call — or (b_count, W, 4); beta, gamma: int64
+        limbs (4,) or (b_count, 4), alike.  Returns {"z": int64 [3 D][b_count][z_pitch][4] — entries [0, n_rows] written, the others never; "open": int32
+        (b_count,), bit 3 d + k where Z[n_rows] != 1 (unless open is False)}.  z_pitch: a multiple of 4 above n_rows (0: n_rows + 1 rounded up).  `out`: a dict
+        of the caller's contiguous tensors under those names, written in place.  One launch (two with open), asynchronous on `stream` (default: torch's current
+        stream), capturable from the first call."""
+        assert lens.is_cuda and lens.dtype == torch.int32 and lens.is_contiguous()
+        s = torch.cuda.current_stream(lens.device) if stream is None else stream
+
+        def call(b_count, idx_pitch, table_stride, challenge_stride, z, zp, op):
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            return lib.hrx_lookup_product_device(self._need_device(lens, in_cells, a_idx, s_idx, table, inv_beta, inv_gamma, beta, gamma, z, op), lens.data_ptr(),
+                                                 self.max_chars_size, int(b_begin), b_count, in_cells.data_ptr(), a_idx.data_ptr(), s_idx.data_ptr(), int(n_rows),
+                                                 idx_pitch, table.data_ptr(), inv_beta.data_ptr(), inv_gamma.data_ptr(), table_stride, beta.data_ptr(),
+                                                 gamma.data_ptr(), challenge_stride, z.data_ptr(), zp, ptr(op), FR_CANONICAL if canonical else 0, s.cuda_stream)
+
+        return self._lookup_product(in_cells, a_idx, s_idx, n_rows, table, inv_beta, inv_gamma, beta, gamma, z_pitch, open, out, torch.int32, torch.int64,
+                                    lens.device, call)
+
+    def lookup_product_host(self, lens, in_cells, a_idx, s_idx, n_rows, table, inv_beta, inv_gamma, beta, gamma, b_begin=0, z_pitch=0, canonical=False, open=True,
+                            out=None):
+        """hrx_lookup_product_host: lookup_product over numpy arrays in host memory (uint32 / uint64), on a host-only or a device context — the definition of
+        Z (csrc/hrx_product.hpp) over host threads.  Entries above n_rows are never written (arrays allocated here hold zeros there)."""
+        lens = np.ascontiguousarray(lens, np.uint32)
+        in_cells, table, inv_beta, inv_gamma, beta, gamma = (np.ascontiguousarray(x, np.uint64) for x in (in_cells, table, inv_beta, inv_gamma, beta, gamma))
+        a_idx, s_idx = np.ascontiguousarray(a_idx, np.uint32), np.ascontiguousarray(s_idx, np.uint32)
+
+        def call(b_count, idx_pitch, table_stride, challenge_stride, z, zp, op):
+            return lib.hrx_lookup_product_host(self._need_ctx(), lens.ctypes.data, self.max_chars_size, int(b_begin), b_count, in_cells.ctypes.data, a_idx.ctypes.data,
+                                               s_idx.ctypes.data, int(n_rows), idx_pitch, table.ctypes.data, inv_beta.ctypes.data, inv_gamma.ctypes.data, table_stride,
+                                               beta.ctypes.data, gamma.ctypes.data, challenge_stride, z.ctypes.data, zp, op.ctypes.data if op is not None else None,
+                                               FR_CANONICAL if canonical else 0)
+
+        return self._lookup_product(in_cells, a_idx, s_idx, n_rows, table, inv_beta, inv_gamma, beta, gamma, z_pitch, open, out, np.uint32, np.uint64, None, call)
+
+    def _lookup_product(self, in_cells, a_idx, s_idx, n_rows, table, inv_beta, inv_gamma, beta, gamma, z_pitch, open, out, u32, u64, device, call):
+        """what lookup_product (torch) and lookup_product_host (numpy, device None) share: the shapes, the strides, the output buffers — the caller's or fresh
+        ones; numpy's zeroed — and the call: call(b_count, idx_pitch, table_stride, challenge_stride, z, z_pitch, open)"""
+        W, ncols, M = self.lookup_words(), 3 * self.num_defs, self.max_chars_size
+        contiguous = lambda t: t.is_contiguous() if device is not None else t.flags.c_contiguous
+        if in_cells.dtype != u64 or not contiguous(in_cells) or len(in_cells.shape) != 4 or tuple(in_cells.shape[0:1] + in_cells.shape[2:]) != (ncols, M, 4):
+            raise HrxError(HRX_ERR_ARG, "in_cells: contiguous 64-bit limbs of shape [%d][b_count][%d][4]" % (ncols, M))
+        b_count = in_cells.shape[1]
+        for name, t in (("a_idx", a_idx), ("s_idx", s_idx)):
+            if t.dtype != u32 or not contiguous(t) or len(t.shape) != 3 or tuple(t.shape[:2]) != (ncols, b_count) or tuple(t.shape) != tuple(a_idx.shape):
+                raise HrxError(HRX_ERR_ARG, "%s: contiguous 32-bit words of shape [%d][%d][idx_pitch]" % (name, ncols, b_count))
+        for name, t in (("table", table), ("inv_beta", inv_beta), ("inv_gamma", inv_gamma)):
+            if t.dtype != u64 or not contiguous(t) or tuple(t.shape) not in ((W, 4), (b_count, W, 4)) or tuple(t.shape) != tuple(table.shape):
+                raise HrxError(HRX_ERR_ARG, "%s: contiguous 64-bit limbs of shape [%d][4] or [%d][%d][4], the three alike" % (name, W, b_count, W))
+        if _theta_stride(beta, b_count, u64) != _theta_stride(gamma, b_count, u64):
+            raise HrxError(HRX_ERR_ARG, "beta and gamma: both (4,) or both (%d, 4)" % b_count)
+        n_rows, z_pitch = int(n_rows), int(z_pitch)
+        p = z_pitch if z_pitch else (n_rows + 4) & ~3
+        given = out if isinstance(out, dict) else {}
+        res = {"z": _out_buffer(given.get("z"), "z", (ncols, b_count, p, 4), u64, device, zeros=True)}
+        if open or "open" in given:
+            res["open"] = _out_buffer(given.get("open"), "open", (b_count,), u32, device, zeros=True)
+        _check(call(b_count, a_idx.shape[2], 4 * W if len(table.shape) == 3 else 0, _theta_stride(beta, b_count, u64), res["z"], z_pitch, res.get("open")))
         return res
 
     def witness_batch(self, chars, lens, out=None, stream=None):

@@ -9,7 +9,8 @@
 // q = floor(v * R / r) by at most 2, so v * R - q' * r needs at most two corrective subtractions.  Plain C++ (unsigned
 // __int128) so that hipcc compiles it for the kernel and g++/hipcc for the host-side known-answer tests.
 // Below F::from: arithmetic on elements as eight u32 limbs — fr_add, fr_mul (the Montgomery product), fr_reduce (any 256-bit value mod r), and fr_fold, the
-// fold of a lookup tuple with a challenge's powers (fr_powers) that LOOKUP COMPRESS is made of (hrx_compress.hpp).
+// fold of a lookup tuple with a challenge's powers (fr_powers) that LOOKUP COMPRESS is made of (hrx_compress.hpp); and fr_inv, the Fermat inversion LOOKUP
+// PRODUCT's inverse tables need once per run (hrx_product.hpp).
 #pragma once
 #include <stdint.h>
 
@@ -179,6 +180,52 @@ HRX_FR_UNROLL
 HRX_FR_UNROLL
     for (int i = 0; i < 8; ++i) out[i] = t[i];      // (t[8] == 0: t < 2 r)
     fr_sub_if_ge<0>(out);
+}
+
+HRX_HD bool fr_is_zero(const uint32_t (&a)[8]) { return (a[0] | a[1] | a[2] | a[3] | a[4] | a[5] | a[6] | a[7]) == 0u; }
+HRX_HD bool fr_eq(const uint32_t (&a)[8], const uint32_t (&b)[8]) {
+    uint32_t d = 0;
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) d |= a[i] ^ b[i];
+    return d == 0u;
+}
+// the Montgomery form of 1 (R), or the plain 1
+HRX_HD void fr_one(bool canonical, uint32_t (&out)[8]) {
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) out[i] = canonical ? (i == 0 ? 1u : 0u) : kFrR32[i];
+}
+
+// out = x^-1 in Montgomery form (x R -> x^-1 R), 0 -> 0: Fermat, x^(r - 2) by square-and-multiply from the top bit of the CONSTANT exponent — 253 squarings
+// and 126 products, about 380 dependent fr_mul.  The one data-dependent branch is x == 0; which steps multiply is a property of r.  Not unrolled: the
+// loop's body is two fr_mul.
+constexpr uint32_t kFrRm2_32[8] = {0xefffffffu, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};   // r - 2 (254 bits)
+constexpr uint32_t kFrR5_32[8] = {0xa17a2cefu, 0x00915951u, 0x9fd7425cu, 0xbf25f2ddu, 0xa7eeefb8u, 0xfb6cfdc4u, 0xb32c8ec9u, 0x06eaaa4fu};    // R^5 mod r
+HRX_HD void fr_inv(const uint32_t (&x)[8], uint32_t (&out)[8]) {
+    if (fr_is_zero(x)) {
+HRX_FR_UNROLL
+        for (int i = 0; i < 8; ++i) out[i] = 0u;
+        return;
+    }
+    uint32_t acc[8], t[8];
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) acc[i] = x[i];                  // bit 253 of the exponent
+#if defined(__clang__)
+#pragma nounroll
+#endif
+    for (int bit = 252; bit >= 0; --bit) {
+        fr_mul(acc, acc, t);
+        uint32_t limb = 0;                                      // limb bit / 32 of the exponent, without a variable index into a constant array
+HRX_FR_UNROLL
+        for (int i = 0; i < 8; ++i) limb = (bit >> 5) == i ? kFrRm2_32[i] : limb;
+        if ((limb >> (bit & 31)) & 1u) {
+            fr_mul(t, x, acc);
+        } else {
+HRX_FR_UNROLL
+            for (int i = 0; i < 8; ++i) acc[i] = t[i];
+        }
+    }
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) out[i] = acc[i];
 }
 
 // The fold of a lookup tuple with a challenge: out = a0 t3 + a1 t2 + a2 t1 + a3 one mod r for components a0 .. a3 below 2^16 and t3, t2, t1, one below r.

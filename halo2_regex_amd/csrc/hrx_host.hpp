@@ -194,6 +194,33 @@ class RegexVerifyConfig {
         check(hrx_verify_rows_device_planes(ctx_, layout, chars, stride, lens, record_planes, n_planes, masked, B, max_chars_size_, verdict, stream));
     }
 
+    // LOOKUP PRODUCT (include/hrx.h): the inverse tables 1 / (S + shift) of compressed table runs and the grand product Z, as the C calls are (device pointers
+    // and `stream` for the device forms, host memory for the host forms); flags: 0 or HRX_FR_CANONICAL
+    static size_t lookup_invert_workspace_bytes(const hrx_defs *defs, size_t n_runs) { return hrx_lookup_invert_workspace_bytes(defs, n_runs); }
+    void lookup_invert_table_device(const uint64_t *table_cells, size_t n_runs, const uint64_t *shift, size_t shift_stride, uint64_t *inv_cells, int flags,
+                                    void *workspace, size_t workspace_bytes, void *stream) const {
+        check(hrx_lookup_invert_table_device(ctx_, table_cells, n_runs, shift, shift_stride, inv_cells, flags, workspace, workspace_bytes, stream));
+    }
+    void lookup_invert_table_host(const uint64_t *table_cells, size_t n_runs, const uint64_t *shift, size_t shift_stride, uint64_t *inv_cells, int flags) const {
+        check(hrx_lookup_invert_table_host(ctx_, table_cells, n_runs, shift, shift_stride, inv_cells, flags));
+    }
+    void lookup_product_device(const uint32_t *lens, size_t b_begin, size_t b_count, const uint64_t *in_cells, const uint32_t *a_idx, const uint32_t *s_idx,
+                               size_t n_rows, size_t idx_pitch, const uint64_t *table_cells, const uint64_t *inv_beta, const uint64_t *inv_gamma, size_t table_stride,
+                               const uint64_t *beta, const uint64_t *gamma, size_t challenge_stride, uint64_t *z, size_t z_pitch, uint32_t *open, int flags,
+                               void *stream) const {
+        check(hrx_lookup_product_device(ctx_, lens, max_chars_size_, b_begin, b_count, in_cells, a_idx, s_idx, n_rows, idx_pitch, table_cells, inv_beta, inv_gamma,
+                                        table_stride, beta, gamma, challenge_stride, z, z_pitch, open, flags, stream));
+    }
+    void lookup_product_host(const uint32_t *lens, size_t b_begin, size_t b_count, const uint64_t *in_cells, const uint32_t *a_idx, const uint32_t *s_idx,
+                             size_t n_rows, size_t idx_pitch, const uint64_t *table_cells, const uint64_t *inv_beta, const uint64_t *inv_gamma, size_t table_stride,
+                             const uint64_t *beta, const uint64_t *gamma, size_t challenge_stride, uint64_t *z, size_t z_pitch, uint32_t *open, int flags) const {
+        check(hrx_lookup_product_host(ctx_, lens, max_chars_size_, b_begin, b_count, in_cells, a_idx, s_idx, n_rows, idx_pitch, table_cells, inv_beta, inv_gamma,
+                                      table_stride, beta, gamma, challenge_stride, z, z_pitch, open, flags));
+    }
+    void lookup_product_plan(size_t b_count, size_t n_rows, size_t *tile_rows, size_t *rows_per_lane) const {
+        check(hrx_ctx_lookup_product_plan(ctx_, b_count, n_rows, tile_rows, rows_per_lane));
+    }
+
    private:
     static std::vector<std::vector<uint64_t>> split(const std::vector<uint64_t> &f, size_t D, size_t len) {
         std::vector<std::vector<uint64_t>> o(D);

@@ -462,5 +462,11 @@ hipError_t launch_compress_table(const CompressTableArgs &a, hipStream_t stream)
 // words' launch (where asked for), then the columns' launch
 struct PermuteArgs;    // hrx_permute.hpp
 hipError_t launch_lookup_permute(const PermuteArgs &a, hipStream_t stream);
+// LOOKUP PRODUCT (hrx_kernel_product.hip): the rule of hrx_product.hpp — the inverse tables by batch inversion (one launch), and the grand product Z (one
+// launch, one more for the open words)
+struct InvertArgs;     // hrx_product.hpp
+struct ProductArgs;
+hipError_t launch_lookup_invert(const InvertArgs &a, hipStream_t stream);
+hipError_t launch_lookup_product(const ProductArgs &a, hipStream_t stream);
 
 }  // namespace hrx

@@ -831,6 +831,67 @@ int hrx_lookup_permute_host(hrx_ctx *ctx, const uint32_t *counts, size_t b_count
 int hrx_ctx_lookup_permute_plan(hrx_ctx *ctx, size_t b_count, size_t n_rows, size_t *tile_rows, size_t *chunk_rows, size_t *group_rows, size_t *groups);
 
 /* ------------------------------------------------------------------ */
+/* LOOKUP PRODUCT — the grand product Z of halo2's lookup argument, its denominators from inverse tables                                      */
+/* ------------------------------------------------------------------ */
+/* The last column of lookup::prover (commit_permuted, then commit_product): Z[0] = 1, Z[i + 1] = Z[i] (A[i] + beta)(S[i] + gamma) / ((A'[i] + beta)(S'[i] +
+ * gamma)).  A' and S' are table cells selected by the index columns of LOOKUP PERMUTE, so both inversions are needed per TABLE row, not per witness row:
+ * with a table of 1 / (S + beta) and one of 1 / (S + gamma) a row's term is three multiplications and two gathers, and Z is a running product.  All
+ * arithmetic is in bn256::Fr; cells are 4 u64 limbs, Montgomery by default and plain integers with HRX_FR_CANONICAL in `flags` (other bits HRX_ERR_ARG), as
+ * in LOOKUP COMPRESS; every cell written is a fully reduced element, so the device forms equal the host forms limb for limb.
+ *
+ * INVERSE TABLE (also what a logUp prover needs: m / (S + beta) directly, 1 / (A + beta) by gather).  table_cells: [n_runs][W][4] u64 as
+ * hrx_lookup_compress_table_* writes it, W = hrx_lookup_words_per_string(defs); shift: 4 u64 limbs per run, 8-byte aligned, in DEVICE memory for the device
+ * form, taken mod r first; shift_stride in u64 words: 4 — shift[4 t] belongs to run t; 0 — one for the call; anything else HRX_ERR_ARG.
+ * inv_cells: [n_runs][W][4] u64: inv[w] = (S[w] + shift)^-1, or the zero cell where S[w] + shift = 0 (halo2's batch_invert: zeros stay zero); the pad words
+ * of a run are written as zero cells.  Both cell buffers 16-byte aligned; they must not overlap.  The device form: ONE launch, a workgroup per run (batch
+ * inversion: prefix products, one Fermat inversion x^(r - 2) per run by one lane, suffix products), asynchronous on `stream`; nothing allocated, no context
+ * scratch, no atomics, deterministic; no image of the tables is read, so it is capturable from a context's first call.  workspace:
+ * hrx_lookup_invert_workspace_bytes(defs, n_runs) bytes of device memory, 256-byte aligned — 0 in this build, and NULL accepted (a build that moves the
+ * Fermat step into a launch of its own keeps the runs' totals there); a misaligned or too small one is refused.
+ *
+ * PRODUCT, for every lookup c = 3 d + k (hrx_lookup_num_columns' order) of every string b_begin + i, i < b_count, of a batch whose lengths are lens (the
+ * whole batch's array) and whose rows are M: with (off, T) the lookup's words in the string's run (hrx_lookup_layout) and rows r = 0 .. n_rows - 1,
+ *   A[r]    = in_cells' cell of row r for r < M, the lookup's dummy cell table[off] for r >= M — and where the counts leave an input out, so that A and A'
+ *             stay one multiset: with n_b == M row M - 1 of the transition and the end lookup; with n_b > M every row
+ *   S[r]    = table[off + r] for r < T, table[off] for r >= T (LOOKUP PERMUTE's padding)
+ *   term[r] = 0 where a_idx[r] or s_idx[r] lies outside [off, off + T) — LOOKUP PERMUTE's overflow pattern 0xffffffff included; no index is used as an
+ *             address before that test — else (A[r] + beta)(S[r] + gamma) inv_beta[a_idx[r]] inv_gamma[s_idx[r]]
+ *   Z[0] = 1, Z[r + 1] = Z[r] term[r]: entries [0, n_rows] of the lookup's column are written (halo2's z over the usable rows and the row of l_last);
+ *   entries above n_rows never: the blinding rows are the caller's.
+ * open: [b_count] u32 or NULL (at most 10 defs with it): bit 3 d + k is set where Z[n_rows] != 1.  A zero term keeps Z zero from there on, so a bad index or
+ * a zero denominator always ends in `open`; there is no other error path.
+ * in_cells: [3 D][b_count][M][4] u64 as hrx_lookup_compress_inputs_* writes them; a_idx, s_idx: [3 D][b_count][idx_pitch] u32 as hrx_lookup_permute_*
+ * writes them (idx_pitch: a multiple of 4, at least n_rows; 0 = n_rows rounded up); table_cells, inv_beta, inv_gamma: [runs][W][4] u64 with ONE
+ * table_stride: 0 — one run for the call; 4 W — run i belongs to string i of the window; beta, gamma: 4 u64 limbs each, as `shift` above, with
+ * challenge_stride 4 (per string of the window) or 0; n_rows: LOOKUP PERMUTE's bounds.  z: [3 D][b_count][z_pitch][4] u64; z_pitch: a multiple of 4 above
+ * n_rows (2^k to write straight into polynomial buffers); 0 = n_rows + 1 rounded up.  Cells, index columns and tables 16-byte aligned.
+ * Refused with HRX_ERR_ARG, nothing written: NULL inputs, misaligned buffers, strides other than those named, n_rows or a pitch out of range, unknown flag
+ * bits.  A host-only context: HRX_ERR_HIP for the device forms.
+ * The device form: one launch, one more with `open` (one wave per string: a word has one writer), asynchronous on `stream`; nothing allocated, no context
+ * scratch, no atomics, deterministic; capturable from a context's first call.  One workgroup serves a (string, lookup) from row 0 to n_rows: a window with
+ * fewer lookups than the device has compute units is slow, not wrong. */
+size_t hrx_lookup_invert_workspace_bytes(const hrx_defs *defs, size_t n_runs);
+int hrx_lookup_invert_table_device(hrx_ctx *ctx, const uint64_t *table_cells, size_t n_runs, const uint64_t *shift, size_t shift_stride,
+                                   uint64_t *inv_cells, int flags, void *workspace, size_t workspace_bytes, void *stream);
+int hrx_lookup_product_device(hrx_ctx *ctx, const uint32_t *lens, size_t M, size_t b_begin, size_t b_count,
+                              const uint64_t *in_cells, const uint32_t *a_idx, const uint32_t *s_idx, size_t n_rows, size_t idx_pitch,
+                              const uint64_t *table_cells, const uint64_t *inv_beta, const uint64_t *inv_gamma, size_t table_stride,
+                              const uint64_t *beta, const uint64_t *gamma, size_t challenge_stride,
+                              uint64_t *z, size_t z_pitch, uint32_t *open, int flags, void *stream);
+/* The same with everything in HOST memory, on a host-only or a device context, over HRX_OPT_HOST_THREADS threads by ranges of runs and of strings.  The
+ * definition of the cells. */
+int hrx_lookup_invert_table_host(hrx_ctx *ctx, const uint64_t *table_cells, size_t n_runs, const uint64_t *shift, size_t shift_stride,
+                                 uint64_t *inv_cells, int flags);
+int hrx_lookup_product_host(hrx_ctx *ctx, const uint32_t *lens, size_t M, size_t b_begin, size_t b_count,
+                            const uint64_t *in_cells, const uint32_t *a_idx, const uint32_t *s_idx, size_t n_rows, size_t idx_pitch,
+                            const uint64_t *table_cells, const uint64_t *inv_beta, const uint64_t *inv_gamma, size_t table_stride,
+                            const uint64_t *beta, const uint64_t *gamma, size_t challenge_stride,
+                            uint64_t *z, size_t z_pitch, uint32_t *open, int flags);
+/* How a device product call cuts its work: a workgroup walks its lookup's Z column *tile_rows entries at a time, *rows_per_lane consecutive entries per
+ * lane, one workgroup per (string, lookup) whatever the window.  For tests and tools; the cells do not depend on it. */
+int hrx_ctx_lookup_product_plan(hrx_ctx *ctx, size_t b_count, size_t n_rows, size_t *tile_rows, size_t *rows_per_lane);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */
 /* ------------------------------------------------------------------ */
 /* One circuit: EXACTLY the Vecs the three derive_* calls at the top of match_substrs return (src/lib.rs:316-318), out of the string's compact records, so that the body
