@@ -2,7 +2,7 @@
 //! `RegexVerifyConfig::match_substrs` through libhrx.so.  NOT compiled in this repository (the image has no
 //! Rust toolchain); it documents the drop-in call sites against include/hrx.h.  See INTEGRATION.md.
 #![allow(non_camel_case_types)]
-use std::ffi::{c_char, c_int, c_void, CStr};
+use std::ffi::{c_char, c_int, c_uint, c_void, CStr};
 
 #[repr(C)] pub struct hrx_defs { _p: [u8; 0] }
 #[repr(C)] pub struct hrx_ctx { _p: [u8; 0] }
@@ -292,6 +292,16 @@ extern "C" {
                                    table_stride: usize, beta: *const u64, gamma: *const u64, challenge_stride: usize, z: *mut u64, z_pitch: usize,
                                    open: *mut u32, flags: c_int) -> c_int;
     pub fn hrx_ctx_lookup_product_plan(ctx: *mut hrx_ctx, b_count: usize, n_rows: usize, tile_rows: *mut usize, rows_per_lane: *mut usize) -> c_int;
+    /// FR NTT: the transform of size 2^k over columns of bn256::Fr cells (forward, or inverse with HRX_NTT_INVERSE = 2 in flags), an optional coset shift;
+    /// the workspace holds the twiddle table of one k, written by one prepare launch
+    pub fn hrx_fr_ntt_workspace_bytes(k: c_uint) -> usize;
+    pub fn hrx_fr_ntt_prepare_device(ctx: *mut hrx_ctx, k: c_uint, workspace: *mut c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_fr_ntt_device(ctx: *mut hrx_ctx, input: *const u64, in_pitch: usize, out: *mut u64, out_pitch: usize, n_cols: usize, k: c_uint, n_in: usize,
+                             shift: *const u64, flags: c_int, workspace: *const c_void, workspace_bytes: usize, stream: *mut c_void) -> c_int;
+    pub fn hrx_fr_ntt_host(ctx: *mut hrx_ctx, input: *const u64, in_pitch: usize, out: *mut u64, out_pitch: usize, n_cols: usize, k: c_uint, n_in: usize,
+                           shift: *const u64, flags: c_int) -> c_int;
+    pub fn hrx_ctx_fr_ntt_plan(ctx: *mut hrx_ctx, n_cols: usize, k: c_uint, n_passes: *mut usize, pass_bits: *mut usize, cols_per_group: *mut usize) -> c_int;
+    pub fn hrx_fr_sub(a: *const u64, b: *const u64, out: *mut u64);
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

@@ -171,6 +171,12 @@ def _load():
         "hrx_lookup_product_device": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i, vp]),
         "hrx_lookup_product_host": (i, [vp, vp, sz, sz, sz, vp, vp, vp, sz, sz, vp, vp, vp, sz, vp, vp, sz, vp, sz, vp, i]),
         "hrx_ctx_lookup_product_plan": (i, [vp, sz, sz] + [C.POINTER(sz)] * 2),
+        "hrx_fr_ntt_workspace_bytes": (sz, [C.c_uint]),
+        "hrx_fr_ntt_prepare_device": (i, [vp, C.c_uint, vp, sz, vp]),
+        "hrx_fr_ntt_device": (i, [vp, vp, sz, vp, sz, sz, C.c_uint, sz, vp, i, vp, sz, vp]),
+        "hrx_fr_ntt_host": (i, [vp, vp, sz, vp, sz, sz, C.c_uint, sz, vp, i]),
+        "hrx_ctx_fr_ntt_plan": (i, [vp, sz, C.c_uint, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
+        "hrx_fr_sub": (None, [_u64p, _u64p, _u64p]),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -1728,6 +1734,80 @@ class RegexVerifyConfig:
         _check(call(b_count, a_idx.shape[2], 4 * W if len(table.shape) == 3 else 0, _theta_stride(beta, b_count, u64), res["z"], z_pitch, res.get("open")))
         return res
 
+    def fr_ntt_workspace_bytes(self, k):
+        """hrx_fr_ntt_workspace_bytes: the device workspace of the transforms of size 2^k (the twiddle table and 2^-k); 0 for a k out of range"""
+        return int(lib.hrx_fr_ntt_workspace_bytes(int(k)))
+
+    def fr_ntt_plan(self, n_cols, k):
+        """hrx_ctx_fr_ntt_plan: how a device transform cuts its work — a dict of n_passes, pass_bits (a list of n_passes stage counts, their sum k) and
+        cols_per_group (whole columns a workgroup takes where the call is one pass)"""
+        n, cpg, bits = C.c_size_t(), C.c_size_t(), (C.c_size_t * 3)()
+        _check(lib.hrx_ctx_fr_ntt_plan(self._need_ctx(), int(n_cols), int(k), C.byref(n), bits, C.byref(cpg)))
+        return {"n_passes": int(n.value), "pass_bits": [int(b) for b in bits[:n.value]], "cols_per_group": int(cpg.value)}
+
+    def fr_ntt_prepare(self, k, workspace=None, stream=None):
+        """hrx_fr_ntt_prepare_device: write the tables of size 2^k into `workspace` — an int8 CUDA tensor of fr_ntt_workspace_bytes(k) bytes, allocated where
+        not given — in one launch, asynchronous on `stream` (default: torch's current stream).  Returns the workspace: read-only from then on, for any
+        number of fr_ntt calls of that k."""
+        device = torch.device("cuda", self.device) if workspace is None else workspace.device
+        ws = torch.empty(max(self.fr_ntt_workspace_bytes(k), 1), dtype=torch.int8, device=device) if workspace is None else workspace
+        s = torch.cuda.current_stream(device) if stream is None else stream
+        _check(lib.hrx_fr_ntt_prepare_device(self._need_device(ws), int(k), ws.data_ptr(), ws.numel() * ws.element_size(), s.cuda_stream))
+        return ws
+
+    def fr_ntt(self, cells, k, workspace=None, out=None, inverse=False, n_in=None, shift=None, canonical=False, stream=None):
+        """hrx_fr_ntt_device: the transform of size 2^k of every column of `cells` (include/hrx.h FR NTT) — int64 CUDA limbs (n_cols, in_pitch, 4) or
+        (in_pitch, 4), entries [0, n_in) of a column read (n_in: default min(in_pitch, 2^k)), the others zero and never read.  forward:
+        y[j] = sum_i shift^i x[i] w^(i j); inverse=True: y[i] = shift^i 2^-k sum_j x[j] w^(-i j).  shift: int64 CUDA limbs (4,), or None (1).  Returns int64
+        limbs (n_cols, out_pitch, 4) (or (out_pitch, 4)): `out` if given — the caller's contiguous tensor, out_pitch >= 2^k, entries above 2^k never
+        written; `out is cells`: in place — else a fresh tensor of pitch 2^k (4 for k = 1).  Montgomery limbs unless canonical.  workspace: fr_ntt_prepare(k)'s (prepared
+        here where not given: one more launch).  Asynchronous on `stream` (default: torch's current stream), capturable from the first call."""
+        assert cells.is_cuda and cells.dtype == torch.int64 and cells.is_contiguous()
+        s = torch.cuda.current_stream(cells.device) if stream is None else stream
+        ws = self.fr_ntt_prepare(k, stream=s) if workspace is None else workspace
+
+        def call(n_cols, in_pitch, out, out_pitch, n_in, flags):
+            return lib.hrx_fr_ntt_device(self._need_device(cells, out, shift, ws), cells.data_ptr(), in_pitch, out.data_ptr(), out_pitch, n_cols, int(k), n_in,
+                                         shift.data_ptr() if shift is not None else None, flags, ws.data_ptr(), ws.numel() * ws.element_size(), s.cuda_stream)
+
+        return self._fr_ntt(cells, k, out, inverse, n_in, shift, canonical, torch.int64, cells.device, call)
+
+    def fr_ntt_host(self, cells, k, out=None, inverse=False, n_in=None, shift=None, canonical=False):
+        """hrx_fr_ntt_host: fr_ntt over numpy arrays in host memory (uint64), on a host-only or a device context — the definition of the cells
+        (csrc/hrx_ntt.hpp), an iterative radix-2 transform per column over host threads; no workspace.  Entries above 2^k of a caller's `out` are never
+        written."""
+        if out is not None and out is cells:
+            assert cells.dtype == np.uint64 and cells.flags.c_contiguous
+        else:
+            cells = np.ascontiguousarray(cells, np.uint64)
+        shift = None if shift is None else np.ascontiguousarray(shift, np.uint64)
+
+        def call(n_cols, in_pitch, out, out_pitch, n_in, flags):
+            return lib.hrx_fr_ntt_host(self._need_ctx(), cells.ctypes.data, in_pitch, out.ctypes.data, out_pitch, n_cols, int(k), n_in,
+                                       shift.ctypes.data if shift is not None else None, flags)
+
+        return self._fr_ntt(cells, k, out, inverse, n_in, shift, canonical, np.uint64, None, call)
+
+    def _fr_ntt(self, cells, k, out, inverse, n_in, shift, canonical, u64, device, call):
+        """what fr_ntt (torch) and fr_ntt_host (numpy, device None) share: the shapes, the output buffer — the caller's or a fresh one of pitch 2^k — and the
+        call: call(n_cols, in_pitch, out, out_pitch, n_in, flags)"""
+        k = int(k)
+        contiguous = lambda t: t.is_contiguous() if device is not None else t.flags.c_contiguous
+        if cells.dtype != u64 or len(cells.shape) not in (2, 3) or cells.shape[-1] != 4:
+            raise HrxError(HRX_ERR_ARG, "cells: contiguous 64-bit limbs of shape [n_cols][in_pitch][4] or [in_pitch][4]")
+        if not 1 <= k <= 24:
+            raise HrxError(HRX_ERR_ARG, "k: 1 .. 24")
+        n_cols, in_pitch = (1, cells.shape[0]) if len(cells.shape) == 2 else (cells.shape[0], cells.shape[1])
+        n_in = min(in_pitch, 1 << k) if n_in is None else int(n_in)
+        if shift is not None and (shift.dtype != u64 or not contiguous(shift) or tuple(shift.shape) != (4,)):
+            raise HrxError(HRX_ERR_ARG, "shift: contiguous 64-bit limbs of shape (4,)")
+        if out is None:
+            out = _out_buffer(None, "out", tuple(cells.shape[:-2]) + (max(1 << k, 4), 4), u64, device, zeros=True)
+        elif out.dtype != u64 or not contiguous(out) or len(out.shape) != len(cells.shape) or out.shape[-1] != 4 or tuple(out.shape[:-2]) != tuple(cells.shape[:-2]):
+            raise HrxError(HRX_ERR_ARG, "out: contiguous 64-bit limbs of shape [n_cols][out_pitch][4], as many columns as cells has")
+        _check(call(n_cols, in_pitch, out, out.shape[-2], n_in, (FR_CANONICAL if canonical else 0) | (FR_NTT_INVERSE if inverse else 0)))
+        return out
+
     def witness_batch(self, chars, lens, out=None, stream=None):
         """Device-resident batch: chars (B, stride) uint8 CUDA tensor (stride % 16 == 0), lens (B,) int32 CUDA tensor.
         Asynchronous on `stream` (default: torch's current stream).  Returns (records, masked, status) tensors whose
@@ -1810,6 +1890,18 @@ FR_COLUMN_NAMES = lambda D: (["char_enable", "characters"] + [n % d for d in ran
 
 
 FR_LOOKUP_COLUMN_NAMES = lambda D: [n % d for d in range(D) for n in ("trans[%d]", "start[%d]", "end[%d]")]      # hrx_lookup_compress_inputs_*
+
+
+FR_NTT_INVERSE = 2                     # HRX_NTT_INVERSE
+FR_S = 28                              # bn256::Fr's two-adicity (halo2curves): r - 1 = 2^28 * odd, the multiplicative generator 7
+FR_ROOT_OF_UNITY = 0x03ddb9f5166d18b798865ea93dd31f743215cf6dd39329c8d34f1ed960c37c9c      # 7^((r - 1) / 2^28), of order exactly 2^28
+
+
+def fr_sub(a, b):
+    """hrx_fr_sub: a - b mod r of two elements given as 4 little-endian u64 limbs each (of one limb form); 4 limbs"""
+    x, y, out = (C.c_uint64 * 4)(*[int(v) for v in a]), (C.c_uint64 * 4)(*[int(v) for v in b]), (C.c_uint64 * 4)()
+    lib.hrx_fr_sub(x, y, out)
+    return [int(v) for v in out]
 
 
 def fr_mul(a, b):

@@ -148,6 +148,24 @@ HRX_FR_UNROLL
     fr_sub_if_ge<0>(out);
 }
 
+// out = a - b mod r, a and b below r: the difference, and r added back where it borrowed
+HRX_HD void fr_sub(const uint32_t (&a)[8], const uint32_t (&b)[8], uint32_t (&out)[8]) {
+    uint32_t d[8], borrow = 0;
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) {
+        const uint64_t x = (uint64_t)a[i] - b[i] - borrow;
+        d[i] = (uint32_t)x;
+        borrow = (uint32_t)(x >> 32) & 1u;
+    }
+    uint64_t c = 0;
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) {
+        c += (uint64_t)d[i] + (borrow ? kFrModulus32[i] : 0u);
+        out[i] = (uint32_t)c;
+        c >>= 32;
+    }
+}
+
 // out = a * b / R mod r — the Montgomery product: of two Montgomery forms the Montgomery form of the product; of a plain integer and a Montgomery form the
 // plain product.  a, b below r.  Word-by-word (CIOS) over 32-bit limbs: per limb of b one row of a * b[i] and one of m * r that clears the lowest limb,
 // 128 v_mad_u64_u32 in all; the running value stays below 2 r < 2^255, so one subtraction finishes.
@@ -227,6 +245,34 @@ HRX_FR_UNROLL
 HRX_FR_UNROLL
     for (int i = 0; i < 8; ++i) out[i] = acc[i];
 }
+
+// out = x^e for a Montgomery form x and a plain exponent below 2^32 (x^0 = one): square-and-multiply from the lowest bit; the loop ends with e's top bit.
+HRX_HD void fr_pow_u32(const uint32_t (&x)[8], uint32_t e, uint32_t (&out)[8]) {
+    uint32_t sq[8], t[8];
+HRX_FR_UNROLL
+    for (int i = 0; i < 8; ++i) { sq[i] = x[i]; out[i] = kFrR32[i]; }
+#if defined(__clang__)
+#pragma nounroll
+#endif
+    for (; e; e >>= 1) {
+        if (e & 1u) {
+            fr_mul(out, sq, t);
+HRX_FR_UNROLL
+            for (int i = 0; i < 8; ++i) out[i] = t[i];
+        }
+        fr_mul(sq, sq, t);
+HRX_FR_UNROLL
+        for (int i = 0; i < 8; ++i) sq[i] = t[i];
+    }
+}
+
+// The two-adic subgroup, halo2curves' constants for bn256::Fr: r - 1 = 2^S * odd with S = 28, the multiplicative generator 7, and
+// ROOT_OF_UNITY = 7^((r - 1) / 2^28) = 0x03ddb9f5166d18b798865ea93dd31f743215cf6dd39329c8d34f1ed960c37c9c of order exactly 2^28 (its 2^27-th power is r - 1).
+// Both limb arrays are Montgomery forms (x R mod r).
+constexpr uint32_t kFrS = 28;
+constexpr uint64_t kFrRootOfUnity[4] = {0xd34f1ed960c37c9cull, 0x3215cf6dd39329c8ull, 0x98865ea93dd31f74ull, 0x03ddb9f5166d18b7ull};   // the plain integer
+constexpr uint32_t kFrRootOfUnity32[8] = {0xb639feb8u, 0x9632c7c5u, 0x0d0ff299u, 0x985ce340u, 0x01b0ecd8u, 0xb2dd8800u, 0x6d98ce29u, 0x1d69070du};
+constexpr uint32_t kFrInv2_32[8] = {0x1ffffffeu, 0x783c14d8u, 0x0c8d1eddu, 0xaf982f6fu, 0xfcfd4f45u, 0x8f5f7492u, 0x3d9cbfacu, 0x1f37631au};         // 1 / 2
 
 // The fold of a lookup tuple with a challenge: out = a0 t3 + a1 t2 + a2 t1 + a3 one mod r for components a0 .. a3 below 2^16 and t3, t2, t1, one below r.
 // With t_k = theta^k R mod r and one = R (kFrR32) that is the Montgomery form of a0 theta^3 + a1 theta^2 + a2 theta + a3 — halo2's

@@ -221,6 +221,20 @@ class RegexVerifyConfig {
         check(hrx_ctx_lookup_product_plan(ctx_, b_count, n_rows, tile_rows, rows_per_lane));
     }
 
+    // FR NTT (include/hrx.h): the transform of size 2^k over columns of field cells, as the C calls are; flags: HRX_FR_CANONICAL | HRX_NTT_INVERSE
+    static size_t fr_ntt_workspace_bytes(unsigned k) { return hrx_fr_ntt_workspace_bytes(k); }
+    void fr_ntt_prepare_device(unsigned k, void *workspace, size_t workspace_bytes, void *stream) const {
+        check(hrx_fr_ntt_prepare_device(ctx_, k, workspace, workspace_bytes, stream));
+    }
+    void fr_ntt_device(const uint64_t *in, size_t in_pitch, uint64_t *out, size_t out_pitch, size_t n_cols, unsigned k, size_t n_in, const uint64_t *shift, int flags,
+                       const void *workspace, size_t workspace_bytes, void *stream) const {
+        check(hrx_fr_ntt_device(ctx_, in, in_pitch, out, out_pitch, n_cols, k, n_in, shift, flags, workspace, workspace_bytes, stream));
+    }
+    void fr_ntt_host(const uint64_t *in, size_t in_pitch, uint64_t *out, size_t out_pitch, size_t n_cols, unsigned k, size_t n_in, const uint64_t *shift,
+                     int flags) const {
+        check(hrx_fr_ntt_host(ctx_, in, in_pitch, out, out_pitch, n_cols, k, n_in, shift, flags));
+    }
+
    private:
     static std::vector<std::vector<uint64_t>> split(const std::vector<uint64_t> &f, size_t D, size_t len) {
         std::vector<std::vector<uint64_t>> o(D);

@@ -468,5 +468,9 @@ struct InvertArgs;     // hrx_product.hpp
 struct ProductArgs;
 hipError_t launch_lookup_invert(const InvertArgs &a, hipStream_t stream);
 hipError_t launch_lookup_product(const ProductArgs &a, hipStream_t stream);
+// FR NTT (hrx_kernel_ntt.hip): the rule of hrx_ntt.hpp — the twiddle table of size 2^k (one launch), and the transform (ntt_plan(k).launches launches)
+struct NttArgs;        // hrx_ntt.hpp
+hipError_t launch_ntt_prepare(uint32_t k, uint32_t *ws, hipStream_t stream);
+hipError_t launch_ntt(const NttArgs &a, int device, hipStream_t stream);
 
 }  // namespace hrx

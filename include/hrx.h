@@ -892,6 +892,49 @@ int hrx_lookup_product_host(hrx_ctx *ctx, const uint32_t *lens, size_t M, size_t
 int hrx_ctx_lookup_product_plan(hrx_ctx *ctx, size_t b_count, size_t n_rows, size_t *tile_rows, size_t *rows_per_lane);
 
 /* ------------------------------------------------------------------ */
+/* FR NTT — columns of field cells to coefficients and to cosets: the transform of size 2^k over bn256::Fr                                    */
+/* ------------------------------------------------------------------ */
+/* What halo2 does next with every Lagrange column the lookup stages write — lagrange_to_coeff, coeff_to_extended, extended_to_coeff — is one batched
+ * number-theoretic transform.  The two-adic subgroup is halo2curves': S = 28, generator 7, ROOT_OF_UNITY = 7^((r - 1) / 2^28) =
+ * 0x03ddb9f5166d18b798865ea93dd31f743215cf6dd39329c8d34f1ed960c37c9c, w_k = ROOT_OF_UNITY^(2^(28 - k)).  For every column x[0 .. 2^k) of n_cols, natural
+ * order in and out:
+ *   forward (default):          y[j] = sum_i (g^i x[i]) w_k^(i j)
+ *   inverse (HRX_NTT_INVERSE):  y[i] = g^i 2^-k sum_j x[j] w_k^(-i j)
+ * g is `shift`: 4 u64 limbs in the call's limb form, 8-byte aligned, taken mod r first, in DEVICE memory for the device form; NULL: g = 1, and no
+ * multiplications are spent on it.  The call never inverts g: a forward transform with g is undone by the inverse with g^-1.
+ *   lagrange_to_coeff: inverse, no shift.  coeff_to_extended: forward at the extended k, n_in = 2^k of the column, shift = the coset generator.
+ *   extended_to_coeff: inverse with the generator's inverse.
+ * in: [n_cols][in_pitch][4] u64, entries [0, n_in) of a column are read, 1 <= n_in <= 2^k, entries [n_in, 2^k) count as zero and are NEVER read (halo2's
+ * zero extension without clearing memory); out: [n_cols][out_pitch][4] u64, entries [0, 2^k) of a column are written, entries above never.  Pitches in
+ * cells, multiples of 4, in_pitch >= n_in, out_pitch >= 2^k; both buffers 16-byte aligned.  in == out with equal pitches is the in-place form; any other
+ * overlap of the two ranges is refused.  1 <= k <= 24.  Cells are Montgomery limbs by default, plain integers with HRX_FR_CANONICAL (the transform is
+ * linear: the flag changes how `shift` is read and nothing per cell).  Every cell written is a fully reduced element: the device form equals the host form
+ * limb for limb.
+ * workspace: hrx_fr_ntt_workspace_bytes(k) bytes of device memory, 256-byte aligned, written by hrx_fr_ntt_prepare_device in ONE launch (the table
+ * w_k^e, e < 2^(k-1), each entry by square-and-multiply, and 2^-k) and read-only afterwards: it serves any number of transform calls of that k, on any
+ * streams and contexts of the device.  Nothing depends on g in it.
+ * The device form: asynchronous on `stream`; one launch for k <= 12 (a column in one workgroup's LDS, 2^(10 - k) columns per workgroup below k = 10), else
+ * one permuting launch and one per pass (hrx_ctx_fr_ntt_plan) — a fixed number given k; no atomics, nothing allocated, no context state, deterministic;
+ * capturable from a context's first call.
+ * Refused with HRX_ERR_ARG, nothing written: NULL or misaligned buffers, k, n_in or a pitch out of range, a partial overlap, unknown flag bits, a missing,
+ * misaligned or too small workspace.  A host-only context: HRX_ERR_HIP for the device forms.  n_cols == 0 launches nothing. */
+enum { HRX_NTT_INVERSE = 2 };   /* beside HRX_FR_CANONICAL in `flags` */
+size_t hrx_fr_ntt_workspace_bytes(unsigned k);   /* 0 for a k out of range */
+int hrx_fr_ntt_prepare_device(hrx_ctx *ctx, unsigned k, void *workspace, size_t workspace_bytes, void *stream);
+int hrx_fr_ntt_device(hrx_ctx *ctx, const uint64_t *in, size_t in_pitch, uint64_t *out, size_t out_pitch, size_t n_cols, unsigned k, size_t n_in,
+                      const uint64_t *shift, int flags, const void *workspace, size_t workspace_bytes, void *stream);
+/* The same with everything in HOST memory, on a host-only or a device context: an iterative radix-2 transform per column over HRX_OPT_HOST_THREADS threads
+ * by ranges of columns; it computes its own twiddles and takes no workspace.  The definition of the cells. */
+int hrx_fr_ntt_host(hrx_ctx *ctx, const uint64_t *in, size_t in_pitch, uint64_t *out, size_t out_pitch, size_t n_cols, unsigned k, size_t n_in,
+                    const uint64_t *shift, int flags);
+/* How a device call cuts its work: *n_passes passes of pass_bits[0 .. *n_passes) butterfly stages each (pass_bits: room for 3; the unused ones 0), their sum
+ * k; one pass: the call is one launch and a workgroup takes *cols_per_group whole columns; more: a permuting launch, then a launch per pass.  For tests and
+ * tools; the cells do not depend on it. */
+int hrx_ctx_fr_ntt_plan(hrx_ctx *ctx, size_t n_cols, unsigned k, size_t *n_passes, size_t *pass_bits, size_t *cols_per_group);
+/* out = a - b mod r on 4-limb values of one form, each taken mod r first (beside hrx_fr_mul: for tests and bindings) */
+void hrx_fr_sub(const uint64_t *a, const uint64_t *b, uint64_t *out);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */
 /* ------------------------------------------------------------------ */
 /* One circuit: EXACTLY the Vecs the three derive_* calls at the top of match_substrs return (src/lib.rs:316-318), out of the string's compact records, so that the body
