@@ -908,8 +908,9 @@ int hrx_ctx_lookup_product_plan(hrx_ctx *ctx, size_t b_count, size_t n_rows, siz
  * zero extension without clearing memory); out: [n_cols][out_pitch][4] u64, entries [0, 2^k) of a column are written, entries above never.  Pitches in
  * cells, multiples of 4, in_pitch >= n_in, out_pitch >= 2^k; both buffers 16-byte aligned.  in == out with equal pitches is the in-place form; any other
  * overlap of the two ranges is refused.  1 <= k <= 24.  Cells are Montgomery limbs by default, plain integers with HRX_FR_CANONICAL (the transform is
- * linear: the flag changes how `shift` is read and nothing per cell).  Every cell written is a fully reduced element: the device form equals the host form
- * limb for limb.
+ * linear: the flag changes how `shift` is read and nothing per cell).  Every input cell read must be below r — every producer in this library writes such
+ * cells; unshifted, the first butterfly adds the cells as they are, and a cell of r or more can lose a carry there — and only `shift` is reduced by the call.
+ * Every cell written is a fully reduced element: the device form equals the host form limb for limb.
  * workspace: hrx_fr_ntt_workspace_bytes(k) bytes of device memory, 256-byte aligned, written by hrx_fr_ntt_prepare_device in ONE launch (the table
  * w_k^e, e < 2^(k-1), each entry by square-and-multiply, and 2^-k) and read-only afterwards: it serves any number of transform calls of that k, on any
  * streams and contexts of the device.  Nothing depends on g in it.

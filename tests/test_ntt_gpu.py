@@ -1,7 +1,12 @@
 """FR NTT on the device (include/hrx.h hrx_fr_ntt_prepare_device / hrx_fr_ntt_device; csrc/hrx_kernel_ntt.hip) against the host twin, every limb, every buffer
 between poisoned guards:
   sizes                every k from 1 to two past the plan's largest one-pass k (every packing factor, the whole-LDS tile, the first multi-pass sizes and a
-                       one-bit pass), then the smallest and the largest k <= 20 of every further pass count, one column
+                       one-bit pass), then every k to 20 — the smallest and the largest of every further pass count, and the sizes between those — one
+                       column, forward with a short input and, shifted, inverse in place: every width of a last strided pass
+  three passes         the smallest such k: 3 columns with in_pitch != out_pitch and n_in = 2^k - 1, the in-place pair swap of 2 columns with n_in = 2^(k-2),
+                       inverse canonical at a wider out_pitch
+  the largest sizes    k = 21 .. 24, no host transform of that size: the transform of 2^20 entries coset by coset against 2^(k-20) transforms of size 2^20,
+                       a dense column forward and back in place, Python integers at about 40 outputs around every pass border
   columns              1, cols_per_group - 1, cols_per_group, cols_per_group + 1, 5 at a packed and an unpacked k
   argument forms       both directions and limb forms, with and without a shift, n_in in {1, 2^k - 1, 2^(k-2), 2^k} with the unread input poisoned on
                        the device, in place and out of place, in_pitch != out_pitch
@@ -9,6 +14,7 @@ between poisoned guards:
   the chain            regex1's A', S', Z columns written at pitch 4096 by the device stages, to coefficients in place (Horner in Python integers), then to
                        the extended coset at k = 14
   contract             capture and replay as a fresh context's first calls, a side stream, two contexts in turn, every refusal with nothing written"""
+import contextlib
 import gc
 
 import numpy as np
@@ -52,6 +58,7 @@ def release_the_shared_context():
     modules count on starting without one"""
     yield
     _WS.clear()
+    _BIG.clear()
     _CFG.clear()
     gc.collect()
 
@@ -93,15 +100,18 @@ def shift_of(g, canonical):
     return None if g is None else np.array(cell_limbs(g, canonical), np.uint64)
 
 
-def same_as_host(k, n_cols, n_in=None, inverse=False, canonical=False, g=None, in_place=False, out_pitch=None, in_pitch=None, seed=1, cfg=None, stream=None, ws=None):
-    """one device call between guards against the host twin on the same cells; returns the output cells [n_cols][2^k][4]"""
+def same_as_host(k, n_cols, n_in=None, inverse=False, canonical=False, g=None, in_place=False, out_pitch=None, in_pitch=None, seed=1, cfg=None, stream=None, ws=None,
+                 cells=None, shift=None):
+    """one device call between guards against the host twin on the same cells; returns the output cells [n_cols][2^k][4]
+    (cells: the caller's [n_cols][in_pitch][4] in place of seeded ones; shift: the shift's limbs as they are, reduced or not, in place of g's)"""
     cfg = cfg or dev_cfg()
     n = 1 << k
     n_in = n if n_in is None else n_in
     out_pitch = out_pitch or max(n, 4)
     in_pitch = out_pitch if in_place else (in_pitch or (n_in + 3) & ~3)
-    cells = columns(n_cols, n_in, in_pitch, seed, canonical)
-    shift = shift_of(g, canonical)
+    cells = columns(n_cols, n_in, in_pitch, seed, canonical) if cells is None else cells
+    assert cells.shape == (n_cols, in_pitch, 4) and cells.dtype == np.uint64
+    shift = shift_of(g, canonical) if shift is None else shift
     want = _HOST.fr_ntt_host(cells, k, inverse=inverse, n_in=n_in, shift=shift, canonical=canonical)
     raw_in, d_in = guarded(cells.size, torch.int64)
     d_in = d_in.view(n_cols, in_pitch, 4)
@@ -138,18 +148,57 @@ def test_every_size_up_to_two_past_the_one_pass_limit(k):
     assert workspaces_unchanged()
 
 
-@pytest.mark.parametrize("k", further_pass_sizes())
-def test_smallest_and_largest_size_of_every_further_pass_count(k):
+def extension_and_inverse_in_place(k):
     assert plan(k)["n_passes"] >= 2 and sum(plan(k)["pass_bits"]) == k
     ext = same_as_host(k, 1, n_in=1 << (k - 2), g=7, seed=k)                           # the extension: forward, shifted, a quarter of the input
     same_as_host(k, 1, inverse=True, g=pow(7, -1, R), in_place=True, seed=k + 1)
     assert ext.shape == (1, 1 << k, 4)
 
 
+@pytest.mark.parametrize("k", further_pass_sizes())
+def test_smallest_and_largest_size_of_every_further_pass_count(k):
+    extension_and_inverse_in_place(k)
+
+
+SIZES_BETWEEN = [k for k in range(P + 3, 21) if k not in further_pass_sizes()]
+BIG = [21, 22, 23, 24]                                                                  # no host transform of these sizes: see "the largest sizes" below
+
+
+@pytest.mark.parametrize("k", SIZES_BETWEEN)
+def test_every_size_between_those(k):
+    """with the two tests above: every k up to 20, so every width 2^cb of a last strided pass is run inverse with a shift"""
+    extension_and_inverse_in_place(k)
+
+
 def test_pass_counts_covered():
     counts = {plan(k)["n_passes"] for k in list(range(1, P + 3)) + further_pass_sizes()}
     assert counts == {plan(k)["n_passes"] for k in range(1, 21)}
     assert 1 in {b for k in range(P + 1, P + 3) for b in plan(k)["pass_bits"]}, "a one-bit pass"
+    host_checked = list(range(1, P + 3)) + further_pass_sizes() + SIZES_BETWEEN            # each of them forward and, shifted, inverse
+    assert sorted(host_checked + BIG) == list(range(1, 25)), "every k the call accepts, once"
+    passes = lambda ks: {(j, b) for k in ks for j, b in enumerate(plan(k)["pass_bits"])}    # (which pass, how many stages)
+    assert passes(host_checked + BIG) == passes(range(1, 25))
+    assert {b for _, b in passes(host_checked)} == {b for _, b in passes(range(1, 25))}, "every stage count of a pass, against the host twin"
+    assert {(2, 5), (2, 6)} <= passes(BIG) - passes(host_checked), "a second strided pass of 5 and of 6 stages: the largest sizes only"
+    last_cb = lambda ks: {P - plan(k)["pass_bits"][-1] for k in ks if k > P}          # a strided tile is 2^cb cells wide, cb = tile bits - stages
+    assert last_cb(host_checked) == last_cb(range(1, 21)) and {7, 8} <= last_cb(SIZES_BETWEEN)
+
+
+# ---- three passes ---------------------------------------------------------------------------------------------------------------------------------
+K3 = min(k for k in range(1, 25) if plan(k)["n_passes"] == 3)                           # two strided passes: col = blockIdx.x >> tpc in both
+
+
+@pytest.mark.parametrize("form", ["columns and pitches", "pair swap with a short input", "inverse canonical"])
+def test_three_passes_with_columns_pitches_and_short_inputs(form):
+    n = 1 << K3
+    assert K3 <= 20
+    if form == "columns and pitches":
+        same_as_host(K3, 3, n_in=n - 1, g=G, in_pitch=n, out_pitch=n + 4, seed=61)
+    elif form == "pair swap with a short input":
+        same_as_host(K3, 2, n_in=n >> 2, g=7, in_place=True, seed=62)
+    else:
+        same_as_host(K3, 2, inverse=True, canonical=True, g=G, out_pitch=n + 4, seed=63)
+    assert workspaces_unchanged()
 
 
 # ---- columns -------------------------------------------------------------------------------------------------------------------------------------
@@ -208,6 +257,130 @@ def test_two_workspaces_in_turn_and_one_on_two_streams():
     for i in range(2):
         assert np.array_equal(outs[i].cpu().numpy().view(np.uint64), _HOST.fr_ntt_host(cells[i], kb, inverse=bool(i)))
     assert workspaces_unchanged()
+
+
+# ---- the largest sizes ----------------------------------------------------------------------------------------------------------------------------
+# k = 21 .. 24 (coeff_to_extended of a k = 20 .. 22 circuit): pass shapes (5, 4), (5, 5), (6, 5), (6, 6) behind the 12-stage pass.  The host twin is too slow
+# for them, so none of these tests runs it at 2^K: a coset decomposition into transforms of 2^20, a round trip, and Python integers at chosen outputs.
+K20, N20, G0 = 20, 1 << 20, 7
+_BIG = {}
+
+
+def big_input():
+    """(x, y0): one column of 2^20 seeded cells at a pitch of 2^20 + 8, poison above; y0 = the host twin's forward transform of size 2^20 with shift 7 —
+    once per module, coset 0 of every K"""
+    if not _BIG:
+        x = columns(1, N20, N20 + 8, 2024, False)
+        _BIG["x"], _BIG["y0"] = x, _HOST.fr_ntt_host(x, K20, n_in=N20, shift=shift_of(G0, False))
+    return _BIG["x"], _BIG["y0"]
+
+
+@contextlib.contextmanager
+def own_workspace(k):
+    """a workspace of size 2^k between guards for one test — not kept in _WS — checked unchanged when the test is through with it"""
+    raw, ws = guarded(dev_cfg().fr_ntt_workspace_bytes(k) // 8, torch.int64)
+    dev_cfg().fr_ntt_prepare(k, workspace=ws.view(torch.int8))
+    torch.cuda.synchronize()
+    keep = ws.clone()
+    yield ws.view(torch.int8)
+    torch.cuda.synchronize()
+    assert intact(raw, ws.numel(), torch.int64) and torch.equal(ws, keep), ("the workspace", k)
+
+
+@pytest.fixture
+def memory_returned():
+    """what a test of the largest sizes allocated goes back to the device with it, not into torch's cache"""
+    yield
+    gc.collect()
+    torch.cuda.empty_cache()
+
+
+@pytest.mark.usefixtures("memory_returned")
+@pytest.mark.parametrize("K", BIG)
+def test_largest_sizes_are_their_cosets_of_size_2_to_the_20(K):
+    """With w_K^(2^d) = w_20, d = K - 20: output 2^d j + c of the forward K-transform of x (2^20 entries, shift g0) is output j of the forward 20-transform of x
+    with shift g0 w_K^c.  2^d calls at k = 20, each compared on the device; c = 0 and the last (odd) c against the host twin as well.
+    Peak device memory at K = 24: 0.5 GiB the output, 0.25 GiB the table and 0.25 GiB its copy, 32 MiB each the input and ONE sub-transform: 1.1 GiB."""
+    d, cfg = K - K20, dev_cfg()
+    x, y0 = big_input()
+    raw_in, d_in = guarded(x.size, torch.int64)
+    d_in = d_in.view(1, N20 + 8, 4)
+    d_in.copy_(on_device(x))
+    raw_out, d_out = guarded(4 << K, torch.int64)
+    d_out = d_out.view(1, 1 << K, 4)
+    raw_sub, sub = guarded(4 * N20, torch.int64)
+    sub = sub.view(1, N20, 4)
+    with own_workspace(K) as ws:
+        cfg.fr_ntt(d_in, K, workspace=ws, out=d_out, n_in=N20, shift=on_device(shift_of(G0, False)))
+    assert intact(raw_out, d_out.numel(), torch.int64) and intact(raw_in, d_in.numel(), torch.int64)
+    assert np.array_equal(d_in.cpu().numpy().view(np.uint64), x), "the input, and the poison above n_in"
+    by_coset = d_out.view(N20, 1 << d, 4)
+    for c in range(1 << d):
+        g = shift_of(G0 * pow(nr.omega(K), c, R) % R, False)
+        raw_sub.fill_(POISON64)
+        cfg.fr_ntt(d_in, K20, workspace=workspace(K20), out=sub, n_in=N20, shift=on_device(g))
+        torch.cuda.synchronize()
+        assert intact(raw_sub, sub.numel(), torch.int64)
+        assert torch.equal(by_coset[:, c], sub[0]), (K, c)
+        if c == 0:
+            assert np.array_equal(sub.cpu().numpy().view(np.uint64), y0), (K, c)
+        elif c == (1 << d) - 1:
+            assert np.array_equal(sub.cpu().numpy().view(np.uint64), _HOST.fr_ntt_host(x, K20, n_in=N20, shift=g)), (K, c)
+    assert workspaces_unchanged()
+
+
+@pytest.mark.usefixtures("memory_returned")
+@pytest.mark.parametrize("K", BIG)
+def test_largest_sizes_forward_then_inverse_in_place(K):
+    """A dense column of 2^K random reduced cells (two columns at K = 21), forward in place with G, inverse in place with 1 / G: the column again.
+    Peak device memory at K = 24: 0.5 GiB each the column, its copy and the random draw, 0.25 GiB the table and 0.25 GiB its copy: 2 GiB."""
+    cfg, n, n_cols = dev_cfg(), 1 << K, 2 if K == 21 else 1
+    raw, d = guarded(n_cols * n * 4, torch.int64)
+    d = d.view(n_cols, n, 4)
+    gen = torch.Generator(device=DEV)
+    gen.manual_seed(K)
+    d.copy_(torch.randint(0, 1 << 62, (n_cols, n, 4), dtype=torch.int64, device=DEV, generator=gen))
+    d[:, :, 3] >>= 2                                                                       # below 2^252 < r
+    keep = d.clone()
+    g, ginv = on_device(shift_of(G, False)), on_device(shift_of(pow(G, -1, R), False))
+    with own_workspace(K) as ws:
+        assert cfg.fr_ntt(d, K, workspace=ws, out=d, shift=g).data_ptr() == d.data_ptr()
+        torch.cuda.synchronize()
+        assert not torch.equal(d, keep) and bool((d[:, :, 3] >> 62 == 0).all())           # transformed, every cell below 2^254
+        cfg.fr_ntt(d, K, workspace=ws, out=d, inverse=True, shift=ginv)
+    assert torch.equal(d, keep) and intact(raw, d.numel(), torch.int64)
+
+
+@pytest.mark.usefixtures("memory_returned")
+@pytest.mark.parametrize("K", BIG)
+def test_largest_sizes_against_python_integers_around_every_pass_border(K):
+    """n_in = 64 and shift G: both directions, both limb forms, about 40 outputs each against Horner evaluation in Python integers —
+    forward y[j] = x(G w_K^j); inverse y[i] = G^i 2^-K x(w_K^-i) — at 0, 1, 2^K - 1, 2^(K-1) +- 1, 4095 .. 4097, around 2^s0 of every pass and 24 seeded ones.
+    Peak device memory at K = 24: 0.5 GiB the output, 0.25 GiB the table and 0.25 GiB its copy: 1 GiB."""
+    cfg, n, n_in = dev_cfg(), 1 << K, 64
+    starts = np.cumsum([0] + plan(K)["pass_bits"][:-1])                                    # s0 of every pass
+    idx = {0, 1, n - 1, n // 2 - 1, n // 2 + 1, 4095, 4096, 4097} | {(1 << int(s0)) + e for s0 in starts for e in (-1, 0, 1)}
+    idx = sorted(idx | {int(i) for i in np.random.default_rng(K).integers(0, n, 24)})
+    assert len(starts) == 3 and 30 <= len(idx) <= 45
+    w, winv, ninv = nr.omega(K), pow(nr.omega(K), -1, R), pow(n, -1, R)
+    raw, d_out = guarded(4 * n, torch.int64)
+    d_out = d_out.view(1, n, 4)
+    pick = torch.tensor(idx, device=DEV)
+    with own_workspace(K) as ws:
+        for inverse in (False, True):
+            for canonical in (False, True):
+                cells = columns(1, n_in, n_in, 70 + 2 * inverse + canonical, canonical)
+                x = nr.values_of(cells[0], canonical)
+                raw.fill_(POISON64)
+                cfg.fr_ntt(on_device(cells), K, workspace=ws, out=d_out, inverse=inverse, n_in=n_in, shift=on_device(shift_of(G, canonical)), canonical=canonical)
+                torch.cuda.synchronize()
+                assert intact(raw, d_out.numel(), torch.int64) and bool((d_out[0, :, 3] != POISON64).all()), "every entry below 2^K written"
+                got = nr.values_of(d_out[0, pick].cpu().numpy().view(np.uint64), canonical)
+                if inverse:
+                    want = [pow(G, i, R) * ninv * nr.eval_at(x, pow(winv, i, R)) % R for i in idx]
+                else:
+                    want = [nr.eval_at(x, G * pow(w, j, R) % R) for j in idx]
+                assert got == want, (K, inverse, canonical, [i for i, a, b in zip(idx, got, want) if a != b])
 
 
 # ---- the chain -------------------------------------------------------------------------------------------------------------------------------------
