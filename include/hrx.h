@@ -837,7 +837,9 @@ int hrx_ctx_lookup_permute_plan(hrx_ctx *ctx, size_t b_count, size_t n_rows, siz
  * gamma)).  A' and S' are table cells selected by the index columns of LOOKUP PERMUTE, so both inversions are needed per TABLE row, not per witness row:
  * with a table of 1 / (S + beta) and one of 1 / (S + gamma) a row's term is three multiplications and two gathers, and Z is a running product.  All
  * arithmetic is in bn256::Fr; cells are 4 u64 limbs, Montgomery by default and plain integers with HRX_FR_CANONICAL in `flags` (other bits HRX_ERR_ARG), as
- * in LOOKUP COMPRESS; every cell written is a fully reduced element, so the device forms equal the host forms limb for limb.
+ * in LOOKUP COMPRESS; every cell written is a fully reduced element, so the device forms equal the host forms limb for limb.  Every table, input and
+ * inverse cell read must be below r — every producer in this library writes such cells; the sums S + shift, A + beta and S + gamma add the cells as they
+ * are, and a cell of r or more can leave a sum unreduced there — and only `shift`, `beta` and `gamma` are reduced by the calls.
  *
  * INVERSE TABLE (also what a logUp prover needs: m / (S + beta) directly, 1 / (A + beta) by gather).  table_cells: [n_runs][W][4] u64 as
  * hrx_lookup_compress_table_* writes it, W = hrx_lookup_words_per_string(defs); shift: 4 u64 limbs per run, 8-byte aligned, in DEVICE memory for the device
