@@ -728,9 +728,7 @@ void hrx_fr_from_u64(uint64_t v, int flags, uint64_t *limbs) {
     if (v >> 32) {
         fr_from_u64(v, w, (flags & HRX_FR_CANONICAL) != 0);
     } else {   // the kernel's route (every witness value fits 32 bits)
-        uint32_t h[8];
-        fr_from_u32((uint32_t)v, h, (flags & HRX_FR_CANONICAL) != 0);
-        for (int i = 0; i < 4; ++i) w[i] = (uint64_t)h[2 * i] | (uint64_t)h[2 * i + 1] << 32;
+        fr_store_cell(w, fr_from_u32((uint32_t)v, (flags & HRX_FR_CANONICAL) != 0));
     }
     if (limbs) { limbs[0] = w[0]; limbs[1] = w[1]; limbs[2] = w[2]; limbs[3] = w[3]; }
 }

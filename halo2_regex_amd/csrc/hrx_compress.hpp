@@ -43,13 +43,6 @@ HRX_XHD CompressTuples compress_def_row(uint32_t dummy, uint32_t r, uint32_t n, 
     return t;
 }
 
-HRX_XHD void compress_theta_limbs(const uint64_t *theta, uint32_t (&w)[8]) {
-    for (int i = 0; i < 4; ++i) { w[2 * i] = (uint32_t)theta[i]; w[2 * i + 1] = (uint32_t)(theta[i] >> 32); }
-}
-HRX_XHD void compress_put_cell(uint64_t *cell, const uint32_t (&w)[8]) {
-    for (int i = 0; i < 4; ++i) cell[i] = (uint64_t)w[2 * i] | (uint64_t)w[2 * i + 1] << 32;
-}
-
 // What a compress call over rows is told: the rows, and
 struct CompressArgs : RowsIn {
     uint32_t b_begin, b_count;                      // the strings of this launch
@@ -72,18 +65,14 @@ inline void compress_string(const CompressArgs &a, size_t i, uint32_t n, const S
         for (uint32_t k = 0; k < 3; ++k) col[k] = a.cells + ((size_t)(3u * d + k) * a.col_cells + i * M) * 4u;
         for (uint32_t r = 0; r < M; ++r) {
             if (n > M) {
-                for (uint32_t k = 0; k < 3; ++k) col[k][4 * r] = col[k][4 * r + 1] = col[k][4 * r + 2] = col[k][4 * r + 3] = 0;
+                for (uint32_t k = 0; k < 3; ++k) fr_store_cell(col[k] + 4 * (size_t)r, Fr{});
                 continue;
             }
             const uint32_t dummy = a.dummy[d];
             const uint32_t next_state = r + 1u < M ? src.rec(r + 1u, d) & 0xffffu : dummy;
             const CompressTuples t = compress_def_row(dummy, r, n, r < n ? src.chr(r) : 0u, src.rec(r, d), next_state);
             const uint32_t *tup[3] = {t.trans, t.start, t.end};
-            for (uint32_t k = 0; k < 3; ++k) {
-                uint32_t w[8];
-                fr_fold(tup[k][0], tup[k][1], tup[k][2], tup[k][3], p.t3, p.t2, p.t1, p.one, w);
-                compress_put_cell(col[k] + 4 * (size_t)r, w);
-            }
+            for (uint32_t k = 0; k < 3; ++k) fr_store_cell(col[k] + 4 * (size_t)r, fr_fold(tup[k][0], tup[k][1], tup[k][2], tup[k][3], p));
         }
     }
 }

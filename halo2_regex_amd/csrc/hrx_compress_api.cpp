@@ -84,11 +84,7 @@ size_t hrx_lookup_num_columns(size_t D) { return 3 * D; }
 
 void hrx_fr_mul(const uint64_t *a, const uint64_t *b, uint64_t *out) {
     if (!a || !b || !out) return;
-    uint32_t x[8], y[8], z[8];
-    compress_theta_limbs(a, x);
-    compress_theta_limbs(b, y);
-    fr_mul(x, y, z);
-    compress_put_cell(out, z);
+    fr_store_cell(out, fr_mul(fr_load_cell(a), fr_load_cell(b)));
 }
 
 int hrx_lookup_compress_inputs_device(hrx_ctx *ctx, int layout, const uint8_t *chars, size_t stride, const uint32_t *lens, const uint32_t *records, size_t rec_pitch,

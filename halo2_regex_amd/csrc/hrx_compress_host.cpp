@@ -15,11 +15,7 @@ void compress_inputs_host(const CompressArgs &a, unsigned threads) {
             FrPowers p;
             for (size_t i = i0; i < i1; ++i) {      // strings [i0, i1) of the window
                 const size_t b = (size_t)a.b_begin + i;
-                if (i == i0 || a.theta_stride) {
-                    uint32_t th[8];
-                    compress_theta_limbs(a.theta + i * a.theta_stride, th);
-                    fr_powers(th, a.canonical != 0, p);
-                }
+                if (i == i0 || a.theta_stride) p = fr_powers(a.theta + i * a.theta_stride, a.canonical != 0);
                 compress_string(a, i, a.lens[b], RowsOf<decltype(form)::value>(a, b), p);
             }
         });
@@ -36,15 +32,11 @@ void compress_table_host(const CompressTableArgs &a, unsigned threads) {
         for (size_t c = c0; c < c1; ++c) {
             const size_t t = c / a.W, w = c - t * a.W;
             if (t != run) {
-                uint32_t th[8];
-                compress_theta_limbs(a.theta + t * a.theta_stride, th);
-                fr_powers(th, a.canonical != 0, p);
+                p = fr_powers(a.theta + t * a.theta_stride, a.canonical != 0);
                 run = t;
             }
             const uint32_t *tup = a.image + 4 * w;
-            uint32_t out[8];
-            fr_fold(tup[0], tup[1], tup[2], tup[3], p.t3, p.t2, p.t1, p.one, out);
-            compress_put_cell(a.cells + 4 * c, out);
+            fr_store_cell(a.cells + 4 * c, fr_fold(tup[0], tup[1], tup[2], tup[3], p));
         }
     });
 }

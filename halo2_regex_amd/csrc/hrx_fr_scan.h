@@ -9,52 +9,37 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include "hrx_fr.h"
+#include "hrx_fr_device.h"
 
 namespace hrx {
 
-// v: the product of the lane's elements (Montgomery form).  before: the product of the elements of all lanes below this one (R, the Montgomery one, for
-// lane 0); total: the workgroup's product.  wtot: WAVES x 8 words of LDS, free again after the call's first barrier.  Every lane of the workgroup calls.
+struct FrScan {
+    Fr before;      // the product of the elements of all lanes below this one (R, the Montgomery one, for lane 0)
+    Fr total;       // the workgroup's product
+};
+
+// v: the product of the lane's elements (Montgomery form).  wtot: WAVES elements of LDS, free again after the call's first barrier.  Every lane of the
+// workgroup calls.
 template <uint32_t WAVES>
-__device__ __forceinline__ void fr_block_scan_excl(const uint32_t (&v)[8], uint32_t (&before)[8], uint32_t (&total)[8], uint32_t (*wtot)[8]) {
+__device__ __forceinline__ FrScan fr_block_scan_excl(const Fr &v, Fr *wtot) {
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
-    uint32_t inc[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) inc[i] = v[i];
+    Fr inc = v;
 #pragma nounroll
-    for (uint32_t off = 1; off < 64u; off <<= 1) {
-        uint32_t n[8], p[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) n[i] = (uint32_t)__shfl_up((int)inc[i], off, 64);
-        fr_mul(n, inc, p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) inc[i] = lane >= off ? p[i] : inc[i];
-    }
+    for (uint32_t off = 1; off < 64u; off <<= 1) inc = fr_select(lane >= off, fr_mul(fr_shfl_up(inc, off), inc), inc);
     __syncthreads();                                 // (wtot is free again)
-    if (lane == 63u) {
-#pragma unroll
-        for (int i = 0; i < 8; ++i) wtot[wave][i] = inc[i];
-    }
+    if (lane == 63u) wtot[wave] = inc;
     __syncthreads();
-    uint32_t ex[8];                                  // the lanes below in this wave
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        const uint32_t up = (uint32_t)__shfl_up((int)inc[i], 1u, 64);
-        ex[i] = lane == 0u ? kFrR32[i] : up;
-    }
-    uint32_t wb[8];                                  // the waves below: R for wave 0, else what `total` was before this wave's turn
-#pragma unroll
-    for (int i = 0; i < 8; ++i) { wb[i] = kFrR32[i]; total[i] = wtot[0][i]; }
+    const Fr ex = fr_select(lane == 0u, fr_R(), fr_shfl_up(inc, 1u));      // the lanes below in this wave
+    Fr wb = fr_R();                                  // the waves below: R for wave 0, else what `total` was before this wave's turn
+    FrScan out;
+    out.total = wtot[0];
 #pragma unroll
     for (uint32_t w = 1; w < WAVES; ++w) {
-        uint32_t x[8], p[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) { x[i] = wtot[w][i]; wb[i] = wave == w ? total[i] : wb[i]; }
-        fr_mul(total, x, p);
-#pragma unroll
-        for (int i = 0; i < 8; ++i) total[i] = p[i];
+        wb = fr_select(wave == w, out.total, wb);
+        out.total = fr_mul(out.total, wtot[w]);
     }
-    fr_mul(wb, ex, before);
+    out.before = fr_mul(wb, ex);
+    return out;
 }
 
 }  // namespace hrx

@@ -2,8 +2,7 @@
 // small auxiliary kernels: the states-in entry points of lib.rs:825-888 and the field-cell expansion.
 #include <hip/hip_runtime.h>
 
-#include "hrx_device.h"
-#include "hrx_fr.h"
+#include "hrx_fr_device.h"
 #include "hrx_kernel.hpp"
 #include "hrx_lane.h"
 
@@ -100,12 +99,7 @@ __global__ __launch_bounds__(256) void fr_columns_kernel(const FrArgs a) {
     // build first (one entry each; 8 KiB), anything larger (states of DFAs beyond 256 states) is computed in place.  Computed per cell by both lanes of a pair the launch was VALU-bound
     // at 0.68 of the HBM peak.
     __shared__ uint4 frtab[512];
-    {
-        uint32_t w[8];
-        fr_from_u32(threadIdx.x, w, a.canonical != 0);
-        frtab[2u * threadIdx.x] = make_uint4(w[0], w[1], w[2], w[3]);
-        frtab[2u * threadIdx.x + 1u] = make_uint4(w[4], w[5], w[6], w[7]);
-    }
+    fr_store16(&frtab[2u * threadIdx.x], fr_from_u32(threadIdx.x, a.canonical != 0));
     __syncthreads();
     const uint32_t half = threadIdx.x & 1u;
     const uint32_t bi = blockIdx.y;              // index inside the requested range
@@ -128,9 +122,8 @@ __global__ __launch_bounds__(256) void fr_columns_kernel(const FrArgs a) {
                 if (v[j] < 256u) {
                     cell = frtab[2u * v[j] + half];
                 } else {
-                    uint32_t w[8];
-                    fr_from_u32(v[j], w, a.canonical != 0);
-                    cell = half ? make_uint4(w[4], w[5], w[6], w[7]) : make_uint4(w[0], w[1], w[2], w[3]);
+                    const Fr w = fr_from_u32(v[j], a.canonical != 0);
+                    cell = half ? fr_hi16(w) : fr_lo16(w);
                 }
                 unsigned char *p = reinterpret_cast<unsigned char *>(out0 + (size_t)col * col_cells * 4u + (size_t)j * 32u * 4u);
                 store16_nt(p, cell);    // streaming: nothing reads the cells back here

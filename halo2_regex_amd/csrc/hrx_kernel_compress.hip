@@ -16,29 +16,17 @@
 
 #include "../../include/hrx.h"
 #include "hrx_compress.hpp"
-#include "hrx_device.h"
+#include "hrx_fr_device.h"
 
 namespace hrx {
 
 namespace {
 
 // the powers of the workgroup's challenge: computed by lane 0, handed on through LDS, kept in scalar registers (they are operands of every multiply-add)
-__device__ __forceinline__ void powers_of(const uint64_t *theta, const bool canonical, FrPowers *lds, FrPowers &p) {
-    if (threadIdx.x == 0) {
-        uint32_t th[8];
-        compress_theta_limbs(theta, th);
-        FrPowers q;
-        fr_powers(th, canonical, q);
-        *lds = q;
-    }
+__device__ __forceinline__ FrPowers powers_of(const uint64_t *theta, const bool canonical, FrPowers *lds) {
+    if (threadIdx.x == 0) *lds = fr_powers(theta, canonical);
     __syncthreads();
-#pragma unroll
-    for (int i = 0; i < 8; ++i) {
-        p.t1[i] = __builtin_amdgcn_readfirstlane(lds->t1[i]);
-        p.t2[i] = __builtin_amdgcn_readfirstlane(lds->t2[i]);
-        p.t3[i] = __builtin_amdgcn_readfirstlane(lds->t3[i]);
-        p.one[i] = __builtin_amdgcn_readfirstlane(lds->one[i]);
-    }
+    return FrPowers{fr_readfirstlane(lds->t1), fr_readfirstlane(lds->t2), fr_readfirstlane(lds->t3), fr_readfirstlane(lds->one)};
 }
 
 template <int REC>
@@ -46,8 +34,7 @@ __global__ __launch_bounds__(kCzThreads) void compress_inputs_kernel(const Compr
     __shared__ FrPowers pw;
     const uint32_t bi = blockIdx.y;              // index inside the launch's strings
     const uint32_t b = a.b_begin + bi;
-    FrPowers p;
-    powers_of(a.theta + (size_t)bi * a.theta_stride, a.canonical != 0, &pw, p);
+    const FrPowers p = powers_of(a.theta + (size_t)bi * a.theta_stride, a.canonical != 0, &pw);
     const uint32_t M = a.M, n = a.lens[b];
     const bool none = n > M;                     // the string has no rows: zero cells, nothing read
     const RowsPlace s = rows_place<false>(a, b);
@@ -91,16 +78,16 @@ __global__ __launch_bounds__(kCzThreads) void compress_inputs_kernel(const Compr
                 uint64_t *colp = a.cells + ((size_t)(3u * d + col) * a.col_cells + (size_t)bi * M) * 4u + h * 2u;
 #pragma unroll
                 for (uint32_t pr = 0; pr < kPairs; ++pr) {
-                    uint32_t w[8];
-                    fr_fold(e[pr][0], e[pr][1], e[pr][2], e[pr][3], p.t3, p.t2, p.t1, p.one, w);      // (a tuple of three components has e[0] = 0)
+                    const Fr w = fr_fold(e[pr][0], e[pr][1], e[pr][2], e[pr][3], p);      // (a tuple of three components has e[0] = 0)
                     // the even lane sends the high half of its cell and takes the low half of the odd lane's
                     uint32_t got[4];
 #pragma unroll
                     for (int i = 0; i < 4; ++i)
-                        got[i] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(h ? w[i] : w[4 + i]), 0xB1 /* quad_perm [1, 0, 3, 2] */, 0xf, 0xf, false);
+                        got[i] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(h ? w.w[i] : w.w[4 + i]), 0xB1 /* quad_perm [1, 0, 3, 2] */, 0xf, 0xf, false);
+                    const uint4 theirs = make_uint4(got[0], got[1], got[2], got[3]);
                     const uint32_t r_a = wbase + pr * 2u * kCzRowsPerStore + k, r_b = r_a + kCzRowsPerStore;
-                    uint4 cell_a = h ? make_uint4(got[0], got[1], got[2], got[3]) : make_uint4(w[0], w[1], w[2], w[3]);
-                    uint4 cell_b = h ? make_uint4(w[4], w[5], w[6], w[7]) : make_uint4(got[0], got[1], got[2], got[3]);
+                    uint4 cell_a = h ? theirs : fr_lo16(w);
+                    uint4 cell_b = h ? fr_hi16(w) : theirs;
                     if (none) cell_a = cell_b = make_uint4(0, 0, 0, 0);
                     if (r_a < M) store16_nt(colp + (size_t)r_a * 4u, cell_a);      // streaming: nothing reads the cells back here
                     if (r_b < M) store16_nt(colp + (size_t)r_b * 4u, cell_b);
@@ -123,18 +110,13 @@ __global__ __launch_bounds__(kCzThreads) void compress_inputs_kernel(const Compr
 __global__ __launch_bounds__(kCzThreads) void compress_table_kernel(const CompressTableArgs a) {
     __shared__ FrPowers pw;
     const uint32_t t = blockIdx.y;               // the run
-    FrPowers p;
-    powers_of(a.theta + (size_t)t * a.theta_stride, a.canonical != 0, &pw, p);
+    const FrPowers p = powers_of(a.theta + (size_t)t * a.theta_stride, a.canonical != 0, &pw);
 #pragma unroll
     for (uint32_t j = 0; j < kCzTableRowsPerGroup / kCzThreads; ++j) {
         const uint32_t w = blockIdx.x * kCzTableRowsPerGroup + j * kCzThreads + threadIdx.x;
         if (w < a.W) {
             const uint4 tup = reinterpret_cast<const uint4 *>(a.image)[w];
-            uint32_t out[8];
-            fr_fold(tup.x, tup.y, tup.z, tup.w, p.t3, p.t2, p.t1, p.one, out);
-            uint64_t *cell = a.cells + ((size_t)t * a.W + w) * 4u;
-            store16_nt(cell, make_uint4(out[0], out[1], out[2], out[3]));
-            store16_nt(cell + 2, make_uint4(out[4], out[5], out[6], out[7]));
+            fr_store16_nt(a.cells + ((size_t)t * a.W + w) * 4u, fr_fold(tup.x, tup.y, tup.z, tup.w, p));      // streaming: nothing reads the cells back here
         }
     }
 }

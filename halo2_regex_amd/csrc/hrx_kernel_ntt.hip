@@ -23,7 +23,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/hrx.h"
-#include "hrx_device.h"
+#include "hrx_fr_device.h"
 #include "hrx_ntt.hpp"
 
 namespace hrx {
@@ -47,31 +47,6 @@ struct NttPermute {
     uint32_t k, n_in, in_place;
 };
 
-__device__ __forceinline__ void lds_get(const uint32_t *lds, const uint32_t plane, const uint32_t slot, uint32_t (&w)[8]) {
-    const uint4 lo = *reinterpret_cast<const uint4 *>(lds + slot * 4u), hi = *reinterpret_cast<const uint4 *>(lds + (plane + slot) * 4u);
-    w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w; w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
-}
-__device__ __forceinline__ void lds_put(uint32_t *lds, const uint32_t plane, const uint32_t slot, const uint32_t (&w)[8]) {
-    *reinterpret_cast<uint4 *>(lds + slot * 4u) = make_uint4(w[0], w[1], w[2], w[3]);
-    *reinterpret_cast<uint4 *>(lds + (plane + slot) * 4u) = make_uint4(w[4], w[5], w[6], w[7]);
-}
-__device__ __forceinline__ void load8(const uint32_t *p, uint32_t (&w)[8]) {
-    const uint4 lo = *reinterpret_cast<const uint4 *>(p), hi = *reinterpret_cast<const uint4 *>(p + 4);
-    w[0] = lo.x; w[1] = lo.y; w[2] = lo.z; w[3] = lo.w; w[4] = hi.x; w[5] = hi.y; w[6] = hi.z; w[7] = hi.w;
-}
-__device__ __forceinline__ void copy8(uint32_t (&d)[8], const uint32_t (&s)[8]) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) d[i] = s[i];
-}
-// x <- x^(2^n)
-__device__ __forceinline__ void square_n(uint32_t (&x)[8], const uint32_t n) {
-    uint32_t t[8];
-#pragma nounroll
-    for (uint32_t i = 0; i < n; ++i) {
-        fr_mul(x, x, t);
-        copy8(x, t);
-    }
-}
 __device__ __forceinline__ uint32_t rev_bits(const uint32_t i, const uint32_t bits) { return bits ? __brev(i) >> (32u - bits) : 0u; }
 
 // cell e of the workgroup's tile: its column and its index inside the column
@@ -87,12 +62,14 @@ __device__ __forceinline__ void tile_cell(const NttPass &a, const uint32_t e, ui
 }
 
 __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const NttPass a) {
-    uint32_t *lds = reinterpret_cast<uint32_t *>(smem);
+    uint4 *lds = reinterpret_cast<uint4 *>(smem);    // 16-byte slots: the plane of low halves, then the plane of high halves
     const uint32_t tid = threadIdx.x, h = tid & 1u, k = a.k, cells = 1u << a.tile_bits, per_lane = cells / kNttThreads, cmask = (1u << a.cb) - 1u;
     const bool inverse = a.inverse != 0;
     // the swizzle: the top sb bits of a cell's index inside its column (its tile) onto the slot's low bits (sb <= kk / 2: the two do not overlap)
     const uint32_t kk = a.one_launch ? k : a.tile_bits, sb = min(4u, kk >> 1), sw_shift = kk - sb, sw_mask = (1u << sb) - 1u;
     auto slot = [&](const uint32_t e) { return e ^ ((e >> sw_shift) & sw_mask); };
+    auto get = [&](const uint32_t e) { return fr_load16(lds + slot(e), cells); };
+    auto put = [&](const uint32_t e, const Fr &x) { fr_store16(lds + slot(e), x, cells); };
 
     for (uint32_t c = tid >> 1; c < cells; c += kNttThreads / 2u) {          // the tile's cells in: whole lines
         uint32_t col, i;
@@ -100,29 +77,21 @@ __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const NttPass a) 
         uint4 v = make_uint4(0, 0, 0, 0);
         if (col < a.n_cols && i < a.n_in) v = *reinterpret_cast<const uint4 *>(a.src + ((size_t)col * a.src_pitch + i) * 4u + h * 2u);
         const uint32_t e = a.one_launch ? ((c >> k) << k) | rev_bits(i, k) : c;
-        *reinterpret_cast<uint4 *>(lds + (h * cells + slot(e)) * 4u) = v;
+        lds[h * cells + slot(e)] = v;
     }
-    uint32_t g[8], step[8], m[8], x[8], t[8];
-    if (a.shift) {
-        ntt_shift(a.shift, a.canonical != 0, g);
-        copy8(step, g);
-    }
+    Fr g, step, m;
+    if (a.shift) step = g = ntt_shift(a.shift, a.canonical != 0);
     if (a.first && !inverse && a.shift) {            // x g^i on the cells as they lie bit-reversed: the lane's cells are i = tid + kNttThreads r (times 2^(k - 12))
         __syncthreads();
         const uint32_t tpc = a.one_launch ? 0u : k - a.tile_bits, low = a.one_launch ? 0u : rev_bits(blockIdx.x & ((1u << tpc) - 1u), tpc);
         const uint32_t qmask = (1u << kk) - 1u;
         const bool stepping = kk > kNttThreadBits;   // columns of as many cells as the workgroup has lanes, or fewer: the lane's cells have one index, in several columns
-        if (stepping) square_n(step, kNttThreadBits + tpc);
-        fr_pow_u32(g, ((tid & qmask) << tpc) | low, m);
+        if (stepping) step = fr_square_n(step, kNttThreadBits + tpc);
+        m = fr_pow_u32(g, ((tid & qmask) << tpc) | low);
         for (uint32_t r = 0; r < per_lane; ++r) {
             const uint32_t q = tid + r * kNttThreads, e = (q & ~qmask) | rev_bits(q & qmask, kk);
-            if (r && stepping) {
-                fr_mul(m, step, t);
-                copy8(m, t);
-            }
-            lds_get(lds, cells, slot(e), x);
-            fr_mul(x, m, t);
-            lds_put(lds, cells, slot(e), t);
+            if (r && stepping) m = fr_mul(m, step);
+            put(e, fr_mul(get(e), m));
         }
     }
     const uint32_t tile = a.one_launch ? 0u : blockIdx.x & ((1u << (k - a.tile_bits)) - 1u);
@@ -135,42 +104,35 @@ __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const NttPass a) 
             const uint32_t e0 = (m0 << a.cb) | l, e1 = e0 + (1u << (st + a.cb));
             bool neg;
             const uint32_t ti = ntt_twiddle_index(k, s, (lowm << a.s0) + low_pos + l, inverse, neg);
-            uint32_t tw[8], y[8];
-            load8(a.ws + (size_t)ti * 8u, tw);
-            lds_get(lds, cells, slot(e0), x);
-            lds_get(lds, cells, slot(e1), y);
+            const Fr tw = fr_load16(a.ws + (size_t)ti * 8u);
+            Fr x = get(e0), y = get(e1);
             ntt_butterfly(x, y, tw, neg);
-            lds_put(lds, cells, slot(e0), x);
-            lds_put(lds, cells, slot(e1), y);
+            put(e0, x);
+            put(e1, y);
         }
     }
     __syncthreads();
     if (a.last && inverse) {                         // 2^-k g^i: lanes side by side on adjacent cells, a lane's next cell a fixed distance on
-        uint32_t scale[8];
-        load8(a.ws + ntt_table_cells(k) * 8u, scale);
+        const Fr scale = fr_load16(a.ws + ntt_table_cells(k) * 8u);
         // one launch: cells tid + kNttThreads r, that far apart (one index where the columns are that short); a strided tile: lb bits of the lane pick the cell of a
         // row, the others a run of `rows` rows 2^s0 apart, and where a row is wider than the workgroup the lane takes 2^(cb - lb) such runs
         const uint32_t lb = min(a.cb, kNttThreadBits), rows = a.one_launch ? per_lane : per_lane >> (a.cb - lb);
         const bool stepping = a.shift && (a.one_launch ? k > kNttThreadBits : true);
-        if (stepping) square_n(step, a.one_launch ? kNttThreadBits : a.s0);
+        if (stepping) step = fr_square_n(step, a.one_launch ? kNttThreadBits : a.s0);
         for (uint32_t r = 0; r < per_lane; ++r) {
             const uint32_t mr = r % rows;
             const uint32_t e = a.one_launch ? tid + r * kNttThreads
                                             : (((tid >> lb) * rows + mr) << a.cb) | ((tid & ((1u << lb) - 1u)) + ((r / rows) << kNttThreadBits));
             if (!a.shift) {
-                copy8(m, scale);
+                m = scale;
             } else if (mr == 0u) {
                 uint32_t col, i;
                 tile_cell(a, e, col, i);
-                fr_pow_u32(g, i, t);
-                fr_mul(t, scale, m);
+                m = fr_mul(fr_pow_u32(g, i), scale);
             } else if (stepping) {
-                fr_mul(m, step, t);
-                copy8(m, t);
+                m = fr_mul(m, step);
             }
-            lds_get(lds, cells, slot(e), x);
-            fr_mul(x, m, t);
-            lds_put(lds, cells, slot(e), t);
+            put(e, fr_mul(get(e), m));
         }
         __syncthreads();
     }
@@ -178,10 +140,10 @@ __global__ __launch_bounds__(kNttThreads) void ntt_pass_kernel(const NttPass a) 
         uint32_t col, i;
         tile_cell(a, c, col, i);
         if (col >= a.n_cols) continue;
-        const uint4 v = *reinterpret_cast<const uint4 *>(lds + (h * cells + slot(c)) * 4u);
+        const uint4 v = lds[h * cells + slot(c)];
         uint64_t *p = a.out + ((size_t)col * a.out_pitch + i) * 4u + h * 2u;
         if (a.last) store16_nt(p, v);
-        else *reinterpret_cast<uint4 *>(p) = v;
+        else *reinterpret_cast<uint4 *>(p) = v;      // plain: the next pass reads them
     }
 }
 
@@ -219,16 +181,8 @@ __global__ __launch_bounds__(kPermThreads) void ntt_permute_kernel(const NttPerm
 __global__ __launch_bounds__(256) void ntt_prepare_kernel(const uint32_t k, uint32_t *ws) {
     const size_t n = ntt_table_cells(k), e = (size_t)blockIdx.x * 256u + threadIdx.x;
     if (e >= n) return;
-    uint32_t w[8], p[8];
-    ntt_omega(k, w);
-    fr_pow_u32(w, (uint32_t)e, p);
-    *reinterpret_cast<uint4 *>(ws + e * 8u) = make_uint4(p[0], p[1], p[2], p[3]);
-    *reinterpret_cast<uint4 *>(ws + e * 8u + 4u) = make_uint4(p[4], p[5], p[6], p[7]);
-    if (e == 0u) {
-        ntt_inv_n(k, p);
-        *reinterpret_cast<uint4 *>(ws + n * 8u) = make_uint4(p[0], p[1], p[2], p[3]);
-        *reinterpret_cast<uint4 *>(ws + n * 8u + 4u) = make_uint4(p[4], p[5], p[6], p[7]);
-    }
+    fr_store16(ws + e * 8u, fr_pow_u32(ntt_omega(k), (uint32_t)e));      // plain stores: the workspace is read by every later launch
+    if (e == 0u) fr_store16(ws + n * 8u, ntt_inv_n(k));
 }
 
 }  // namespace

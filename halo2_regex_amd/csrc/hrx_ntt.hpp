@@ -59,50 +59,16 @@ HRX_HD size_t ntt_table_cells(uint32_t k) { return k > 1u ? (size_t)1 << (k - 1u
 HRX_HD size_t ntt_workspace_bytes(uint32_t k) { return ((ntt_table_cells(k) + 1u) * 32u + 255u) & ~(size_t)255; }
 
 // w = ROOT_OF_UNITY^(2^(28 - k)), the primitive 2^k-th root (Montgomery form)
-HRX_HD void ntt_omega(uint32_t k, uint32_t (&w)[8]) {
-    uint32_t t[8];
-HRX_FR_UNROLL
-    for (int i = 0; i < 8; ++i) w[i] = kFrRootOfUnity32[i];
-#if defined(__clang__)
-#pragma nounroll
-#endif
-    for (uint32_t s = k; s < kFrS; ++s) {
-        fr_mul(w, w, t);
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) w[i] = t[i];
-    }
-}
+HRX_HD Fr ntt_omega(uint32_t k) { return fr_square_n(fr_root_of_unity(), kFrS - k); }
 // 2^-k (Montgomery form)
-HRX_HD void ntt_inv_n(uint32_t k, uint32_t (&out)[8]) {
-    uint32_t h[8];
-HRX_FR_UNROLL
-    for (int i = 0; i < 8; ++i) h[i] = kFrInv2_32[i];
-    fr_pow_u32(h, k, out);
-}
+HRX_HD Fr ntt_inv_n(uint32_t k) { return fr_pow_u32(fr_half(), k); }
 // the shift as the Montgomery form its powers are formed from: 4 u64 limbs of any 256-bit value in the call's limb form, taken mod r first
-HRX_HD void ntt_shift(const uint64_t *p, bool canonical, uint32_t (&g)[8]) {
-    uint32_t x[8];
-HRX_FR_UNROLL
-    for (int i = 0; i < 4; ++i) { x[2 * i] = (uint32_t)p[i]; x[2 * i + 1] = (uint32_t)(p[i] >> 32); }
-    fr_reduce(x);
-    if (canonical) {
-        uint32_t r2[8];
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) r2[i] = kFrR2_32[i];
-        fr_mul(x, r2, g);
-    } else {
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) g[i] = x[i];
-    }
-}
+HRX_HD Fr ntt_shift(const uint64_t *p, bool canonical) { return fr_to_mont(fr_challenge(p), canonical); }
 // one butterfly: (a, b) -> (a + t b, a - t b), the two swapped where `neg` (the inverse direction's -t)
-HRX_HD void ntt_butterfly(uint32_t (&a)[8], uint32_t (&b)[8], const uint32_t (&t)[8], bool neg) {
-    uint32_t tb[8], s[8], d[8];
-    fr_mul(b, t, tb);
-    fr_add(a, tb, s);
-    fr_sub(a, tb, d);
-HRX_FR_UNROLL
-    for (int i = 0; i < 8; ++i) { a[i] = neg ? d[i] : s[i]; b[i] = neg ? s[i] : d[i]; }
+HRX_HD void ntt_butterfly(Fr &a, Fr &b, const Fr &t, bool neg) {
+    const Fr tb = fr_mul(b, t), s = fr_add(a, tb), d = fr_sub(a, tb);
+    a = fr_select(neg, d, s);
+    b = fr_select(neg, s, d);
 }
 // which table entry stage s reads for the entry whose index mod 2^s is `pos`, and whether it stands for its negative
 HRX_HD uint32_t ntt_twiddle_index(uint32_t k, uint32_t s, uint32_t pos, bool inverse, bool &neg) {

@@ -93,12 +93,7 @@ int hrx_ctx_fr_ntt_plan(hrx_ctx *ctx, size_t n_cols, unsigned k, size_t *n_passe
 
 void hrx_fr_sub(const uint64_t *a, const uint64_t *b, uint64_t *out) {
     if (!a || !b || !out) return;
-    uint32_t x[8], y[8], z[8];
-    for (int i = 0; i < 4; ++i) { x[2 * i] = (uint32_t)a[i]; x[2 * i + 1] = (uint32_t)(a[i] >> 32); y[2 * i] = (uint32_t)b[i]; y[2 * i + 1] = (uint32_t)(b[i] >> 32); }
-    fr_reduce(x);
-    fr_reduce(y);
-    fr_sub(x, y, z);
-    for (int i = 0; i < 4; ++i) out[i] = (uint64_t)z[2 * i] | (uint64_t)z[2 * i + 1] << 32;
+    fr_store_cell(out, fr_sub(fr_challenge(a), fr_challenge(b)));
 }
 
 }  // extern "C"

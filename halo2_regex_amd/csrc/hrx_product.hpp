@@ -14,8 +14,8 @@
 // Every result is a fully reduced element of bn256::Fr, so two implementations agree limb for limb whatever their order of operations.
 //
 // Limb forms.  Montgomery (the default): every cell is x R; fr_mul of two cells is the cell of the product.  Canonical: every cell is the plain x; the scan
-// still runs on Montgomery forms — a term is its four plain factors multiplied (x / R^3) times R^5, and a Z is taken out of Montgomery form with a product
-// by the plain 1 as it is written.  The inverse table likewise: S + c is taken into Montgomery form (times R^2), inverted, and taken out.
+// still runs on Montgomery forms — a term is its four plain factors multiplied (x / R^3) times R^5, and a Z is taken out of Montgomery form as it is written
+// (fr_from_mont).  The inverse table likewise: S + c is taken into Montgomery form (fr_to_mont), inverted, and taken out.  hrx_fr.h has the rule.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -34,51 +34,10 @@ HRX_XHD uint32_t product_table_row(uint32_t i, uint32_t T) { return i < T ? i : 
 // an index column's word that may be used as an address into the string's run
 HRX_XHD bool product_index_ok(uint32_t w, uint32_t off, uint32_t T) { return w >= off && w - off < T; }
 
-HRX_XHD void product_get_cell(const uint64_t *cell, uint32_t (&w)[8]) {
-    for (int i = 0; i < 4; ++i) { w[2 * i] = (uint32_t)cell[i]; w[2 * i + 1] = (uint32_t)(cell[i] >> 32); }
-}
-HRX_XHD void product_put_cell(uint64_t *cell, const uint32_t (&w)[8]) {
-    for (int i = 0; i < 4; ++i) cell[i] = (uint64_t)w[2 * i] | (uint64_t)w[2 * i + 1] << 32;
-}
-
-// s (a cell plus its shift, in the call's limb form) as the Montgomery form the scans multiply: s itself, or s R where the call is canonical
-HRX_HD void product_to_mont(const uint32_t (&s)[8], bool canonical, uint32_t (&out)[8]) {
-    if (canonical) {
-        uint32_t r2[8];
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) r2[i] = kFrR2_32[i];
-        fr_mul(s, r2, out);
-    } else {
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) out[i] = s[i];
-    }
-}
-// a Montgomery form as the call's limb form: itself, or x R / R where the call is canonical
-HRX_HD void product_from_mont(const uint32_t (&x)[8], bool canonical, uint32_t (&out)[8]) {
-    if (canonical) {
-        uint32_t one[8];
-        fr_one(true, one);
-        fr_mul(x, one, out);
-    } else {
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) out[i] = x[i];
-    }
-}
-
 // term[i] as a Montgomery form out of the four cells in the call's limb form: ab = A + beta, sg = S + gamma, ib = inv_beta[ia], ig = inv_gamma[is]
-HRX_HD void product_term(const uint32_t (&ab)[8], const uint32_t (&sg)[8], const uint32_t (&ib)[8], const uint32_t (&ig)[8], bool canonical, uint32_t (&out)[8]) {
-    uint32_t u[8], v[8];
-    fr_mul(ab, ib, u);
-    fr_mul(sg, ig, v);
-    fr_mul(u, v, out);
-    if (canonical) {                                // the plain product over R^3 -> its Montgomery form
-        uint32_t r5[8];
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) r5[i] = kFrR5_32[i];
-        fr_mul(out, r5, u);
-HRX_FR_UNROLL
-        for (int i = 0; i < 8; ++i) out[i] = u[i];
-    }
+HRX_HD Fr product_term(const Fr &ab, const Fr &sg, const Fr &ib, const Fr &ig, bool canonical) {
+    const Fr t = fr_mul(fr_mul(ab, ib), fr_mul(sg, ig));
+    return canonical ? fr_mul(t, fr_R5()) : t;      // the plain product over R^3 -> its Montgomery form
 }
 
 // ---- how the kernels cut the work (hrx_kernel_product.hip): a workgroup of kPdThreads lanes walks one run (invert) or one (string, lookup) (product) in

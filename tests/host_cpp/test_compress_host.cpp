@@ -95,10 +95,13 @@ static Big big_mod(const Big &a, const Big &m) {          // binary long divisio
     rem.resize(k);
     return rem;
 }
-static void limbs_of_big(Big a, uint32_t (&w)[8]) {
+static Fr fr_of_big(Big a) {
     a.resize(16, 0);
-    for (int i = 0; i < 8; ++i) w[i] = a[2 * i] | a[2 * i + 1] << 16;
+    Fr x;
+    for (int i = 0; i < 8; ++i) x.w[i] = a[2 * i] | a[2 * i + 1] << 16;
+    return x;
 }
+static Big big_of(const Fr &x) { return big_of_limbs(x.w, 8); }
 static Big modulus() { return big_of_limbs(kFrModulus32, 8); }
 static Big two_pow_256() { Big b(17, 0); b[16] = 1; return b; }
 
@@ -125,34 +128,25 @@ static uint32_t rnd() {                                  // splitmix64
     z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
     return (uint32_t)((z ^ (z >> 31)) >> 16);
 }
-static void rnd_below_r(uint32_t (&w)[8]) {
-    for (int i = 0; i < 8; ++i) w[i] = rnd();
-    limbs_of_big(big_mod(big_of_limbs(w, 8), modulus()), w);
+static Fr rnd_256() {
+    Fr x;
+    for (int i = 0; i < 8; ++i) x.w[i] = rnd();
+    return x;
 }
-static bool same(const uint32_t (&a)[8], const uint32_t (&b)[8]) { return memcmp(a, b, 32) == 0; }
+static Fr rnd_below_r() { return fr_of_big(big_mod(big_of(rnd_256()), modulus())); }
+static bool same(const Fr &a, const Fr &b) { return memcmp(a.w, b.w, 32) == 0; }
 
 static void check_mul_add() {
     const Big m = modulus();
-    std::vector<std::vector<uint32_t>> vals;
-    uint32_t w[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    vals.emplace_back(w, w + 8);                           // 0
-    w[0] = 1; vals.emplace_back(w, w + 8);                 // 1
-    limbs_of_big(big_sub(m, Big{1}), w); vals.emplace_back(w, w + 8);      // r - 1
-    vals.emplace_back(kFrR32, kFrR32 + 8);                 // R
-    vals.emplace_back(kFrR2_32, kFrR2_32 + 8);             // R^2
-    for (int i = 0; i < 40; ++i) { rnd_below_r(w); vals.emplace_back(w, w + 8); }
+    std::vector<Fr> vals = {Fr{}, fr_unit(true), fr_of_big(big_sub(m, Big{1})), fr_R(), fr_R2()};      // 0, 1, r - 1, R, R^2
+    for (int i = 0; i < 40; ++i) vals.push_back(rnd_below_r());
     EXPECT(big_cmp(big_mod(big_mul(big_mod(two_pow_256(), m), big_mod(two_pow_256(), m)), m), big_of_limbs(kFrR2_32, 8)) == 0);
     EXPECT(big_cmp(big_mod(two_pow_256(), m), big_of_limbs(kFrR32, 8)) == 0);
     for (size_t i = 0; i < vals.size(); ++i)
         for (size_t j = 0; j < (i < 5 ? vals.size() : 8); ++j) {
-            uint32_t a[8], b[8], got[8], want[8];
-            memcpy(a, vals[i].data(), 32); memcpy(b, vals[j].data(), 32);
-            fr_mul(a, b, got);
-            limbs_of_big(big_mod(big_mul(big_mul(big_of_limbs(a, 8), big_of_limbs(b, 8)), r_inverse()), m), want);
-            EXPECT(same(got, want));
-            fr_add(a, b, got);
-            limbs_of_big(big_mod(big_add(big_of_limbs(a, 8), big_of_limbs(b, 8)), m), want);
-            EXPECT(same(got, want));
+            const Fr a = vals[i], b = vals[j];
+            EXPECT(same(fr_mul(a, b), fr_of_big(big_mod(big_mul(big_mul(big_of(a), big_of(b)), r_inverse()), m))));
+            EXPECT(same(fr_add(a, b), fr_of_big(big_mod(big_add(big_of(a), big_of(b)), m))));
         }
 }
 
@@ -164,78 +158,66 @@ static void check_reduce() {
             if (q == 0 && delta < 0) continue;
             Big x = delta < 0 ? big_sub(k, Big{1}) : delta > 0 ? big_add(k, Big{1}) : k;
             if (big_cmp(x, two_pow_256()) >= 0) continue;
-            uint32_t w[8], want[8];
-            limbs_of_big(x, w);
-            limbs_of_big(big_mod(x, m), want);
-            fr_reduce(w);
-            EXPECT(same(w, want));
+            EXPECT(same(fr_reduce(fr_of_big(x)), fr_of_big(big_mod(x, m))));
         }
         k = big_add(k, m);
     }
-    uint32_t w[8], want[8];
-    for (int i = 0; i < 8; ++i) w[i] = 0xffffffffu;        // 2^256 - 1
-    limbs_of_big(big_mod(big_of_limbs(w, 8), m), want);
-    fr_reduce(w);
-    EXPECT(same(w, want));
+    Fr w;
+    for (int i = 0; i < 8; ++i) w.w[i] = 0xffffffffu;      // 2^256 - 1
+    EXPECT(same(fr_reduce(w), fr_of_big(big_mod(big_of(w), m))));
     for (int i = 0; i < 200; ++i) {
-        for (int j = 0; j < 8; ++j) w[j] = rnd();
-        limbs_of_big(big_mod(big_of_limbs(w, 8), m), want);
-        fr_reduce(w);
-        EXPECT(same(w, want));
+        w = rnd_256();
+        EXPECT(same(fr_reduce(w), fr_of_big(big_mod(big_of(w), m))));
     }
 }
 
-static void fold_by_the_yardstick(const uint32_t (&e)[4], const FrPowers &p, uint32_t (&want)[8]) {
-    Big s = big_mul(Big{e[0]}, big_of_limbs(p.t3, 8));
-    s = big_add(s, big_mul(Big{e[1]}, big_of_limbs(p.t2, 8)));
-    s = big_add(s, big_mul(Big{e[2]}, big_of_limbs(p.t1, 8)));
-    s = big_add(s, big_mul(Big{e[3]}, big_of_limbs(p.one, 8)));
-    limbs_of_big(big_mod(s, modulus()), want);
+static Fr fold_by_the_yardstick(const uint32_t (&e)[4], const FrPowers &p) {
+    Big s = big_mul(Big{e[0]}, big_of(p.t3));
+    s = big_add(s, big_mul(Big{e[1]}, big_of(p.t2)));
+    s = big_add(s, big_mul(Big{e[2]}, big_of(p.t1)));
+    s = big_add(s, big_mul(Big{e[3]}, big_of(p.one)));
+    return fr_of_big(big_mod(s, modulus()));
+}
+// fr_powers of a challenge given as an element: any 256-bit value, taken mod r first
+static FrPowers powers_of(const Fr &theta, bool canonical) {
+    uint64_t th[4];
+    fr_store_cell(th, theta);
+    return fr_powers(th, canonical);
 }
 
 static void check_fold() {
     const Big m = modulus();
-    FrPowers p;
-    uint32_t top[8], got[8], want[8];
-    limbs_of_big(big_sub(m, Big{1}), top);
+    const Fr top = fr_of_big(big_sub(m, Big{1}));
     // the largest sum there is: every component 0xffff, every power and `one` r - 1
-    for (int i = 0; i < 8; ++i) p.t1[i] = p.t2[i] = p.t3[i] = p.one[i] = top[i];
+    FrPowers p = {top, top, top, top};
     const uint32_t ffff[4] = {0xffffu, 0xffffu, 0xffffu, 0xffffu};
-    fr_fold(ffff[0], ffff[1], ffff[2], ffff[3], p.t3, p.t2, p.t1, p.one, got);
-    fold_by_the_yardstick(ffff, p, want);
-    EXPECT(same(got, want));
+    EXPECT(same(fr_fold(ffff[0], ffff[1], ffff[2], ffff[3], p), fold_by_the_yardstick(ffff, p)));
     // theta = r - 1 in both forms, every component 0xffff and the single-component corners
     for (int canonical = 0; canonical < 2; ++canonical) {
-        fr_powers(top, canonical != 0, p);
+        p = powers_of(top, canonical != 0);
         // (r - 1)^2 = 1, (r - 1)^3 = r - 1 mod r; in Montgomery form theta = (r - 1) / R, whose powers the yardstick gives
-        uint32_t t2[8], t3[8];
+        Fr t2, t3;
         if (canonical) {
-            limbs_of_big(big_mod(big_mul(big_of_limbs(top, 8), big_of_limbs(top, 8)), m), t2);
-            limbs_of_big(big_mod(big_mul(big_of_limbs(t2, 8), big_of_limbs(top, 8)), m), t3);
+            t2 = fr_of_big(big_mod(big_mul(big_of(top), big_of(top)), m));
+            t3 = fr_of_big(big_mod(big_mul(big_of(t2), big_of(top)), m));
         } else {
-            limbs_of_big(big_mod(big_mul(big_mul(big_of_limbs(top, 8), big_of_limbs(top, 8)), r_inverse()), m), t2);
-            limbs_of_big(big_mod(big_mul(big_mul(big_of_limbs(t2, 8), big_of_limbs(top, 8)), r_inverse()), m), t3);
+            t2 = fr_of_big(big_mod(big_mul(big_mul(big_of(top), big_of(top)), r_inverse()), m));
+            t3 = fr_of_big(big_mod(big_mul(big_mul(big_of(t2), big_of(top)), r_inverse()), m));
         }
         EXPECT(same(p.t1, top) && same(p.t2, t2) && same(p.t3, t3));
         for (uint32_t mask = 0; mask < 16; ++mask) {
             uint32_t e[4];
             for (int i = 0; i < 4; ++i) e[i] = (mask >> i) & 1u ? 0xffffu : 0u;
-            fr_fold(e[0], e[1], e[2], e[3], p.t3, p.t2, p.t1, p.one, got);
-            fold_by_the_yardstick(e, p, want);
-            EXPECT(same(got, want));
+            EXPECT(same(fr_fold(e[0], e[1], e[2], e[3], p), fold_by_the_yardstick(e, p)));
         }
     }
     for (int i = 0; i < 300; ++i) {
-        uint32_t th[8], e[4];
-        for (int j = 0; j < 8; ++j) th[j] = rnd();         // any 256-bit value: taken mod r first
-        fr_powers(th, (i & 1) != 0, p);
-        uint32_t t1[8];
-        limbs_of_big(big_mod(big_of_limbs(th, 8), m), t1);
-        EXPECT(same(p.t1, t1));
+        uint32_t e[4];
+        const Fr th = rnd_256();                           // any 256-bit value: taken mod r first
+        p = powers_of(th, (i & 1) != 0);
+        EXPECT(same(p.t1, fr_of_big(big_mod(big_of(th), m))));
         for (int j = 0; j < 4; ++j) e[j] = rnd() & 0xffffu;
-        fr_fold(e[0], e[1], e[2], e[3], p.t3, p.t2, p.t1, p.one, got);
-        fold_by_the_yardstick(e, p, want);
-        EXPECT(same(got, want));
+        EXPECT(same(fr_fold(e[0], e[1], e[2], e[3], p), fold_by_the_yardstick(e, p)));
     }
 }
 
@@ -268,10 +250,7 @@ static void check_rows(uint32_t M) {
         for (uint32_t b = 0; b < B; ++b) {
             const uint32_t n = lens[b];
             if (n > M) continue;
-            uint32_t th[8];
-            compress_theta_limbs(&theta[4 * b], th);
-            FrPowers p;
-            fr_powers(th, canonical != 0, p);
+            const FrPowers p = fr_powers(&theta[4 * b], canonical != 0);
             for (uint32_t d = 0; d < D; ++d)
                 for (uint32_t r = 0; r < M; ++r) {
                     const uint32_t x = rec[((size_t)b * M + r) * D + d], en = r < n, dm = dummy[d];
@@ -281,11 +260,7 @@ static void check_rows(uint32_t M) {
                     const uint32_t tup[3][4] = {{en * c, en * cur + (1 - en) * dm, en * nxt + (1 - en) * dm, en * sid},
                                                 {0, se * sid, se * cur + (1 - se) * dm, dm},
                                                 {0, ee * sid, dm, ee * nxt + (1 - ee) * dm}};
-                    for (uint32_t k = 0; k < 3; ++k) {
-                        uint32_t w[8];
-                        fold_by_the_yardstick(tup[k], p, w);
-                        compress_put_cell(&want[(((size_t)(3 * d + k) * B + b) * M + r) * 4], w);
-                    }
+                    for (uint32_t k = 0; k < 3; ++k) fr_store_cell(&want[(((size_t)(3 * d + k) * B + b) * M + r) * 4], fold_by_the_yardstick(tup[k], p));
                 }
         }
         // string-major tight and pitched, position-major with either input layout: exact heap blocks
@@ -350,15 +325,11 @@ static void check_table() {
         CompressTableArgs a{h_img.get(), W, h_theta.get(), 4, 3, (uint32_t)canonical, cells.get()};
         compress_table_host(a, 2);
         for (uint32_t t = 0; t < 3; ++t) {
-            uint32_t th[8];
-            compress_theta_limbs(&theta[4 * t], th);
-            FrPowers p;
-            fr_powers(th, canonical != 0, p);
+            const FrPowers p = fr_powers(&theta[4 * t], canonical != 0);
             for (uint32_t w = 0; w < W; ++w) {
-                uint32_t e[4] = {img[4 * w], img[4 * w + 1], img[4 * w + 2], img[4 * w + 3]}, want[8];
+                const uint32_t e[4] = {img[4 * w], img[4 * w + 1], img[4 * w + 2], img[4 * w + 3]};
                 uint64_t cell[4];
-                fold_by_the_yardstick(e, p, want);
-                compress_put_cell(cell, want);
+                fr_store_cell(cell, fold_by_the_yardstick(e, p));
                 EXPECT(memcmp(cell, &cells[((size_t)t * W + w) * 4], 32) == 0);
                 if (w >= 17) EXPECT((cell[0] | cell[1] | cell[2] | cell[3]) == 0);
             }

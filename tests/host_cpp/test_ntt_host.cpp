@@ -156,23 +156,18 @@ int main() {
         U c;
         memcpy(c.w, kFrRootOfUnity, 32);
         CHECK(eq(c, root), "kFrRootOfUnity is not 7^((r - 1) / 2^28)");
-        uint32_t w32[8];
-        for (int i = 0; i < 8; ++i) w32[i] = kFrRootOfUnity32[i];
         U m = mulmod(root, kMont), got;
-        for (int i = 0; i < 4; ++i) got.w[i] = (uint64_t)w32[2 * i] | (uint64_t)w32[2 * i + 1] << 32;
+        fr_store_cell(got.w, fr_root_of_unity());
         CHECK(eq(got, m), "kFrRootOfUnity32 is not its Montgomery form");
-        for (int i = 0; i < 4; ++i) got.w[i] = (uint64_t)kFrInv2_32[2 * i] | (uint64_t)kFrInv2_32[2 * i + 1] << 32;
+        fr_store_cell(got.w, fr_half());
         CHECK(eq(got, mulmod(kHalf, kMont)), "kFrInv2_32 is not the Montgomery form of 1 / 2");
         CHECK(eq(addmod(kHalf, kHalf), kOne), "(r + 1) / 2");
         CHECK(eq(powmod(root, 1ull << 28), kOne) && !eq(powmod(root, 1ull << 27), kOne), "the root's order is not 2^28");
     }
     for (int t = 0; t < 2000; ++t) {     // fr_sub
         const U a = t == 0 ? U{{0, 0, 0, 0}} : random_element(rng), b = t == 1 ? a : t == 2 ? submod(U{{0, 0, 0, 0}}, kOne) : random_element(rng);
-        uint32_t x[8], y[8], z[8];
-        for (int i = 0; i < 4; ++i) { x[2 * i] = (uint32_t)a.w[i]; x[2 * i + 1] = (uint32_t)(a.w[i] >> 32); y[2 * i] = (uint32_t)b.w[i]; y[2 * i + 1] = (uint32_t)(b.w[i] >> 32); }
-        fr_sub(x, y, z);
         U got;
-        for (int i = 0; i < 4; ++i) got.w[i] = (uint64_t)z[2 * i] | (uint64_t)z[2 * i + 1] << 32;
+        fr_store_cell(got.w, fr_sub(fr_load_cell(a.w), fr_load_cell(b.w)));
         CHECK(eq(got, submod(a, b)), "fr_sub, sample %d", t);
     }
     for (unsigned k = 1; k <= 6; ++k) {
