@@ -14,7 +14,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hrx_device.h"
-#include "hrx_walk_pm.h"
+#include "hrx_tile_end.h"
 
 namespace hrx {
 
@@ -254,15 +254,7 @@ __global__ __launch_bounds__(256) void witness_combine_summary_kernel(const Comb
         TileBits tb{st, en1, ch};
         TileMasks tm = tile_masks<64>(tb, mc, t0, tile_is_exact(t0, n, M), rows_below(t0, n));
         if (!active) tm.fix = 0;
-        uint64_t fixm = __ballot(tm.fix != 0);
-        while (fixm) {   // an earlier optimistic end_mask = 1 turned out wrong: zero those masked rows (rare)
-            const int j = __ffsll((unsigned long long)fixm) - 1;
-            fixm &= fixm - 1;
-            const uint32_t fs = (uint32_t)__builtin_amdgcn_readlane((int)tm.fix_start, j);
-            const uint32_t bj = b0 + (uint32_t)j;
-            for (uint32_t r = fs + lane; r < t0; r += 64u)
-                a.masked[((size_t)blk0 * q8 + (size_t)(r >> 3) * nb + (bj - blk0)) * 8u + (r & 7u)] = 0;
-        }
+        take_back_end_mask(tm.fix != 0, tm.fix_start, t0, b0, lane, PmBlockRows{a.masked, blk0, nb, q8});
         uint32_t cw[16];
 #pragma unroll
         for (uint32_t i = 0; i < 4u; ++i) {
@@ -272,17 +264,11 @@ __global__ __launch_bounds__(256) void witness_combine_summary_kernel(const Comb
             const bool have = t0 + 16u * i <= row_cap;
             cw[4 * i] = have ? c.x : 0u; cw[4 * i + 1] = have ? c.y : 0u; cw[4 * i + 2] = have ? c.z : 0u; cw[4 * i + 3] = have ? c.w : 0u;
         }
-        const uint32_t mlo = (uint32_t)tm.mask, mhi = (uint32_t)(tm.mask >> 32);
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
+        tile_octets(cw, sidq, tm.mask, [&](const int k, const uint4 &v) {
             const uint32_t row8 = t0 + 8u * k;
-            if (row8 < M) {
-                const uint32_t mbyte = ((k < 4 ? mlo : mhi) >> (8 * (k & 3))) & 0xffu;
-                uint4 v = make_uint4(0, 0, 0, 0);
-                if (mbyte) v = masked_octet(cw[2 * k], cw[2 * k + 1], sidq[2 * k], sidq[2 * k + 1], mbyte);
+            if (row8 < M)   // only the octets that exist
                 __builtin_nontemporal_store(v4{v.x, v.y, v.z, v.w}, reinterpret_cast<v4 *>(a.masked + ((size_t)blk0 * q8 + (size_t)(row8 >> 3) * nb + bl) * 8u));
-            }
-        }
+        });
     }
     if (!active) return;
     uint64_t sw = 0;

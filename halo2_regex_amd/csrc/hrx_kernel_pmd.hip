@@ -15,7 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hrx_device.h"
-#include "hrx_walk_pm.h"
+#include "hrx_tile_end.h"
 
 namespace hrx {
 
@@ -391,32 +391,16 @@ __global__ __launch_bounds__(FIN && (D >= 7 || (!CW && D >= 3)) ? 640 : 512) voi
             TileBits all{st, en1, ch};
             TileMasks tm = tile_masks<64>(all, mc, t0, tile_is_exact(t0, n, M), rows_below(t0, n));
             if (!active) tm.fix = 0;
-            uint64_t fixm = __ballot(tm.fix != 0);
-            if (a.debug & kDbgSkipFixups) fixm = 0;
-            while (fixm) {   // an earlier optimistic end_mask = 1 turned out wrong: zero those masked rows (rare)
-                const int j = __ffsll((unsigned long long)fixm) - 1;
-                fixm &= fixm - 1;
-                const uint32_t fs = (uint32_t)__builtin_amdgcn_readlane((int)tm.fix_start, j);
-                const uint32_t bj = b0 + (uint32_t)j;
-                for (uint32_t r = fs + lane; r < t0; r += 64u) {
-                    if (SMO) a.masked[(size_t)bj * a.msk_pitch + r] = 0;
-                    else a.masked[((size_t)blk0 * q8 + (size_t)(r >> 3) * nb + (bj - blk0)) * 8u + (r & 7u)] = 0;     // (in this group's block of the buffer)
-                }
-            }
+            take_back_end_mask(tm.fix != 0, tm.fix_start, t0, b0, lane, PmOrSmRows<SMO>{{a.masked, blk0, nb, q8}, {a.masked, (size_t)a.msk_pitch}}, false, (a.debug & kDbgSkipFixups) != 0);
             {
                 // (streamed unless a string of the wave has an open optimistic span: rows that may be zeroed later stay in L2 for the repair — hrx_kernel_pm.hip octets_out)
                 const bool nt_tile = nt_msk && !(!(a.nt_mix & kNtMixNoOpenSpan) && __any(mc.pend != 0u));
-                const uint32_t mlo = (uint32_t)tm.mask, mhi = (uint32_t)(tm.mask >> 32);
-#pragma unroll
-                for (int q = 0; q < 8; ++q) {
-                    const uint32_t mbyte = ((q < 4 ? mlo : mhi) >> (8 * (q & 3))) & 0xffu;
-                    uint4 v = make_uint4(0, 0, 0, 0);
-                    if (mbyte) v = masked_octet(cwl[2 * q], cwl[2 * q + 1], sidq[2 * q], sidq[2 * q + 1], mbyte);  // lib.rs:752-761
-                    if constexpr (SMO) {   // string-major masked rows [B][pitch]: a string's 64 rows are one 128-byte line — through LDS, so that a store instruction writes the full lines of eight strings
+                if constexpr (SMO) {   // string-major masked rows [B][pitch]: a string's 64 rows are one 128-byte line — through LDS, so that a store instruction writes the full lines of eight strings
+                    tile_octets(cwl, sidq, tm.mask, [&](const int q, const uint4 &v) {
                         *(__attribute__((address_space(3))) v4u32 *)(uintptr_t)(mbuf + (lane * 8u + ((uint32_t)q ^ (lane & 7u))) * 16u) = v4u32{v.x, v.y, v.z, v.w};
-                    } else {
-                        if (t0 + (uint32_t)q * 8u < M && !(a.debug & kDbgSkipMasked)) store16(mp + (size_t)q * mstep, v, nt_tile);
-                    }
+                    });
+                } else {
+                    store_tile_octets(cwl, sidq, tm.mask, mp, mstep, false, t0, M, nt_tile, !(a.debug & kDbgSkipMasked));
                 }
                 if constexpr (SMO) {
                     __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");

@@ -70,6 +70,16 @@ def test_every_witness_variant_on_the_lever_batch(hra, oracle, row):
             _witness(hra, oracle, row, case)
 
 
+def test_string_major_rows_of_three_defs_on_the_lever_batch(hra, oracle):
+    """String-major outputs of three defs come from the position-major kernel's own string-major form, which the variant matrix has no row for: its walker
+    ends its tiles itself and takes ranges back at the string's pitch.  The 'three' form at 2048 rows (checked without a device by
+    tests/test_carry_cpu.py::test_forms_are_what_they_claim[three]), into pitched buffers."""
+    row = dict(id="sm-three-defs", entry="sm", flags=0, shape=None, expect=r"witness_pm_kernel<3, false, \w+, false, true, false>")
+    case = cd.scenario_batch(cd.WITNESS_M, chunk=cd.FORCED_CHUNK, **cd.FORMS["three"])
+    case.seed = 3
+    _witness(hra, oracle, row, case)
+
+
 def _chunk_row(expect, flags):
     return dict(id="chunked", entry="pm", flags=flags, shape=None, expect=re.escape(expect))
 
