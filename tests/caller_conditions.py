@@ -286,7 +286,10 @@ def calibrate_delay(torch, want_ms=25.0):
 
 # ---- the cases both files use -----------------------------------------------------------------------------------------------------------------------
 CHUNK_ROW_ID = "chunked"
-SCRATCH_ROWS = (CHUNK_ROW_ID, "pm-multi-pass-merge", "pm-multi-pass-combine", "sm-via-pm-half", "pm-dynamic-groups")        # the witness paths that own context scratch
+SCRATCH_ROWS = (CHUNK_ROW_ID, "pm-multi-pass-merge", "pm-multi-pass-combine", "sm-via-pm-half", "pm-dynamic-groups",        # the witness paths that own context scratch
+                # string-major outputs of four and more defs, one row of each route: group-private records behind the copy-mode combine; position-major scratch and the
+                # transposer behind the class-wide launch, behind class-wide groups with the summary combine, and behind groups of three merged by the last pass
+                "sm-multi-pass-copy-combine", "sm-class-wide-transpose", "sm-class-wide-groups-transpose", "sm-multi-pass-merge-transpose")
 SEQUENCE_ROWS = SCRATCH_ROWS + ("pm-narrow", "pm-class-def-parallel", "sm-split-4byte")
 SEQUENCE_SIZES = (129, 1, 65, 320, 64, 129, 0)
 

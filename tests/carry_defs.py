@@ -19,7 +19,7 @@ One substring definition: every transition into state 1 or 2, start states {0}, 
   second=True   states 4, 5 and the bytes t (-> 4), u (stays in 4), d (-> 5) with a second substring definition (every transition into 4 or 5, start
                 states {0, 2}, end states {5}): the id changes A -> B without a flag (`s r t`), with a start (`f t`), and `x e t` puts A's end flag and
                 B's start flag on one row (index of t).
-  D = 2 .. 8    def k has six lever bytes of its own (LEVERS[k]); the bytes of the other defs are filler to it.  ST / EN / SID are sums over the
+  D = 2 .. 12   def k has six lever bytes of its own (LEVERS[k]); the bytes of the other defs are filler to it.  ST / EN / SID are sums over the
                 defs, so `x e` of def 1 confirms a range def 0's `s` opened, and def 1's `s` takes it back.  The byte BOTH is `s` to every def:
                 out of state 0 two defs flag one row (status 2).
   pad=n         n more states (HALF / BYTE tables want 150 .. 256): the byte p walks through them in a ring, every other byte acts in them as in
@@ -36,6 +36,7 @@ import numpy as np
 import fuzz_defs as fd
 
 LEVERS = [b"fsrexy", b"FSREXY", b"!\"#$%&", b"'()*+,", b"-./012", b"345678", b"9:;<=>", b"?@ABCD"]
+LEVERS += [bytes(range(0xB0 + 6 * j, 0xB6 + 6 * j)) for j in range(4)]      # defs 8 .. 11: 0xB0 .. 0xC7, above every CLASS0 + j (which end below 0xA8)
 BOTH = ord("b")
 UNDEF = ord("~")             # no def has a transition for it
 PADB = ord("p")
@@ -555,7 +556,24 @@ FORCED_CHUNK = 256                                             # kDbgForceSpec: 
 CHUNKED = [(2048, 256, "forced"), (8192, 256, "forced"),       # (M, rows per chunk, forced or the planner's own): 8 and 32 forced chunks,
            (8192, 1024, "8x16"), (65536, 2048, "32x32"), (131072, 4096, "32x64")]      # 8 x 16, 32 x 32 and 32 x 64 tiles
 FORMS = {"one": dict(D=1), "second": dict(D=1, second=True), "two": dict(D=2), "three": dict(D=3), "big": dict(D=1, pad=200), "reduced": dict(D=1, reduced=True),
-         "four_classes": dict(D=4, classes=20), "seven_wide": dict(D=7, classes=40), "eight": dict(D=8, classes=20)}
+         "four_classes": dict(D=4, classes=20), "seven_wide": dict(D=7, classes=40), "eight": dict(D=8, classes=20),
+         # the forms of the string-major rows of three and more defs (row_form of those rows at their fewest and most defs)
+         "two_big": dict(D=2, pad=200), "three_big": dict(D=3, pad=200), "four_wide": dict(D=4, classes=40), "six_classes": dict(D=6, classes=20),
+         "six_wide": dict(D=6, classes=40), "eight_wide": dict(D=8, classes=40), "nine": dict(D=9, classes=20), "twelve": dict(D=12, classes=20)}
+SM_ROW_FORMS = ("two_big", "three_big", "four_wide", "six_classes", "six_wide", "eight_wide", "nine", "twelve")
+BLOCK_BATCH = 65600                                            # rows that repeat their batch past one position-major block of 65536 strings: 320 rows (321 / 328)
+
+
+def row_ms(shape):
+    """the row counts of a variant row's lever batches: 2048 and a row count off the tile grid (tile_is_exact's second clause, a partial last tile), odd where
+    the row takes any M — 2047 and 1001 for rows of M % 8 != 0 alone, 2040 and 1000 for rows of M % 16 == 8; the first alone where the variant needs 16384
+    strings; 320 (321, 328) alone where it needs 65600 and more"""
+    first = {"odd8": 2047, "m8x": 2040}.get(shape.m, WITNESS_M)
+    if shape.min_batch >= BLOCK_BATCH:
+        return ({"odd8": 321, "m8x": 328}.get(shape.m, 320),)
+    if shape.min_batch:
+        return (first,)
+    return (first, {"any": 1001, "odd8": 1001, "m8x": 1000}.get(shape.m, 2000))
 
 
 def row_form(shape, D):

@@ -28,7 +28,9 @@ import numpy as np
 
 M_SMALL = (1, 2, 3, 5, 7, 8, 9, 31, 33, 100, 257)
 M_16 = (16, 32, 48, 64, 80, 128, 144, 256, 320, 512)
+M_8X = (8, 24, 40, 56, 72, 136, 264, 328)      # M % 16 == 8: below the transposer's 32-row tile, one octet on each side of its border, a partial last tile
 BATCHES = (1, 63, 64, 65, 129)
+PM_BLOCK = 65536          # strings per block of the position-major layouts (include/hrx.h)
 UNDEF_EDGES = ("undef_0", "undef_n-1", "undef_M-1", "undef_odd", "undef_even", "undef_3", "undef_4", "undef_7", "undef_8", "undef_63", "undef_64")
 BYTE_EDGES = ("byte_0", "byte_127", "byte_128", "byte_255")
 LEN_EDGES = ("len_0", "len_1", "len_M-1", "len_M", "len_M+1")
@@ -39,7 +41,7 @@ ALL_EDGES = DEF_EDGES + ("ids_62", "ids_63", "ids_64", "ids_65", "ids_sum_255", 
 @dataclasses.dataclass(frozen=True)
 class Shape:
     """What a kernel variant can take.  states: 'small' (3..60 states), 'big' (150..256: HALF / BYTE tables), 'pair' (a total DFA over 2..4 bytes).
-    m: 'any' (small and odd M too), 'm16' (multiples of 16), 'm8' (M % 8 == 0), 'odd8' (M % 8 != 0).  ids: substring-id edges the variant can
+    m: 'any' (small and odd M too), 'm16' (multiples of 16), 'm8' (M % 8 == 0), 'm8x' (M % 16 == 8), 'odd8' (M % 8 != 0).  ids: substring-id edges the variant can
     take ('ids_62' .. 'ids_65', 'ids_sum_255').  ascii: every def's bytes below 128 (the WIDE table)."""
     d_lo: int = 1
     d_hi: int = 1
@@ -191,6 +193,7 @@ def make_case(seed, shape):
     defs_t, walks = [], []
     shared = _alphabet(rng, shape)
     marker = int(shared[-1]) if D >= 2 and len(shared) >= 3 else None     # planted only where status 2 is wanted
+    big_multi = shape.states == "big" and D > 1      # other defs beside the big one: all of them over the big def's bytes and the shared ones (no draw more or less)
     for d in range(D):
         dens = 1.0
         if shape.states == "big" and d == 0:
@@ -204,6 +207,8 @@ def make_case(seed, shape):
                 opts = opts - {"unused_below_L", "accept_unreachable"}
             if "unused_below_L" in opts or "accept_unreachable" in opts:      # (unused state numbers: stay within 256 rows)
                 S = min(S, 250)
+            if big_multi:
+                alpha = np.union1d(alpha, shared).astype(np.uint8)
             if kind != "partial_255":
                 edges.add(kind)
         elif shape.states == "pair" and d == 0:
@@ -215,7 +220,7 @@ def make_case(seed, shape):
                 alpha = shared if D > 1 or rng.random() < 0.8 else _alphabet(rng, shape, 2, 40)
                 dens = float(rng.choice([1.0, 1.0, 0.97, 0.9]))
             else:       # total over the shared bytes: the walks of def 0 decide how a string ends, the other defs flag rows beside it
-                alpha = shared
+                alpha = defs_t[0][2] if big_multi else shared
         a_t, subs, al, walk = _def_text(rng, S, alpha, dens, opts if d == 0 else set(), counts[d], edges, few_pairs=d > 0, silent=d > 0, marker=marker if d == 1 else None)
         if shape.states == "big" and d == 0 and kind == "partial_255" and a_t.split("\n", 3)[2] == "254" and len({ln.split()[0] for ln in a_t.split("\n")[3:] if ln}) == 255:
             edges.add("partial_255")
@@ -226,6 +231,8 @@ def make_case(seed, shape):
         pool_m = [m for m in M_16 if m <= shape.m_max]
     elif shape.m == "m8":
         pool_m = [m for m in M_16 + (8,) if m <= shape.m_max]
+    elif shape.m == "m8x":
+        pool_m = [m for m in M_8X if m <= shape.m_max]
     elif shape.m == "odd8":
         pool_m = [m for m in M_SMALL + (100, 260) if m % 8 and m <= shape.m_max]
     else:

@@ -43,6 +43,7 @@ MS = (8, 64, 1000, 1001, 1024, 2048, 4096, 32768)
 SETTING_MS = (64, 1001, 4096)
 CUS = (256, 255, 64, 1)
 VIA_ROWS = 1 << 32                            # kDbgMatchViaRows
+RECORDED_ROWS = 21                            # rows of the variant matrix when the fixture was recorded: their settings are lines of the sweep
 
 # every bit of kDbgForceMask (csrc/hrx_kernel.hpp)
 FORCE_BITS = (0x10000, 0x20000, 0x40000, 0x80000, 0x200000, 0x400000, 0x2000, 0x8000, 0x2000000, 0x4000000, 0x8000000, 0x40000000, 0x100000,
@@ -114,8 +115,11 @@ def settings():
     HRX_MP_COMBINE; the match entry's "via rows" bit"""
     from test_variants_gpu import ROWS
     s = {"bit_%x" % b: dict(flags=b) for b in FORCE_BITS}
-    for r in ROWS:
+    for r in ROWS[:RECORDED_ROWS]:
         s["row_" + r["id"]] = dict(flags=r["flags"], mpc=bool(r.get("mp_combine")), option=r.get("option"))
+    # (the matrix's later rows reach their variants by shape — row counts, def counts, batch sizes — under settings the recorded rows already hold: no lines of their own)
+    held = {(st["flags"], st["mpc"], st["option"]) for name, st in s.items() if name.startswith("row_")}
+    assert all((r["flags"], bool(r.get("mp_combine")), r.get("option")) in held for r in ROWS[RECORDED_ROWS:])
     for v in (0, 1, 2):
         s["combiner_wave_%d" % v] = dict(flags=0, option=(1, v))
     for v in (0, 1):

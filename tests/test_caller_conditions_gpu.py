@@ -95,7 +95,7 @@ def test_witness_rows_at_minimum_alignment(hra, oracle, row):
     lens at 4 mod 8, the position-major input written into such a view too"""
     live = False
     cases, fr_seed = cc.alignment_cases(row)
-    assert any(c.B % 64 for c in cases) and (any(c.M % 8 for c in cases) or row["id"] == cc.CHUNK_ROW_ID or row["shape"].m in ("m16", "m8")), row["id"]
+    assert any(c.B % 64 for c in cases) and (any(c.M % 8 for c in cases) or row["id"] == cc.CHUNK_ROW_ID or row["shape"].m in ("m16", "m8", "m8x")), row["id"]
     for case in cases:
         cfg = make_config(hra, row, case, 0)
         check_describe(row, cfg, case)

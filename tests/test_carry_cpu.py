@@ -114,7 +114,8 @@ def _claims(oracle, case, chunk):
     return cols
 
 
-OTHER_M = [(320, cd.FORCED_CHUNK, "variants"), (1001, cd.FORCED_CHUNK, "variants"), (2000, cd.FORCED_CHUNK, "variants")]      # the variant rows' other row counts
+OTHER_M = [(320, cd.FORCED_CHUNK, "variants"), (1001, cd.FORCED_CHUNK, "variants"), (2000, cd.FORCED_CHUNK, "variants"),      # the variant rows' other row counts
+           (321, cd.FORCED_CHUNK, "variants"), (1000, cd.FORCED_CHUNK, "variants"), (2040, cd.FORCED_CHUNK, "variants"), (2047, cd.FORCED_CHUNK, "variants")]
 
 
 @pytest.mark.parametrize("M,chunk,kind", cd.CHUNKED + OTHER_M, ids=["%d-%s" % (m, k) for m, _, k in cd.CHUNKED + OTHER_M])
@@ -122,7 +123,7 @@ def test_batches_are_what_they_claim(oracle, M, chunk, kind):
     _claims(oracle, cd.scenario_batch(M, chunk=chunk, lean=M > 8192), chunk)
 
 
-@pytest.mark.parametrize("form", ["second", "three", "big", "reduced", "seven_wide"])
+@pytest.mark.parametrize("form", ["second", "three", "big", "reduced", "seven_wide"] + list(cd.SM_ROW_FORMS))
 def test_forms_are_what_they_claim(oracle, form):
     case = cd.scenario_batch(cd.WITNESS_M, chunk=cd.FORCED_CHUNK, **cd.FORMS[form])
     _claims(oracle, case, cd.FORCED_CHUNK)
@@ -132,6 +133,34 @@ def test_forms_are_what_they_claim(oracle, form):
         both, opened = int(np.flatnonzero(text == cd.BOTH)[0]), int(np.flatnonzero(text == cd.LEVERS[0][1])[0])
         st = int(_oracle(oracle, case).witness_batch(case.chars[b:b + 1], case.lens[b:b + 1], case.M)[2][0])
         assert st & 0xff == 2 and st >> 40 == both and both - opened >= case.M - 80, (hex(st), opened, both)
+
+
+SM_ROWS = ("sm-three-defs-loader-walker", "sm-multi-pass-copy-combine", "sm-class-wide-transpose", "sm-class-wide-groups-transpose", "sm-multi-pass-merge-transpose",
+           "sm-multi-pass-combine-transpose", "sm-via-pm-half-defs", "sm-one-wave-gs16", "sm-class-wide-transpose-two-blocks", "sm-copy-combine-two-blocks")
+
+
+def test_the_string_major_rows_run_checked_forms_at_checked_row_counts():
+    """the rows of the variant matrix for string-major outputs of three and more defs: the lever batches tests/test_carry_gpu.py gives them are forms and row counts
+    this file checks, at row counts the row's shape admits, and describe_launch of a host-only context names the row's variant for every one of them; the lever
+    table holds twelve defs of six bytes each that nothing else uses"""
+    import fuzz_defs as fd
+    from test_variants_gpu import ROWS, check_describe, make_config
+    own = [c for lv in cd.LEVERS for c in lv]
+    assert len(cd.LEVERS) == 12 and len(set(own)) == 72
+    assert not set(own) & ({cd.BOTH, cd.UNDEF, cd.PADB} | set(cd.SECOND) | set(range(cd.CLASS0, cd.CLASS0 + 40)))
+    checked_m = {cd.WITNESS_M} | {m for m, _, kind in OTHER_M if kind == "variants"}
+    rows = [r for r in ROWS if r["id"] in SM_ROWS]
+    assert len(rows) == len(SM_ROWS)
+    for row in rows:
+        sh = row["shape"]
+        for M in cd.row_ms(sh):
+            assert M in checked_m and (M % 8 != 0 if sh.m == "odd8" else M % 16 == 8 if sh.m == "m8x" else M % 8 == 0 if sh.m in ("m8", "m16") else True), (row["id"], M)
+            for D in sorted({sh.d_lo, sh.d_hi}):
+                form = cd.row_form(sh, D)
+                assert form in cd.FORMS.values(), (row["id"], form)
+                case = cd.scenario_batch(M, chunk=cd.FORCED_CHUNK, min_batch=sh.min_batch, **form)
+                assert case.B >= sh.min_batch and (sh.min_batch < cd.BLOCK_BATCH or case.B % fd.PM_BLOCK % 64)      # (two blocks: the last group of the second is partial)
+                check_describe(row, make_config(hra, row, case, hra.HRX_DEVICE_NONE), case, host_only=True)
 
 
 def test_a_walker_without_the_fix_or_the_repair_fails_every_scenario(oracle):

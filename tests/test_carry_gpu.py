@@ -5,6 +5,7 @@ tests/test_variants_gpu.py, the chunked launch with forced and with the planner'
 Everywhere: describe_launch / describe_match names the kernel the test means; status words equal the oracle's on every string, records and masked rows bit for
 bit on the status-0 ones; the witness outputs go into poisoned, guarded buffers (the fix-up is a store loop of data-dependent length).  What the batches hold is
 checked without a device by tests/test_carry_cpu.py."""
+import dataclasses
 import os
 import re
 
@@ -54,19 +55,21 @@ def _witness(hra, oracle, row, case, fr=False, pitched=None, planes_describe=Fal
 
 
 def _second_m(shape):
-    """a row count off the tile grid (tile_is_exact's second clause, a partial last tile): odd where the row takes any M"""
-    return 1001 if shape.m == "any" else 2000
+    """a row count off the tile grid (tile_is_exact's second clause, a partial last tile): odd where the row takes any M or odd ones alone, M % 16 == 8 where
+    the row takes no other (carry_defs.row_ms)"""
+    return cd.row_ms(dataclasses.replace(shape, min_batch=0))[1]
 
 
 @pytest.mark.parametrize("row", ROWS, ids=ROW_IDS)
 def test_every_witness_variant_on_the_lever_batch(hra, oracle, row):
-    """each row of the variant matrix at the fewest and the most defs it admits: 2048 rows and 1001 / 2000 (2048 alone where the variant needs 16384 strings,
-    320 where it needs 70000)"""
+    """each row of the variant matrix at the fewest and the most defs it admits: 2048 rows and 1001 / 2000 (2047 and 1001 for rows of M % 8 != 0, 2040 and 1000
+    for rows of M % 16 == 8; the first alone where the variant needs 16384 strings, 320 / 321 where it needs 65600 and more)"""
     sh = row["shape"]
-    for M in ((320,) if sh.min_batch >= 70000 else (cd.WITNESS_M,) if sh.min_batch else (cd.WITNESS_M, _second_m(sh))):
+    for M in cd.row_ms(sh):
         for D in sorted({sh.d_lo, sh.d_hi}):
             case = cd.scenario_batch(M, chunk=cd.FORCED_CHUNK, min_batch=sh.min_batch, **cd.row_form(sh, D))
-            case.seed = D + (M & 1)          # (odd: pitched string-major buffers, string-major input to the planes launch; even: the other way)
+            # (odd: pitched string-major buffers, string-major input to the planes launch; even: the other way.  Rows of odd M alone: 2047 pitched, 1001 and 321 not)
+            case.seed = D + ((M >> 1 if sh.m == "odd8" else M) & 1)
             _witness(hra, oracle, row, case)
 
 

@@ -58,6 +58,34 @@ ROWS = [
          expect=r"^hrx::witness_pmd_kernel<{D}, true, true, true> .*sub-tiles"),
     dict(id="pm-multi-pass-merge", entry="pm", flags=0x2000000, shape=fd.Shape(4, 7), expect=r"^multi-pass.*the last pass merges the summaries", planes=False),
     dict(id="pm-multi-pass-combine", entry="pm", flags=0x2000000, mp_combine=True, shape=fd.Shape(4, 7), expect=r"^multi-pass.*\+ hrx::witness_combine_summary_kernel", planes=False),
+    # ---- string-major outputs of three and more defs: what an unmodified string-major caller of such a config runs.  Three defs at M % 8 == 0: the
+    # loader/walker kernel's own string-major form.  More: M % 8 != 0 is the copy-mode combine behind passes over groups of three (its records and masked
+    # rows are per-lane stores at the caller's pitches, its take-backs a store loop of data-dependent length); M % 8 == 0 runs position-major into context
+    # scratch and through the transposer, behind each of its producers: the class-wide def-parallel launch (four and five defs only off M % 16 == 0, where
+    # the sub-tile form takes over), class-wide groups with the summary combine, groups of three merged by the last pass or combined; and behind a HALF
+    # walk of two and three defs.  The transposer's tile is 128 / 64 / 32 / 16 rows at D = 1 / 2 / 3..9 / >= 10: the m8x and m8 pools hold row counts below
+    # a tile, one octet on either side of its border, and partial last tiles.  The two-blocks rows repeat their batches past one position-major block of
+    # 65536 strings (the last group of the second block is partial)
+    dict(id="sm-three-defs-loader-walker", entry="sm", flags=0, shape=fd.Shape(3, 3, m="m8"), expect=r"^hrx::witness_pm_kernel<3, false, \w+, false, true, false> (?!.*transpose)"),
+    dict(id="sm-multi-pass-copy-combine", entry="sm", flags=0, shape=fd.Shape(4, 8, m="odd8"), expect=r"^multi-pass.*\+ hrx::witness_combine_kernel<true>"),
+    dict(id="sm-class-wide-transpose", entry="sm", flags=0, shape=fd.Shape(4, 8, m="m8x", s_max=12), seeds=(0, 1, 2, 4, 9, 18),
+         expect=r"^hrx::witness_pmd_kernel<{D}, true, true, false> .* \+ hrx::transpose_pm_to_sm_kernel$"),
+    # (seeds 21 and 23: 8 rows at ten defs and 16 at twelve, the 16-row tile's first sizes, with more than one string)
+    dict(id="sm-class-wide-groups-transpose", entry="sm", flags=0, shape=fd.Shape(9, 12, m="m8", s_max=12), seeds=(0, 1, 2, 3, 4, 16, 21, 23),
+         expect=r"^multi-pass.*witness_pmd_kernel<.*\+ hrx::witness_combine_summary_kernel \+ hrx::transpose_pm_to_sm_kernel$"),
+    dict(id="sm-multi-pass-merge-transpose", entry="sm", flags=0x2000000, shape=fd.Shape(4, 7, m="m8"),
+         expect=r"^multi-pass.*the last pass merges the summaries.* \+ hrx::transpose_pm_to_sm_kernel$"),
+    dict(id="sm-multi-pass-combine-transpose", entry="sm", flags=0x2000000, mp_combine=True, shape=fd.Shape(4, 7, m="m8"),
+         expect=r"^multi-pass.*\+ hrx::witness_combine_summary_kernel \+ hrx::transpose_pm_to_sm_kernel$"),
+    # (the HALF image holds at most 256 states over all defs: no 255-state def beside others, and small other defs)
+    dict(id="sm-via-pm-half-defs", entry="sm", flags=0x8000, shape=fd.Shape(2, 3, "big", m="m8", big_kinds=("big_total", "big_partial"), s_max=12), seeds=(0, 2, 3, 4, 7, 19, 24),
+         expect=r"witness_pm_kernel<{D}, false, false, true, \w+, false> .* \+ hrx::transpose_pm_to_sm_kernel$"),
+    # (batches of at most 129 strings: fewer groups of 32 than CUs)
+    dict(id="sm-one-wave-gs16", entry="sm", flags=0x10000, shape=fd.Shape(1, 3), expect=r"witness_kernel<{D}, {m8}, false> .* gs=16$"),
+    dict(id="sm-class-wide-transpose-two-blocks", entry="sm", flags=0, shape=fd.Shape(6, 6, m="m8", s_max=12, m_max=40, min_batch=65600),
+         expect=r"^hrx::witness_pmd_kernel<6, true, true, false> .* \+ hrx::transpose_pm_to_sm_kernel$"),
+    dict(id="sm-copy-combine-two-blocks", entry="sm", flags=0, shape=fd.Shape(6, 6, m="odd8", m_max=40, min_batch=65600),
+         expect=r"^multi-pass.*\+ hrx::witness_combine_kernel<true>"),
 ]
 ROW_IDS = [r["id"] for r in ROWS]
 
@@ -80,6 +108,8 @@ def applicable_edges(row):
         e.add("few_classes")
     if sh.m_max <= 64:
         e.discard("undef_64")
+    if sh.m_max <= 63:
+        e.discard("undef_63")
     return e
 
 
