@@ -302,6 +302,19 @@ extern "C" {
                            shift: *const u64, flags: c_int) -> c_int;
     pub fn hrx_ctx_fr_ntt_plan(ctx: *mut hrx_ctx, n_cols: usize, k: c_uint, n_passes: *mut usize, pass_bits: *mut usize, cols_per_group: *mut usize) -> c_int;
     pub fn hrx_fr_sub(a: *const u64, b: *const u64, out: *mut u64);
+    /// LOOKUP QUOTIENT: the lookup argument's five constraints at every point of the extended coset, folded into the quotient accumulator with y and (with
+    /// HRX_QUOTIENT_DIVIDE = 4 in flags) divided by X^n - 1 through the table of hrx_fr_vanishing_inverse_*
+    pub fn hrx_fr_vanishing_inverse_device(ctx: *mut hrx_ctx, k: c_uint, ext_k: c_uint, shift: *const u64, t_inv: *mut u64, flags: c_int, stream: *mut c_void) -> c_int;
+    pub fn hrx_fr_vanishing_inverse_host(ctx: *mut hrx_ctx, k: c_uint, ext_k: c_uint, shift: *const u64, t_inv: *mut u64, flags: c_int) -> c_int;
+    pub fn hrx_lookup_quotient_device(ctx: *mut hrx_ctx, b_count: usize, k: c_uint, ext_k: c_uint, a_ext: *const u64, ap_ext: *const u64, sp_ext: *const u64,
+                                      z_ext: *const u64, pitch: usize, s_ext: *const u64, s_pitch: usize, s_stride: usize, selectors: *const u64,
+                                      sel_pitch: usize, beta: *const u64, gamma: *const u64, y: *const u64, challenge_stride: usize, h_in: *const u64,
+                                      h_out: *mut u64, h_pitch: usize, t_inv: *const u64, flags: c_int, stream: *mut c_void) -> c_int;
+    pub fn hrx_lookup_quotient_host(ctx: *mut hrx_ctx, b_count: usize, k: c_uint, ext_k: c_uint, a_ext: *const u64, ap_ext: *const u64, sp_ext: *const u64,
+                                    z_ext: *const u64, pitch: usize, s_ext: *const u64, s_pitch: usize, s_stride: usize, selectors: *const u64,
+                                    sel_pitch: usize, beta: *const u64, gamma: *const u64, y: *const u64, challenge_stride: usize, h_in: *const u64,
+                                    h_out: *mut u64, h_pitch: usize, t_inv: *const u64, flags: c_int) -> c_int;
+    pub fn hrx_ctx_lookup_quotient_plan(ctx: *mut hrx_ctx, b_count: usize, ext_k: c_uint, tile_cells: *mut usize, cells_per_lane: *mut usize) -> c_int;
     pub fn hrx_fr_num_columns(d: usize) -> usize;
     pub fn hrx_fr_from_u64(v: u64, flags: c_int, limbs: *mut u64);
     /// what src/vrm/js_caller.rs:36-48, 127-157 obtain from V8: regexToDfa's JSON, the AllstrRegexDef text, formatRegexPrintable; and the part search of vrm/mod.rs:540-600

@@ -177,6 +177,11 @@ def _load():
         "hrx_fr_ntt_host": (i, [vp, vp, sz, vp, sz, sz, C.c_uint, sz, vp, i]),
         "hrx_ctx_fr_ntt_plan": (i, [vp, sz, C.c_uint, C.POINTER(sz), C.POINTER(sz), C.POINTER(sz)]),
         "hrx_fr_sub": (None, [_u64p, _u64p, _u64p]),
+        "hrx_fr_vanishing_inverse_device": (i, [vp, C.c_uint, C.c_uint, vp, vp, i, vp]),
+        "hrx_fr_vanishing_inverse_host": (i, [vp, C.c_uint, C.c_uint, vp, vp, i]),
+        "hrx_lookup_quotient_device": (i, [vp, sz, C.c_uint, C.c_uint, vp, vp, vp, vp, sz, vp, sz, sz, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, i, vp]),
+        "hrx_lookup_quotient_host": (i, [vp, sz, C.c_uint, C.c_uint, vp, vp, vp, vp, sz, vp, sz, sz, vp, sz, vp, vp, vp, sz, vp, vp, sz, vp, i]),
+        "hrx_ctx_lookup_quotient_plan": (i, [vp, sz, C.c_uint, C.POINTER(sz), C.POINTER(sz)]),
         "hrx_witness_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u32p, _u16p, _u64p]),
         "hrx_match_batch_device": (i, [vp, i, vp, sz, vp, sz, sz, vp, vp, vp, sz, vp]),
         "hrx_match_batch_host": (i, [vp, _u8p, sz, _u32p, sz, sz, _u64p, _u32p, _u64p, sz]),
@@ -1808,6 +1813,128 @@ class RegexVerifyConfig:
         _check(call(n_cols, in_pitch, out, out.shape[-2], n_in, (FR_CANONICAL if canonical else 0) | (FR_NTT_INVERSE if inverse else 0)))
         return out
 
+    def lookup_quotient_plan(self, b_count, ext_k):
+        """hrx_ctx_lookup_quotient_plan: how a lookup_quotient call cuts its work — a dict of tile_cells (consecutive points of one string a workgroup takes)
+        and cells_per_lane"""
+        v = [C.c_size_t() for _ in range(2)]
+        _check(lib.hrx_ctx_lookup_quotient_plan(self._need_ctx(), int(b_count), int(ext_k), *[C.byref(x) for x in v]))
+        return dict(zip(("tile_cells", "cells_per_lane"), (int(x.value) for x in v)))
+
+    def fr_vanishing_inverse(self, k, ext_k, shift=None, out=None, canonical=False, stream=None):
+        """hrx_fr_vanishing_inverse_device: t_inv[c] = 1 / (g^(2^k) w_ext^(2^k c) - 1), c < 2^(ext_k - k) — what X^n - 1 takes on the extended coset of
+        generator g, inverted; the zero cell where that is zero (include/hrx.h LOOKUP QUOTIENT).  shift: g as int64 CUDA limbs (4,), or None (1).  Returns int64
+        limbs (2^(ext_k - k), 4) on the config's device (`out` if given).  Montgomery limbs unless canonical.  One launch of one workgroup, asynchronous on
+        `stream` (default: torch's current stream), capturable from the first call."""
+        device = torch.device("cuda", self.device) if shift is None else shift.device
+        s = torch.cuda.current_stream(device) if stream is None else stream
+        rot = 1 << max(int(ext_k) - int(k), 0)
+        out = _out_buffer(out, "out", (rot, 4), torch.int64, device)
+        _check(lib.hrx_fr_vanishing_inverse_device(self._need_device(shift, out), int(k), int(ext_k), shift.data_ptr() if shift is not None else None,
+                                                   out.data_ptr(), FR_CANONICAL if canonical else 0, s.cuda_stream))
+        return out
+
+    def fr_vanishing_inverse_host(self, k, ext_k, shift=None, out=None, canonical=False):
+        """hrx_fr_vanishing_inverse_host: fr_vanishing_inverse over numpy arrays (uint64), on a host-only or a device context — the definition of the table
+        (csrc/hrx_quotient.hpp)"""
+        shift = None if shift is None else np.ascontiguousarray(shift, np.uint64)
+        out = _out_buffer(out, "out", (1 << max(int(ext_k) - int(k), 0), 4), np.uint64)
+        _check(lib.hrx_fr_vanishing_inverse_host(self._need_ctx(), int(k), int(ext_k), shift.ctypes.data if shift is not None else None, out.ctypes.data,
+                                                 FR_CANONICAL if canonical else 0))
+        return out
+
+    def lookup_quotient(self, k, ext_k, a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y, h_in=None, out=None, t_inv=None, divide=False,
+                        canonical=False, stream=None):
+        """hrx_lookup_quotient_device: the five constraints of every lookup at every point of the extended coset, folded into the quotient accumulator with y
+        (include/hrx.h LOOKUP QUOTIENT).  a_ext, ap_ext, sp_ext, z_ext: int64 CUDA limbs [3 D][b_count][pitch][4] — A, A', S', Z on the coset (fr_ntt at ext_k
+        with the coset's generator); s_ext: [3 D][s_pitch][4] — one table run for the call — or [3 D][b_count][s_pitch][4]; selectors: [3][sel_pitch][4]
+        (lookup_quotient_selectors); beta, gamma, y: int64 limbs (4,) or (b_count, 4), the three alike; h_in: [b_count][h_pitch][4] or None (zero).  Returns
+        h_out, int64 [b_count][h_pitch][4]: `out` if given (`out is h_in`: in place), else a fresh tensor of pitch 2^ext_k; entries [0, 2^ext_k) of a column
+        written, the others never.  divide=True: times t_inv (fr_vanishing_inverse), the division by X^n - 1.  Montgomery limbs unless canonical.  One
+        launch, asynchronous on `stream` (default: torch's current stream), capturable from the first call."""
+        assert z_ext.is_cuda and z_ext.dtype == torch.int64
+        s = torch.cuda.current_stream(z_ext.device) if stream is None else stream
+
+        def call(b_count, pitch, s_pitch, s_stride, sel_pitch, challenge_stride, h_out, h_pitch, flags):
+            ptr = lambda t: t.data_ptr() if t is not None else None
+            return lib.hrx_lookup_quotient_device(self._need_device(a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y, h_in, h_out, t_inv), b_count, int(k),
+                                                  int(ext_k), a_ext.data_ptr(), ap_ext.data_ptr(), sp_ext.data_ptr(), z_ext.data_ptr(), pitch, s_ext.data_ptr(), s_pitch,
+                                                  s_stride, selectors.data_ptr(), sel_pitch, beta.data_ptr(), gamma.data_ptr(), y.data_ptr(), challenge_stride,
+                                                  ptr(h_in), h_out.data_ptr(), h_pitch, ptr(t_inv), flags, s.cuda_stream)
+
+        return self._lookup_quotient(ext_k, a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y, h_in, out, t_inv, divide, canonical, torch.int64,
+                                     z_ext.device, call)
+
+    def lookup_quotient_host(self, k, ext_k, a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y, h_in=None, out=None, t_inv=None, divide=False,
+                             canonical=False):
+        """hrx_lookup_quotient_host: lookup_quotient over numpy arrays in host memory (uint64), on a host-only or a device context — the definition of the
+        cells (csrc/hrx_quotient.hpp) over host threads by ranges of strings.  Entries above 2^ext_k of a caller's `out` are never written."""
+        a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y = (np.ascontiguousarray(x, np.uint64)
+                                                                          for x in (a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y))
+        t_inv = None if t_inv is None else np.ascontiguousarray(t_inv, np.uint64)
+        if h_in is not None and h_in is not out:
+            h_in = np.ascontiguousarray(h_in, np.uint64)
+
+        def call(b_count, pitch, s_pitch, s_stride, sel_pitch, challenge_stride, h_out, h_pitch, flags):
+            ptr = lambda t: t.ctypes.data if t is not None else None
+            return lib.hrx_lookup_quotient_host(self._need_ctx(), b_count, int(k), int(ext_k), a_ext.ctypes.data, ap_ext.ctypes.data, sp_ext.ctypes.data,
+                                                z_ext.ctypes.data, pitch, s_ext.ctypes.data, s_pitch, s_stride, selectors.ctypes.data, sel_pitch, beta.ctypes.data,
+                                                gamma.ctypes.data, y.ctypes.data, challenge_stride, ptr(h_in), h_out.ctypes.data, h_pitch, ptr(t_inv), flags)
+
+        return self._lookup_quotient(ext_k, a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y, h_in, out, t_inv, divide, canonical, np.uint64, None, call)
+
+    def _lookup_quotient(self, ext_k, a_ext, ap_ext, sp_ext, z_ext, s_ext, selectors, beta, gamma, y, h_in, out, t_inv, divide, canonical, u64, device, call):
+        """what lookup_quotient (torch) and lookup_quotient_host (numpy, device None) share: the shapes, the strides, the output buffer — the caller's or a fresh
+        one of pitch 2^ext_k — and the call: call(b_count, pitch, s_pitch, s_stride, sel_pitch, challenge_stride, h_out, h_pitch, flags)"""
+        ncols = 3 * self.num_defs
+        contiguous = lambda t: t.is_contiguous() if device is not None else t.flags.c_contiguous
+        for name, t in (("a_ext", a_ext), ("ap_ext", ap_ext), ("sp_ext", sp_ext), ("z_ext", z_ext)):
+            if t.dtype != u64 or not contiguous(t) or len(t.shape) != 4 or t.shape[0] != ncols or t.shape[3] != 4 or tuple(t.shape) != tuple(z_ext.shape):
+                raise HrxError(HRX_ERR_ARG, "%s: contiguous 64-bit limbs of shape [%d][b_count][pitch][4], the four alike" % (name, ncols))
+        b_count, pitch = z_ext.shape[1], z_ext.shape[2]
+        if s_ext.dtype != u64 or not contiguous(s_ext) or s_ext.shape[0] != ncols or s_ext.shape[-1] != 4 or \
+                not (len(s_ext.shape) == 3 or (len(s_ext.shape) == 4 and s_ext.shape[1] == b_count)):
+            raise HrxError(HRX_ERR_ARG, "s_ext: contiguous 64-bit limbs of shape [%d][s_pitch][4] or [%d][%d][s_pitch][4]" % (ncols, ncols, b_count))
+        if selectors.dtype != u64 or not contiguous(selectors) or len(selectors.shape) != 3 or selectors.shape[0] != 3 or selectors.shape[2] != 4:
+            raise HrxError(HRX_ERR_ARG, "selectors: contiguous 64-bit limbs of shape [3][sel_pitch][4]")
+        cs = _theta_stride(beta, b_count, u64)
+        if _theta_stride(gamma, b_count, u64) != cs or _theta_stride(y, b_count, u64) != cs:
+            raise HrxError(HRX_ERR_ARG, "beta, gamma and y: all (4,) or all (%d, 4)" % b_count)
+        for name, t in (("h_in", h_in), ("out", out)):
+            if t is not None and (t.dtype != u64 or not contiguous(t) or len(t.shape) != 3 or t.shape[0] != b_count or t.shape[2] != 4):
+                raise HrxError(HRX_ERR_ARG, "%s: contiguous 64-bit limbs of shape [%d][h_pitch][4]" % (name, b_count))
+        if h_in is not None and out is not None and h_in.shape[1] != out.shape[1]:
+            raise HrxError(HRX_ERR_ARG, "h_in and out: one h_pitch")
+        if t_inv is not None and (t_inv.dtype != u64 or not contiguous(t_inv) or len(t_inv.shape) != 2 or t_inv.shape[1] != 4):
+            raise HrxError(HRX_ERR_ARG, "t_inv: contiguous 64-bit limbs of shape [2^(ext_k - k)][4]")
+        if out is None:
+            out = _out_buffer(None, "out", (b_count, h_in.shape[1] if h_in is not None else max(1 << int(ext_k), 4), 4), u64, device, zeros=True)
+        _check(call(b_count, pitch, s_ext.shape[-2], 1 if len(s_ext.shape) == 4 else 0, selectors.shape[1], cs, out, out.shape[1],
+                    (FR_CANONICAL if canonical else 0) | (QUOTIENT_DIVIDE if divide else 0)))
+        return out
+
+    def lookup_quotient_selectors(self, k, ext_k, n_rows, shift, canonical=False, device=None, workspaces=None):
+        """The selector columns lookup_quotient reads — l0 (the Lagrange basis polynomial of row 0), l_last (of row n_rows) and l_active (the sum of the bases
+        of rows [0, n_rows)) — on the extended coset of generator `shift`, as limbs [3][2^ext_k][4]: three unit or indicator columns of 2^k rows through the
+        existing transforms, inverse at k, then forward at ext_k with n_in = 2^k and the shift.  device None: numpy through fr_ntt_host (shift uint64 (4,));
+        else torch through fr_ntt on that device (shift int64 CUDA limbs; workspaces: (fr_ntt_prepare(k), fr_ntt_prepare(ext_k)), prepared here where not
+        given).  n_rows < 2^k.  Once per (k, ext_k, n_rows, shift)."""
+        k, ext_k, n_rows = int(k), int(ext_k), int(n_rows)
+        if not (1 <= k < ext_k <= 24) or not 0 <= n_rows < (1 << k):
+            raise HrxError(HRX_ERR_ARG, "lookup_quotient_selectors: 1 <= k < ext_k <= 24, 0 <= n_rows < 2^k")
+        n = 1 << k
+        one = np.array(fr_from_u64(1, canonical), np.uint64)
+        cols = np.zeros((3, max(n, 4), 4), np.uint64)
+        cols[0, 0] = one
+        cols[1, n_rows] = one
+        cols[2, :n_rows] = one
+        if device is None:
+            coeff = self.fr_ntt_host(cols, k, inverse=True, n_in=n, canonical=canonical)
+            return self.fr_ntt_host(coeff, ext_k, n_in=n, shift=shift, canonical=canonical)
+        cols = torch.from_numpy(cols.view(np.int64)).to(device)
+        ws_k, ws_ext = workspaces if workspaces is not None else (None, None)
+        coeff = self.fr_ntt(cols, k, workspace=ws_k, inverse=True, n_in=n, canonical=canonical)
+        return self.fr_ntt(coeff, ext_k, workspace=ws_ext, n_in=n, shift=shift, canonical=canonical)
+
     def witness_batch(self, chars, lens, out=None, stream=None):
         """Device-resident batch: chars (B, stride) uint8 CUDA tensor (stride % 16 == 0), lens (B,) int32 CUDA tensor.
         Asynchronous on `stream` (default: torch's current stream).  Returns (records, masked, status) tensors whose
@@ -1893,6 +2020,7 @@ FR_LOOKUP_COLUMN_NAMES = lambda D: [n % d for d in range(D) for n in ("trans[%d]
 
 
 FR_NTT_INVERSE = 2                     # HRX_NTT_INVERSE
+QUOTIENT_DIVIDE = 4                    # HRX_QUOTIENT_DIVIDE
 FR_S = 28                              # bn256::Fr's two-adicity (halo2curves): r - 1 = 2^28 * odd, the multiplicative generator 7
 FR_ROOT_OF_UNITY = 0x03ddb9f5166d18b798865ea93dd31f743215cf6dd39329c8d34f1ed960c37c9c      # 7^((r - 1) / 2^28), of order exactly 2^28
 

@@ -9,8 +9,8 @@
 // q = floor(v * R / r) by at most 2, so v * R - q' * r needs at most two corrective subtractions.  Plain C++ (unsigned
 // __int128) so that hipcc compiles it for the kernel and g++/hipcc for the host-side known-answer tests.
 // Below F::from: Fr, an element as a value of eight u32 limbs, and everything the stages compute with one — LOOKUP COMPRESS (hrx_compress.hpp), LOOKUP
-// PRODUCT (hrx_product.hpp), FR NTT (hrx_ntt.hpp) and the field cells (hrx_kernel.hip).  Every function takes and returns Fr by value:
-//   constants   fr_R (the Montgomery one), fr_R2, fr_R5, fr_half, fr_root_of_unity
+// PRODUCT (hrx_product.hpp), FR NTT (hrx_ntt.hpp), LOOKUP QUOTIENT (hrx_quotient.hpp) and the field cells (hrx_kernel.hip).  Every function takes and returns Fr by value:
+//   constants   fr_R (the Montgomery one), fr_R2, fr_R3, fr_R4, fr_R5, fr_half, fr_root_of_unity
 //   arithmetic  fr_add, fr_sub, fr_mul (the Montgomery product), fr_reduce (any 256-bit value mod r), fr_inv (Fermat), fr_pow_u32, fr_square_n,
 //               fr_select, fr_is_zero, fr_eq; fr_powers and fr_fold, the fold of a lookup tuple with a challenge's powers
 //   limb forms  fr_unit, fr_to_mont, fr_from_mont — the one of a call's form, into and out of Montgomery form
@@ -125,6 +125,8 @@ HRX_HD Fr fr_from_u32(uint32_t v, bool canonical = false) {
 constexpr uint32_t kFrInv32 = 0xefffffffu;          // -r^-1 mod 2^32
 constexpr uint32_t kFrR2_32[8] = {0xae216da7u, 0x1bb8e645u, 0xe35c59e3u, 0x53fe3ab1u, 0x53bb8085u, 0x8c49833du, 0x7f4e44a5u, 0x0216d0b1u};   // R^2 mod r
 constexpr uint32_t kFrR5_32[8] = {0xa17a2cefu, 0x00915951u, 0x9fd7425cu, 0xbf25f2ddu, 0xa7eeefb8u, 0xfb6cfdc4u, 0xb32c8ec9u, 0x06eaaa4fu};   // R^5 mod r
+constexpr uint32_t kFrR3_32[8] = {0xb4bf0040u, 0x5e94d8e1u, 0x1cfbb6b8u, 0x2a489cbeu, 0xa19fcfedu, 0x893cc664u, 0x7fcc657cu, 0x0cf8594bu};   // R^3 mod r
+constexpr uint32_t kFrR4_32[8] = {0x00bf2c45u, 0xabbc9482u, 0x4e532f3du, 0x48c48498u, 0xed8c1dd1u, 0x3adf4b7eu, 0xeceb8b73u, 0x1c022fc8u};   // R^4 mod r
 constexpr uint32_t kFrRm2_32[8] = {0xefffffffu, 0x43e1f593u, 0x79b97091u, 0x2833e848u, 0x8181585du, 0xb85045b6u, 0xe131a029u, 0x30644e72u};  // r - 2 (254 bits)
 constexpr uint32_t kFrFoldK = 0xa948e8c4u;          // floor(2^285 / r): the quotient estimate of fr_fold
 // The two-adic subgroup, halo2curves' constants for bn256::Fr: r - 1 = 2^S * odd with S = 28, the multiplicative generator 7, and
@@ -139,6 +141,8 @@ constexpr uint32_t kFrInv2_32[8] = {0x1ffffffeu, 0x783c14d8u, 0x0c8d1eddu, 0xaf9
     HRX_HD constexpr Fr name() { return Fr{{k[0], k[1], k[2], k[3], k[4], k[5], k[6], k[7]}}; }
 HRX_FR_CONSTANT(fr_R, kFrR32)                               // R: the Montgomery form of 1
 HRX_FR_CONSTANT(fr_R2, kFrR2_32)                            // R^2: times it, a plain integer becomes its Montgomery form
+HRX_FR_CONSTANT(fr_R3, kFrR3_32)                            // R^3, R^4: times them, a Montgomery form gains R^2, R^3 (LOOKUP QUOTIENT's selector constants)
+HRX_FR_CONSTANT(fr_R4, kFrR4_32)
 HRX_FR_CONSTANT(fr_R5, kFrR5_32)                            // R^5: times it, a product of four plain integers (x / R^3) becomes its Montgomery form
 HRX_FR_CONSTANT(fr_half, kFrInv2_32)                        // 1 / 2, Montgomery form
 HRX_FR_CONSTANT(fr_root_of_unity, kFrRootOfUnity32)         // ROOT_OF_UNITY, Montgomery form

@@ -235,6 +235,32 @@ class RegexVerifyConfig {
         check(hrx_fr_ntt_host(ctx_, in, in_pitch, out, out_pitch, n_cols, k, n_in, shift, flags));
     }
 
+    // LOOKUP QUOTIENT (include/hrx.h): the lookup argument's five constraints on the extended coset, as the C calls are; flags: HRX_FR_CANONICAL |
+    // HRX_QUOTIENT_DIVIDE
+    void fr_vanishing_inverse_device(unsigned k, unsigned ext_k, const uint64_t *shift, uint64_t *t_inv, int flags, void *stream) const {
+        check(hrx_fr_vanishing_inverse_device(ctx_, k, ext_k, shift, t_inv, flags, stream));
+    }
+    void fr_vanishing_inverse_host(unsigned k, unsigned ext_k, const uint64_t *shift, uint64_t *t_inv, int flags) const {
+        check(hrx_fr_vanishing_inverse_host(ctx_, k, ext_k, shift, t_inv, flags));
+    }
+    void lookup_quotient_device(size_t b_count, unsigned k, unsigned ext_k, const uint64_t *a_ext, const uint64_t *ap_ext, const uint64_t *sp_ext,
+                                const uint64_t *z_ext, size_t pitch, const uint64_t *s_ext, size_t s_pitch, size_t s_stride, const uint64_t *selectors,
+                                size_t sel_pitch, const uint64_t *beta, const uint64_t *gamma, const uint64_t *y, size_t challenge_stride, const uint64_t *h_in,
+                                uint64_t *h_out, size_t h_pitch, const uint64_t *t_inv, int flags, void *stream) const {
+        check(hrx_lookup_quotient_device(ctx_, b_count, k, ext_k, a_ext, ap_ext, sp_ext, z_ext, pitch, s_ext, s_pitch, s_stride, selectors, sel_pitch, beta, gamma, y,
+                                         challenge_stride, h_in, h_out, h_pitch, t_inv, flags, stream));
+    }
+    void lookup_quotient_host(size_t b_count, unsigned k, unsigned ext_k, const uint64_t *a_ext, const uint64_t *ap_ext, const uint64_t *sp_ext,
+                              const uint64_t *z_ext, size_t pitch, const uint64_t *s_ext, size_t s_pitch, size_t s_stride, const uint64_t *selectors,
+                              size_t sel_pitch, const uint64_t *beta, const uint64_t *gamma, const uint64_t *y, size_t challenge_stride, const uint64_t *h_in,
+                              uint64_t *h_out, size_t h_pitch, const uint64_t *t_inv, int flags) const {
+        check(hrx_lookup_quotient_host(ctx_, b_count, k, ext_k, a_ext, ap_ext, sp_ext, z_ext, pitch, s_ext, s_pitch, s_stride, selectors, sel_pitch, beta, gamma, y,
+                                       challenge_stride, h_in, h_out, h_pitch, t_inv, flags));
+    }
+    void lookup_quotient_plan(size_t b_count, unsigned ext_k, size_t *tile_cells, size_t *cells_per_lane) const {
+        check(hrx_ctx_lookup_quotient_plan(ctx_, b_count, ext_k, tile_cells, cells_per_lane));
+    }
+
    private:
     static std::vector<std::vector<uint64_t>> split(const std::vector<uint64_t> &f, size_t D, size_t len) {
         std::vector<std::vector<uint64_t>> o(D);

@@ -472,5 +472,11 @@ hipError_t launch_lookup_product(const ProductArgs &a, hipStream_t stream);
 struct NttArgs;        // hrx_ntt.hpp
 hipError_t launch_ntt_prepare(uint32_t k, uint32_t *ws, hipStream_t stream);
 hipError_t launch_ntt(const NttArgs &a, int device, hipStream_t stream);
+// LOOKUP QUOTIENT (hrx_kernel_quotient.hip): the rule of hrx_quotient.hpp — the table 1 / (X^n - 1) on the coset (one launch of one workgroup), and the
+// five constraints of every lookup folded into the quotient accumulator (one launch)
+struct QuotientArgs;   // hrx_quotient.hpp
+struct VanishArgs;
+hipError_t launch_lookup_quotient(const QuotientArgs &a, hipStream_t stream);
+hipError_t launch_vanishing_inverse(const VanishArgs &a, hipStream_t stream);
 
 }  // namespace hrx

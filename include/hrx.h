@@ -938,6 +938,59 @@ int hrx_ctx_fr_ntt_plan(hrx_ctx *ctx, size_t n_cols, unsigned k, size_t *n_passe
 void hrx_fr_sub(const uint64_t *a, const uint64_t *b, uint64_t *out);
 
 /* ------------------------------------------------------------------ */
+/* LOOKUP QUOTIENT — the lookup argument's five constraints on the extended coset, folded into the quotient and divided by X^n - 1                */
+/* ------------------------------------------------------------------ */
+/* What halo2 does with the columns FR NTT takes to the extended coset: the lookup part of evaluate_h.  n = 2^k, e = ext_k - k, N = 2^ext_k, rot = 2^e; point
+ * j of the extended coset is g w_ext^j, so p(w X) at point j is p at point (j + rot) mod N and p(w^-1 X) is p at point (j - rot) mod N.  For every string
+ * i < b_count, lookups c = 0 .. 3 D - 1 in hrx_lookup_num_columns' order, every point j < N, with v = h_in[j] (0 where h_in is NULL, and then it is never
+ * read), every lookup applies halo2's five steps in halo2's order:
+ *   v = v y + (1 - Z[j]) l0[j]
+ *   v = v y + (Z[j]^2 - Z[j]) l_last[j]
+ *   v = v y + (Z[j + rot] (A'[j] + beta) (S'[j] + gamma) - Z[j] (A[j] + beta) (S[j] + gamma)) l_active[j]
+ *   v = v y + (A'[j] - S'[j]) l0[j]
+ *   v = v y + (A'[j] - S'[j]) (A'[j] - A'[j - rot]) l_active[j]
+ * and h_out[j] = v after the last lookup — v t_inv[j mod rot] with HRX_QUOTIENT_DIVIDE in `flags`.  The implementations regroup the steps (powers of y, the
+ * expressions grouped by selector: 12 products a lookup and point instead of 16); every cell written is a fully reduced element, so the device form equals
+ * the host form limb for limb.  Cells are Montgomery limbs by default, plain integers with HRX_FR_CANONICAL; the expressions are not linear in the cells,
+ * and what the plain form costs is paid per point and string, not per cell (csrc/hrx_quotient.hpp).  Every cell read must be below r; only beta, gamma and y
+ * are reduced by the call.
+ * a_ext, ap_ext, sp_ext, z_ext: [3 D][b_count][pitch][4] u64, the compressed inputs A, the permuted columns A', S' and the grand product Z on the extended
+ * coset (hrx_fr_ntt_* at ext_k with the coset's generator as shift).  s_ext: [3 D][runs][s_pitch][4], the compressed table S the same way; s_stride 0 — one
+ * run for the call; 1 — run i belongs to string i of the window; anything else HRX_ERR_ARG.  selectors: [3][sel_pitch][4] — l0, the Lagrange basis
+ * polynomial of row 0; l_last, that of row n_rows (LOOKUP PERMUTE's and LOOKUP PRODUCT's n_rows: Z's entries [0, n_rows] are the ones the product call
+ * writes); l_active, the sum of the bases of rows [0, n_rows) — on the same coset.  beta, gamma, y: 4 u64 limbs each, 8-byte aligned, in DEVICE memory for
+ * the device form, taken mod r first; challenge_stride in u64 words, one for the three: 4 — per string of the window; 0 — one set for the call.
+ * h_in, h_out: [b_count][h_pitch][4]; h_in NULL, or == h_out (in place), or apart from it; h_out apart from every input.  Entries [0, 2^ext_k) of every
+ * h_out column are written and none above; no input is written.  Pitches in cells, multiples of 4, at least 2^ext_k; cell buffers 16-byte aligned.
+ * 1 <= k, 1 <= ext_k - k <= 6, ext_k <= 24.  t_inv: [2^(ext_k - k)][4], required with HRX_QUOTIENT_DIVIDE and ignored otherwise.
+ * VANISHING INVERSE.  t_inv[c] = 1 / (g^n w_ext^(n c) - 1), c < 2^(ext_k - k): the values X^n - 1 takes on the coset, inverted; the zero cell where that is
+ * zero (g in the subgroup), as in hrx_lookup_invert_table_*.  g is `shift` as FR NTT reads it (the call's limb form, taken mod r first, DEVICE memory for the
+ * device form; NULL: g = 1, where entry 0 is the zero cell).  Once per (k, ext_k, g): one launch of one workgroup, a lane per entry.
+ * Refused with HRX_ERR_ARG, nothing written: NULL or misaligned buffers, k, ext_k, a pitch or a stride out of range, an overlap other than h_in == h_out,
+ * HRX_QUOTIENT_DIVIDE without t_inv, unknown flag bits.  A host-only context: HRX_ERR_HIP for the device forms.
+ * The device form: ONE launch, asynchronous on `stream`; a workgroup takes a tile of consecutive points of one string and carries v in registers across
+ * all 3 D lookups; nothing allocated, no context scratch, no atomics, no grid-wide barrier, deterministic; capturable from a context's first call.
+ * b_count == 0 launches nothing. */
+enum { HRX_QUOTIENT_DIVIDE = 4 };   /* beside HRX_FR_CANONICAL in `flags` */
+int hrx_fr_vanishing_inverse_device(hrx_ctx *ctx, unsigned k, unsigned ext_k, const uint64_t *shift, uint64_t *t_inv, int flags, void *stream);
+int hrx_lookup_quotient_device(hrx_ctx *ctx, size_t b_count, unsigned k, unsigned ext_k,
+                               const uint64_t *a_ext, const uint64_t *ap_ext, const uint64_t *sp_ext, const uint64_t *z_ext, size_t pitch,
+                               const uint64_t *s_ext, size_t s_pitch, size_t s_stride, const uint64_t *selectors, size_t sel_pitch,
+                               const uint64_t *beta, const uint64_t *gamma, const uint64_t *y, size_t challenge_stride,
+                               const uint64_t *h_in, uint64_t *h_out, size_t h_pitch, const uint64_t *t_inv, int flags, void *stream);
+/* The same with everything in HOST memory, on a host-only or a device context, the quotient over HRX_OPT_HOST_THREADS threads by ranges of strings.  The
+ * definition of the cells. */
+int hrx_fr_vanishing_inverse_host(hrx_ctx *ctx, unsigned k, unsigned ext_k, const uint64_t *shift, uint64_t *t_inv, int flags);
+int hrx_lookup_quotient_host(hrx_ctx *ctx, size_t b_count, unsigned k, unsigned ext_k,
+                             const uint64_t *a_ext, const uint64_t *ap_ext, const uint64_t *sp_ext, const uint64_t *z_ext, size_t pitch,
+                             const uint64_t *s_ext, size_t s_pitch, size_t s_stride, const uint64_t *selectors, size_t sel_pitch,
+                             const uint64_t *beta, const uint64_t *gamma, const uint64_t *y, size_t challenge_stride,
+                             const uint64_t *h_in, uint64_t *h_out, size_t h_pitch, const uint64_t *t_inv, int flags);
+/* How a device quotient call cuts its work: a workgroup takes *tile_cells consecutive points of one string, *cells_per_lane per lane.  For tests and tools;
+ * the cells do not depend on it. */
+int hrx_ctx_lookup_quotient_plan(hrx_ctx *ctx, size_t b_count, unsigned ext_k, size_t *tile_cells, size_t *cells_per_lane);
+
+/* ------------------------------------------------------------------ */
 /* SURVEY §8 f3 — from the compact records to what the reference's fill consumes (host only, no context, re-entrant)   */
 /* ------------------------------------------------------------------ */
 /* One circuit: EXACTLY the Vecs the three derive_* calls at the top of match_substrs return (src/lib.rs:316-318), out of the string's compact records, so that the body
